@@ -10,6 +10,15 @@ configs[3]: 32768 sharded over 8 GPUs = 4096 per GPU, i.e. weak scaling), fp32, 
 "U11L-128"  with trained random-init weights.  Inputs are resident in HBM before
 the timed region; for N > 1 every step ends with the RCCL all-gather of the first 20 slow
 features (north_star).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline fields: metric, value, unit,
+higher_is_better, dtype, ms_per_step, config).  Everything beside the headline — per-kernel event times and the
+roofline, batches in flight, parity against the oracle, the frame leg, the extra legs, the CPU baselines — runs
+only with --full (the --no-* switches then leave out single parts of it, as before).
+
+--dump-outputs DIR writes what the last timed step returned (the float32 features a caller of the step receives,
+(world * rows, 20)) to DIR/features.npy; inputs and weights are seeded, so runs with the same arguments are
+comparable output for output.
 """
 from __future__ import annotations
 
@@ -463,11 +472,11 @@ def main():
     ap.add_argument("--rows", type=int, default=ROWS_PER_GPU, help="sub-images per GPU per step")
     ap.add_argument("--input-dtype", default="float32", choices=["float32", "uint8", "float64"])
     ap.add_argument("--generic", action="store_true", help="force the generic plan (diagnostic)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-frame", action="store_true", help="skip the configs[2] frame leg (frames_per_s)")
-    ap.add_argument("--no-inflight", action="store_true", help="skip the batches-in-flight figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-frame", action="store_true", help="with --full: skip the configs[2] frame leg (frames_per_s)")
+    ap.add_argument("--no-inflight", action="store_true", help="with --full: skip the batches-in-flight figure")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip host_path / u11l_64 / train_leg / uniform_input (figures beside the headline, outside the timed region)")
+                    help="with --full: skip host_path / u11l_64 / train_leg / uniform_input (figures beside the headline, outside the timed region)")
     ap.add_argument("--gather-stream", default="side", choices=["side", "same"],
                     help="distributed path: the all-gather on a side stream under the next step's kernels (default) or on the kernels' own stream")
     ap.add_argument("--compare-collective", action="store_true",
@@ -475,7 +484,14 @@ def main():
                          "same-stream gather in THIS process (collective_compare in the line; VERDICT r4 item 3)")
     ap.add_argument("--node-kind", default="pca_exp_sfa", choices=["pca_exp_sfa", "igsfa"],
                     help="node type of the synthetic 11-layer net (default: the BASELINE.md workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the figures beside it: per-kernel times + roofline, batches in flight, oracle parity, "
+                         "frame leg, extra legs, CPU baselines (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the features the last timed step returned to DIR/features.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
 
@@ -584,7 +600,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y_last = step()
     torch.cuda.synchronize(dev)      # every stream of the device: kernels and the last gathers
     if distributed:
         dist.barrier()
@@ -602,6 +618,10 @@ def main():
         blocks = sf.y_alls[(sf._n - 1) & 1].view(world, rows, N_COLS)
         if not bool((blocks.abs().amax(dim=(1, 2)) > 0).all()) or (world > 1 and torch.equal(blocks[0], blocks[1])):
             raise SystemExit("bench.py: all-gather result misses a rank's block")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, copied out before anything else runs on the device
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "features.npy"), y_last.cpu().numpy().astype(np.float32))
     # --- the same step with and without the collective, in THIS process (--compare-collective; every rank runs every variant)
     collective_compare = None
     if distributed and args.compare_collective:
@@ -639,7 +659,7 @@ def main():
     # --- per-kernel durations: HIP events recorded by the library around every stage launch, on
     # the stream the kernels run on (separate passes, outside the timed region)
     stage_rows = []
-    if rank == 0:
+    if rank == 0 and args.full:
         L = None
         from pyfaceanalysis_amd import _capi
         L = _capi.lib()
@@ -665,7 +685,7 @@ def main():
     # three of them in flight on their own streams, each with its own flow handle and workspace: the ramp and the tail of
     # one batch's kernels (SIMD arbiter skew) are filled by the other's.  Same K full steps, same results.
     in_flight = None
-    if not distributed and not args.no_inflight and not args.generic:
+    if args.full and not distributed and not args.no_inflight and not args.generic:
         in_flight = {}
         extra_flows = [Flow.from_blob(blob, device=local_rank, output_dtype=np.float32) for _ in range(2)]
         for f in extra_flows:
@@ -690,16 +710,17 @@ def main():
             f.close()
 
     if rank == 0:
-        # parity of the timed configuration on a slice of the batch (oracle = checker only)
-        from oracle import mdp_restate
-        m = 64
-        check_rows = np.arange(m) * (rows // m) if rows >= m else np.arange(rows)      # rows 0, rows/64, 2 rows/64, ...: every part of the batch
-        m = len(check_rows)
-        ref = mdp_restate.execute_flow(nodes, x_host[check_rows].astype(np.float64))[:, :N_COLS]
-        got = y.cpu().numpy()[check_rows].astype(np.float64)
-        max_rel = float(np.abs(got - ref).max() / np.abs(ref).max())
-        # worst case per column over the first 20: each column against ITS OWN largest reference magnitude
-        per_col = np.abs(got - ref).max(axis=0) / np.abs(ref).max(axis=0)
+        if args.full:
+            # parity of the timed configuration on a slice of the batch (oracle = checker only)
+            from oracle import mdp_restate
+            m = 64
+            check_rows = np.arange(m) * (rows // m) if rows >= m else np.arange(rows)      # rows 0, rows/64, 2 rows/64, ...: every part of the batch
+            m = len(check_rows)
+            ref = mdp_restate.execute_flow(nodes, x_host[check_rows].astype(np.float64))[:, :N_COLS]
+            got = y.cpu().numpy()[check_rows].astype(np.float64)
+            max_rel = float(np.abs(got - ref).max() / np.abs(ref).max())
+            # worst case per column over the first 20: each column against ITS OWN largest reference magnitude
+            per_col = np.abs(got - ref).max(axis=0) / np.abs(ref).max(axis=0)
 
         total_rows = rows * world
         value = total_rows * args.steps / elapsed
@@ -784,19 +805,19 @@ def main():
                                                                      (", RCCL all-gather of the features " + ("on the kernels' stream" if args.gather_stream == "same" else "overlapped with the next step")) if distributed else ""),
                        "settle_ms": round(settle_ms, 1), "rows_per_gpu": rows, "global_rows": total_rows, "plan": "fused" if info.plan_kind == 1 else "generic",
                        "parallelism": "row-shard x%d" % world, **({"gather_events": gather_events} if gather_events else {})},
-            "max_rel_err_vs_oracle": max_rel,
-            "max_rel_err_first20_percol": {"worst": float(per_col.max()), "worst_column": int(per_col.argmax()),
-                                           "per_column": [float("%.3e" % v) for v in per_col], "rows_checked": m,
-                                           "row_set": "rows k * %d, k = 0 .. %d (strided over the whole batch)" % (max(1, rows // 64), m - 1),
-                                           "definition": "max_i |y[i,c] - ref[i,c]| / max_i |ref[i,c]| per column c"},
+            **({"max_rel_err_vs_oracle": max_rel,
+                "max_rel_err_first20_percol": {"worst": float(per_col.max()), "worst_column": int(per_col.argmax()),
+                                               "per_column": [float("%.3e" % v) for v in per_col], "rows_checked": m,
+                                               "row_set": "rows k * %d, k = 0 .. %d (strided over the whole batch)" % (max(1, rows // 64), m - 1),
+                                               "definition": "max_i |y[i,c] - ref[i,c]| / max_i |ref[i,c]| per column c"}} if args.full else {}),
             "flops_per_subimage": flops_row, "padded_flops_per_subimage": int(info.padded_flops_per_row),
-            "roofline": roof,
+            **({"roofline": roof} if args.full else {}),
         }
         if in_flight is not None:
             out["batches_in_flight"] = in_flight
         if collective_compare is not None:
             out["collective_compare"] = collective_compare
-        if not args.no_frame and world == 1 and info.plan_kind == 1 and args.node_kind == "pca_exp_sfa":
+        if args.full and not args.no_frame and world == 1 and info.plan_kind == 1 and args.node_kind == "pca_exp_sfa":
             try:
                 fr = frame_leg(flow, dev, flow_factory=lambda: Flow.from_blob(blob, device=local_rank, output_dtype=np.float32))
                 out["frames_per_s"] = fr["frames_per_s"]                 # one frame at a time (latency figure)
@@ -805,7 +826,7 @@ def main():
                 out["frame_leg"] = fr
             except Exception as exc:      # noqa: BLE001
                 out["frame_leg"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        if not args.no_extra_legs and world == 1 and info.plan_kind == 1 and args.node_kind == "pca_exp_sfa" and rows == ROWS_PER_GPU:
+        if args.full and not args.no_extra_legs and world == 1 and info.plan_kind == 1 and args.node_kind == "pca_exp_sfa" and rows == ROWS_PER_GPU:
             leg_steps = max(50, min(args.steps, 400))
             # figures beside the headline: a leg that fails reports its error and leaves the headline line intact
             for key, leg in (("uniform_input", lambda: uniform_leg(flow, nodes, dev, rows, leg_steps)), ("u11l_64", lambda: u11l_64_leg(dev, rows, leg_steps)),
@@ -814,7 +835,7 @@ def main():
                     out[key] = leg()
                 except Exception as exc:      # noqa: BLE001
                     out[key] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(nodes)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
             op = out["cpu_baseline"].get("optimised_port")

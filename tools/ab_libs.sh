@@ -2,7 +2,7 @@
 # Every round runs each library once, in order; prints value, ms/step and the per-stage event times.
 cd $GRAFT_REPO_ROOT
 N=${1:-2}; shift
-run() { HIGSFA_LIB="$2" timeout -k 10 200 python bench.py --no-cpu-baseline --no-frame --no-inflight --no-extra-legs 2>/dev/null | python -c "
+run() { HIGSFA_LIB="$2" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-frame --no-inflight --no-extra-legs 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$1'.ljust(34), round(d['value']),round(d['ms_per_step'],4),[round(x*1e3,1) for x in d['roofline']['stages_ms'][:9]])"; }
 for i in $(seq $N); do
   for L in "$@"; do
