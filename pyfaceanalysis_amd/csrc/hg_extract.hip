@@ -395,8 +395,7 @@ void launch_gather(const void* frame, int64_t ld, int fw, const int32_t* tabs, i
                    hipStream_t st) {
     if constexpr (sizeof(FT) == 1) {
         const int tpr = w >> 4;
-        static const bool v1 = getenv("HIGSFA_EXTENT_V1") != nullptr;      // (A/B: the four-pixels-per-thread kernel for every shape)
-        if (!v1 && out_dtype == HG_U8 && (w & 15) == 0 && tpr >= 1 && tpr <= 256 && (tpr & (tpr - 1)) == 0 && ((w + h) & 3) == 0 && (ldo & 15) == 0 &&
+        if (out_dtype == HG_U8 && (w & 15) == 0 && tpr >= 1 && tpr <= 256 && (tpr & (tpr - 1)) == 0 && ((w + h) & 3) == 0 && (ldo & 15) == 0 &&
             ((uintptr_t)out & 15) == 0 && ((uintptr_t)tabs & 15) == 0) {
             // whole windows per workgroup while that leaves >= 1024 workgroups, else row chunks (the column indices are read once per chunk)
             const int rows_per_pass = 256 / tpr;

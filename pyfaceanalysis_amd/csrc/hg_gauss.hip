@@ -265,34 +265,19 @@ int hg_gauss_regression_multi_device(hg_gauss* const* gs, int m, const void* x, 
         }
         GaussMulti M;
         for (int s = 0; s < m; ++s) M.g[s] = hg::gauss_params(gs[s]);
-        // eight rows per workgroup where the batch has them (every workgroup streams its classifier's matrices through L2 once for its
-        // rows: 348 rows x 4 pose regressors moved 56 MB at four rows per workgroup and took 14 us whatever the batch)
-        // (measured and not used, round 5: 16.0-17.9 us per launch against 14.1-15.2 at four rows — the launch is bound by the chain of
-        // fp64 FMAs per thread, not by L2; the instantiation stays for HIGSFA_GAUSS_R8=1)
-        const bool r8 = r4 && n >= 64 && kd_max <= 2048 && getenv("HIGSFA_GAUSS_R8") != nullptr;
-        const int R = r8 ? 8 : r4 ? 4 : 1;
+        // (eight rows per workgroup, measured and dropped in round 5: 16.0-17.9 us per launch against 14.1-15.2 at four rows — the
+        // launch is bound by the chain of fp64 FMAs per thread, not by L2.)  R <= 4 and K d <= 1536 at R = 4: at most 51 200 B of LDS.
+        const int R = r4 ? 4 : 1;
         const size_t lds = (size_t)R * (64 + kd_max) * 8;
         const dim3 grid((unsigned)((n + R - 1) / R), (unsigned)m);
         hipStream_t st = (hipStream_t)stream;
-#define HG_GAUSS_WGM(TT, RR)                                                                                                                  \
-    do {                                                                                                                                       \
-        if (lds > 64 * 1024) {                                                                                                                 \
-            static bool raised = false;      /* once per instantiation */                                                                      \
-            if (!raised) HG_HIP(hipFuncSetAttribute((const void*)k_gauss_regression_wg_multi<TT, RR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            raised = true;                                                                                                                     \
-        }                                                                                                                                      \
-        hipLaunchKernelGGL((k_gauss_regression_wg_multi<TT, RR>), grid, dim3(256), lds, st, (const TT*)x, ldx, n, M, out_reg, out_stride);     \
-    } while (0)
         if (x_dtype == HG_F32) {
-            if (r8) HG_GAUSS_WGM(float, 8);
-            else if (r4) HG_GAUSS_WGM(float, 4);
-            else HG_GAUSS_WGM(float, 1);
+            if (r4) hipLaunchKernelGGL((k_gauss_regression_wg_multi<float, 4>), grid, dim3(256), lds, st, (const float*)x, ldx, n, M, out_reg, out_stride);
+            else hipLaunchKernelGGL((k_gauss_regression_wg_multi<float, 1>), grid, dim3(256), lds, st, (const float*)x, ldx, n, M, out_reg, out_stride);
         } else {
-            if (r8) HG_GAUSS_WGM(double, 8);
-            else if (r4) HG_GAUSS_WGM(double, 4);
-            else HG_GAUSS_WGM(double, 1);
+            if (r4) hipLaunchKernelGGL((k_gauss_regression_wg_multi<double, 4>), grid, dim3(256), lds, st, (const double*)x, ldx, n, M, out_reg, out_stride);
+            else hipLaunchKernelGGL((k_gauss_regression_wg_multi<double, 1>), grid, dim3(256), lds, st, (const double*)x, ldx, n, M, out_reg, out_stride);
         }
-#undef HG_GAUSS_WGM
         HG_HIP(hipGetLastError());
     });
     if (rc != HG_OK) hg::set_last_error(g_gauss_error);

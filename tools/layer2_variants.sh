@@ -1,4 +1,4 @@
-for v in "" "HIGSFA_NO_PACK=1" "HIGSFA_NO_PREFETCH_ALL=1" "HIGSFA_NO_REM4=1"; do
+for v in "" "HIGSFA_NO_PACK=1" "HIGSFA_NO_REM4=1"; do
   env $v python bench.py --full --no-frame --no-extra-legs --no-cpu-baseline --no-inflight --steps 300 --warmup 100 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
