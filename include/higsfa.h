@@ -307,6 +307,64 @@ int hg_cascade_detect_frame_device(hg_cascade* c, const void* frame_dev, int fra
 int hg_cascade_grid_device(int device, const hg_cascade_level* levels, int n_levels, double* boxes_dev, double* level_dev,
                            int64_t cap, int64_t* n0, void* stream);
 
+/* --- Eye localisation and duplicate purge after the face cascade (FaceDetectUpdated.py:947-1041, :1180) -------------------
+ * For the survivors of one frame (boxes (n,4), angles (n)), on the frame the cascade read:
+ *   eye boxes      compute_approximate_eye_boxes_coordinates(box, 0.825, 2.3719, rot_angle=angle) (face_analysis.py:61-133), float64
+ *                  in its own operation order; left boxes are rows 0..n-1 of every 2n-row intermediate, right boxes rows n..2n-1.
+ *                  The right eye goes through the left eye's procedure unchanged (find_Right_eyes, face_analysis.py:1022-1033,
+ *                  passes the unswapped box with left_eye=1; the swap back cannot move the box centre).
+ *   patches        eye_w x eye_h windows rotated by delta_ang = -angle, the patcher's NEAREST / EXTENT rule, then the contrast
+ *                  step: per patch, from exact int64 sums S1 = sum p, S2 = sum p^2 over N = w*h pixels (zeros outside the frame),
+ *                  mean = S1/N, std = sqrt((N*S2 - S1^2) / (N*N)); p' = clip((p - mean) / (std / target_std + 1e-8) + target_mean,
+ *                  0, 255) as float32 (image_array_contrast_normalize_avg_std, face_analysis.py:318-327; the mapping of the
+ *                  reference's obj_avg / obj_std to pixel units is not known: the targets are the caller's).
+ *   networks       EyeLX / EyeLY (networks[num_networks-5], [num_networks-4]): one hg_flow_execute_device over the 2n rows when
+ *                  both stages name one flow, then one hg_gauss_regression_multi_device for both classifiers.
+ *   too far        |reg| >= tolerance for either classifier and either eye (face_analysis.py:1073).
+ *   shift          reg / eye_sampling * box side / regression size, rotated by -angle, subtracted from the eye box; the eye is the
+ *                  box centre (face_analysis.py:1075-1104, FaceDetectUpdated.py:1008-1009). */
+typedef struct hg_eyes hg_eyes;
+typedef struct hg_eye_consts {
+    double eye_regression_width, eye_regression_height;  /* Pipeline header line 3: 64 64 (face_analysis.py:395-400)      */
+    double face_sampling, eye_sampling;                   /* 0.825, 2.3719 (FaceDetectUpdated.py:948, :1074-1082)          */
+    double tolerance;                                     /* tolerance_xy_eye 9.0 (face_analysis.py:1018)                  */
+    double target_mean, target_std;                       /* contrast targets in pixel units: required, no default          */
+    int32_t eye_w, eye_h;                                 /* eye_subimage_width x eye_subimage_height: 64 x 64              */
+    int32_t n_features;                                   /* feature columns kept per row (>= both classifiers' input_dim) */
+    int32_t reserved;                                     /* 0                                                              */
+} hg_eye_consts;
+/* flow_x / flow_y must live on `device` (they run with float32 output), input width eye_w * eye_h; the classifiers on `device`
+ * with input_dim <= n_features.  HG_ERR_ARG / HG_ERR_DIM on a violation.  The handles stay owned by the caller. */
+int hg_eyes_create(hg_flow* flow_x, hg_gauss* clf_x, hg_flow* flow_y, hg_gauss* clf_y, const hg_eye_consts* consts, int device,
+                   hg_eyes** out);
+void hg_eyes_free(hg_eyes* e);
+/* The eye step for n faces, BEFORE the discard: frame_dev (h, w) uint8 on the device, row stride ld; boxes_dev (n,4) and angles_dev (n)
+ * float64 on the device.  Outputs (device): eye_coords_dev (n,4) = (eyeL_x, eyeL_y, eyeR_x, eyeR_y), too_far_dev (n) 0/1;
+ * patches_dev (nullable) the contrast-normalised patches (2n, eye_w*eye_h) float32; reg_dev (nullable) the regressions (2, 2n) float64,
+ * row 0 EyeLX, row 1 EyeLY.  Enqueued on `stream`. */
+int hg_eyes_locate_device(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_dev,
+                          const double* angles_dev, int64_t n, double* eye_coords_dev, uint8_t* too_far_dev, float* patches_dev,
+                          double* reg_dev, void* stream);
+/* The eye boxes alone (the first step of hg_eyes_locate_device, exported for callers that drive the steps themselves): eye_boxes_dev
+ * (2n, 4) float64, left boxes then right boxes; delta_angs_dev (nullable, 2n) the rotation their patches are cut with (-angle). */
+int hg_eyes_boxes_device(hg_eyes* e, const double* boxes_dev, const double* angles_dev, int64_t n, double* eye_boxes_dev, double* delta_angs_dev,
+                         void* stream);
+/* purgue_detected_faces_angles_eyes_confidence (face_analysis.py:186-221) on the device, one workgroup: rows_dev (n,10) float64
+ * (x0, y0, x1, y1, angle, eyeL_x, eyeL_y, eyeR_x, eyeR_y, confidence).  w = (1 - conf) * |eyeR - eyeL|, w / max(w); rows in the order
+ * of numpy.argsort(w, kind="stable")[::-1] (NaN first; the reference's argsort is not stable, the build pins this tie rule); the
+ * greedy pass keeps a row whose smallest relative_error_detection against the rows kept so far is > 0.25, IEEE semantics.
+ * out_rows_dev receives the kept rows in order and needs room for n + 1 rows (the reference's loop appends its first row a second
+ * time when that row's eye distance is zero); *count_dev (device int32) their number.  Synchronous (it owns a scratch buffer). */
+int hg_purge_detections_device(int device, const double* rows_dev, int64_t n, double* out_rows_dev, int32_t* count_dev, void* stream);
+/* One frame, one host call: hg_cascade_detect_frame_device's prescale, grid and stage loop, then the eye step on the survivors (on the
+ * frame the cascade read), the discard of the too-far faces (order kept), the row assembly and the purge.  The host reads nothing
+ * between the cascade's last survivor count and the final count.  out_rows (host): room for out_cap faces of 10 doubles; the call fails
+ * with HG_ERR_ARG, writing no row, when more faces remain.  *n_before_purge: faces after the discard.  Synchronous. */
+int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld,
+                                         int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows,
+                                         int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, int32_t* stage_counts,
+                                         int64_t* rows_executed, void* stream);
+
 /* --- SFA training step for one layer of nodes (BASELINE.json configs[4]) -----
  * Not on the reference's path (it never trains, face_analysis.py:451-479); restates
  * mdp.nodes.SFANode train/stop_training per node k over input columns conn[k*d .. (k+1)*d):

@@ -208,6 +208,34 @@ class DeviceCascade(object):
         return dict(coords=coords[:n].copy(), angles=angles[:n].copy(), orig_index=oidx[:n].astype(np.int64), confidence=conf[:n].copy(),
                     counts=counts.tolist(), rows_executed=rows.value, n_windows=n0)
 
+    def detect_faces(self, frame, eyes, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+        """detect_frame, then the eye step (``eyes``: an ``eyes.EyeLocator`` on this device) on the survivors, on the frame the cascade
+        read, the discard of the too-far faces, one row per face and the purge — as ONE host call
+        (hg_cascade_detect_faces_frame_device; FaceDetectUpdated.py:947-1041, :1180).  Returns faces (m, 10) = (x0, y0, x1, y1, angle,
+        eyeL_x, eyeL_y, eyeR_x, eyeR_y, confidence), n_before_purge, counts, rows_executed, n_windows.  The frame is checked on every
+        call; everything that depends only on the frame size is computed once and kept."""
+        from .eyes import check_frame
+        t, L = self.torch, _capi.lib()
+        check_frame(t, frame, self.dev)
+        if eyes.device != self.device:
+            raise ValueError("eye locator on device %d, cascade on device %d" % (eyes.device, self.device))
+        fh, fw = int(frame.shape[0]), int(frame.shape[1])
+        key = ("faces", fw, fh, float(smallest_face), int(prescale_size or 0))
+        plan = self._frames.get(key)
+        if plan is None:
+            pw, ph = grid.prescaled_size(fw, fh, prescale_size) if prescale_size else (fw, fh)
+            pre = (pw, ph) if (pw, ph) != (fw, fh) else (0, 0)
+            levels, n_levels, n0 = frame_levels(pw, ph, smallest_face, self.pipeline, (self.w, self.h))
+            rows, counts = np.empty((n0 + 1, 10)), np.zeros(len(self.stages), dtype=np.int32)      # the purge may keep n + 1 rows
+            plan = self._frames[key] = (pre, levels, n_levels, n0, rows, counts, C.c_int64(), C.c_int64(), C.c_int64())
+        pre, levels, n_levels, n0, rows, counts, n_out, n_before, n_rows = plan
+        _capi.check(L.hg_cascade_detect_faces_frame_device(
+            self._handle(), eyes._handle(), frame.data_ptr(), fh, fw, frame.stride(0), pre[0], pre[1], levels, n_levels,
+            rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(n_out), C.byref(n_before), counts.ctypes.data_as(C.c_void_p), C.byref(n_rows),
+            t.cuda.current_stream(self.dev).cuda_stream))
+        return dict(faces=rows[:n_out.value].copy(), n_before_purge=n_before.value, counts=counts.tolist(), rows_executed=n_rows.value,
+                    n_windows=n0)
+
     def close(self):
         if self._h is not None:
             _capi.lib().hg_cascade_free(self._h)

@@ -17,7 +17,12 @@
 #include "hg_common.hpp"
 #include "hg_gauss_dev.hpp"
 
-namespace hg { void set_last_error(const std::string& s); }
+namespace hg {
+void set_last_error(const std::string& s);
+void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
+                     const double* conf, int64_t n, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st);
+int eyes_device(const hg_eyes* e);
+}
 
 namespace {
 
@@ -658,7 +663,7 @@ uint64_t key_of(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
 
 void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
                  const LevelTable* T, int64_t n0, double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence,
-                 int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
+                 int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr) {
     if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
     if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
     if (n0 > 0 && (!frame_dev || (!T && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
@@ -831,6 +836,38 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
     }
     *n_out = n_bound;
     if (rows_executed) *rows_executed = rows;
+    if (final_buf) *final_buf = cur;      // the survivors stay in coords[cur], angles[cur], conf[cur] until the next call
+}
+
+// FaceDetectUpdated.py:551-561: im.resize((w, h), NEAREST) before the grid is laid out — PIL's nearest resize is the EXTENT rule over
+// the whole frame (tested against PIL), so the patcher does it, into a buffer that lives with the cascade (prescale_w = 0: none).
+// fr / fh / fw / fld: the frame the grid and the stage loop read.
+void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
+                    const void*& fr, int& fh, int& fw, int64_t& fld) {
+    fr = frame_dev;
+    fh = frame_h;
+    fw = frame_w;
+    fld = ld;
+    if (prescale_w > 0 || prescale_h > 0) {
+        if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
+        set_dev(c->device);
+        if (c->pre_src_w != frame_w || c->pre_src_h != frame_h) {
+            const double box[4] = {0.0, 0.0, (double)frame_w, (double)frame_h};
+            c->pre_box.upload(box, sizeof box);
+            c->pre_src_w = frame_w;
+            c->pre_src_h = frame_h;
+        }
+        c->pre_frame.alloc((size_t)prescale_w * prescale_h);
+        const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
+        if (hg_patcher_extract_keyed_device(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), frame_dev, HG_U8, frame_h, frame_w, ld,
+                                            (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8,
+                                            (int64_t)prescale_w * prescale_h, stream) != HG_OK)
+            hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
+        fr = c->pre_frame.p;
+        fh = prescale_h;
+        fw = prescale_w;
+        fld = prescale_w;
+    }
 }
 
 }  // namespace
@@ -863,33 +900,35 @@ int hg_cascade_detect_frame_device(hg_cascade* c, const void* frame_dev, int fra
     return guarded([&] {
         if (!c) hg::fail(HG_ERR_ARG, "null argument");
         const LevelTable T = make_level_table(levels, n_levels);
-        const void* fr = frame_dev;
-        int fh = frame_h, fw = frame_w;
-        int64_t fld = ld;
-        if (prescale_w > 0 || prescale_h > 0) {
-            // FaceDetectUpdated.py:551-561: im.resize((w, h), NEAREST) before the grid is laid out — PIL's nearest resize is the EXTENT
-            // rule over the whole frame (tested against PIL), so the patcher does it, into a buffer that lives with the cascade
-            if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
-            set_dev(c->device);
-            if (c->pre_src_w != frame_w || c->pre_src_h != frame_h) {
-                const double box[4] = {0.0, 0.0, (double)frame_w, (double)frame_h};
-                c->pre_box.upload(box, sizeof box);
-                c->pre_src_w = frame_w;
-                c->pre_src_h = frame_h;
-            }
-            c->pre_frame.alloc((size_t)prescale_w * prescale_h);
-            const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
-            if (hg_patcher_extract_keyed_device(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), frame_dev, HG_U8, frame_h, frame_w, ld,
-                                                (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8,
-                                                (int64_t)prescale_w * prescale_h, stream) != HG_OK)
-                hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
-            fr = c->pre_frame.p;
-            fh = prescale_h;
-            fw = prescale_w;
-            fld = prescale_w;
-        }
+        const void* fr;
+        int fh, fw;
+        int64_t fld;
+        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
         detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, T.first[T.n_levels], out_coords, out_angles, out_orig_index, out_confidence, out_cap,
                     n_out, stage_counts, rows_executed, stream);
+    });
+}
+
+// prescale + grid + stage loop (as hg_cascade_detect_frame_device), then the eyes, the discard, the rows and the purge on the survivors
+// left on the device (hg_eyes.hip), on the frame the cascade read (FaceDetectUpdated.py:947-1041, :1180)
+int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w,
+                                         int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out,
+                                         int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
+    return guarded([&] {
+        if (!c || !e || !n_out) hg::fail(HG_ERR_ARG, "null argument");
+        if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+        const LevelTable T = make_level_table(levels, n_levels);
+        const void* fr;
+        int fh, fw;
+        int64_t fld;
+        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
+        int64_t n = 0;
+        int cur = 0;
+        const int64_t n0 = T.first[T.n_levels];
+        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
+        hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
+                            out_rows, out_cap, n_out, n_before_purge, (hipStream_t)stream);
     });
 }
 

@@ -114,3 +114,23 @@ def build_face_cascade(flow, features, pipeline=None, keep_fraction=0.1, n_class
             kw = dict(pass_fraction=passed[id(flows[role])], cut_off=CUT_OFFS_FACE[int(name[-1])], descending=flip)
         out.append(Stage(name, flows[role] if own else None, quantile_classifier(f, d, labels(name[:-1], k), device=device, **kw)))
     return out
+
+
+# the reference's eye classifiers (SavedClassifiers, EyeLX / EyeLY of Pipelines/Pipeline_experimental.txt): 50 classes on 12 / 10 features,
+# avg_labels spanning about +-10.5 (the training range Dx, Dy in (-10, 10) of the eye flow's name)
+EYE_WIDTHS = (12, 10)
+
+
+def build_eye_stages(flow64, features, n_classes=50, widths=EYE_WIDTHS, span=10.5, device=0):
+    """The two eye classifiers (EyeLX, EyeLY) for the synthetic 64x64 eye flow ``flow64``, calibrated on ``features`` — (m, >= 12)
+    features of a sample of eye patches: 50 classes along the quantiles of the first feature (ascending for X, descending for Y), labels
+    evenly spread over [-span, span].  The outer classes regress beyond the reference's tolerance 9.0 (face_analysis.py:1018), so the
+    too-far discard removes a visible share of the faces.  Returns (flow64, clf_x, flow64, clf_y)."""
+    f = np.asarray(features, dtype=np.float64)
+    labels = np.linspace(-span, span, n_classes)
+    k = max(2, min(n_classes, len(f) // 4))
+    if k != n_classes:
+        labels = np.linspace(-span, span, k)
+    clf_x = quantile_classifier(f, min(widths[0], f.shape[1]), labels, device=device)
+    clf_y = quantile_classifier(f, min(widths[1], f.shape[1]), labels, device=device, descending=True)
+    return flow64, clf_x, flow64, clf_y
