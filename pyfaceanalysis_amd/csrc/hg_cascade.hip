@@ -5,8 +5,8 @@
 //     boolean-mask compaction of coordinates, angles, indices, sl, subimages_arr           :739-759
 // so that extract -> execute -> regression -> update -> discard -> compaction chain on one stream without a host copy of any
 // per-candidate array (the host reads back ONE integer, the survivor count, where it needs a launch size).
-// All arithmetic is float64 in the reference's operation order (no contraction), so coordinates follow the numpy path bit for
-// bit given the same regression outputs.  Candidates of all pyramid levels may share one batch (the author's note
+// All arithmetic is float64 in the reference's operation order, compiled without contraction (see the pragma below), so
+// coordinates follow the numpy path bit for bit given the same regression outputs.  Candidates of all pyramid levels may share one batch (the author's note
 // FaceDetectUpdated.py:599): the per-level constants max_Dx_diff, max_Dy_diff, base_side travel per ORIGINAL window.
 #include <hip/hip_runtime.h>
 
@@ -24,7 +24,16 @@ void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w
 int eyes_device(const hg_eyes* e);
 }
 
+// No contraction anywhere below (hg_gauss_dev.hpp, the regression, is included above and keeps the build's default): under hipcc's
+// -ffp-contract=fast-honor-pragmas the __dadd_rn / __dmul_rn of the HIP headers are plain operators, so `oa + net_Dang * tol` or
+// `dx * dx + dy * dy` could become one fma and move a discard decision that sits on its threshold by one ulp.  The helpers are defined
+// under the pragma: each operation rounds on its own, as numpy's do (tests/test_fp_contract.py checks the fma count).
+#pragma clang fp contract(off)
 namespace {
+__device__ __forceinline__ double d_add(double a, double b) { return a + b; }
+__device__ __forceinline__ double d_sub(double a, double b) { return a - b; }
+__device__ __forceinline__ double d_mul(double a, double b) { return a * b; }
+__device__ __forceinline__ double d_div(double a, double b) { return a / b; }
 
 template <typename F>
 int guarded(F&& fn) {
@@ -40,56 +49,54 @@ int guarded(F&& fn) {
     }
 }
 
+// One candidate through one stage: update_current_subimage_coordinates (face_analysis.py:803-840; Disc leaves the window as it is)
+// and identify_patches_to_discard (:842-887).  Returns the discard flag.  k_cascade_update and the group launches share it.
+__device__ __forceinline__ bool update_one(int type, const hg_cascade_consts& c, double& x0, double& y0, double& x1, double& y1, double& ang,
+                                            double r, const double* oc, double oa, const double* lvl) {
+    switch (type) {
+        case HG_STAGE_DISC: return r >= c.cut_off_face;
+        case HG_STAGE_POSX: {
+            const double ro = d_div(d_mul(r, d_sub(x1, x0)), c.regression_width);
+            x0 = d_sub(x0, ro);
+            x1 = d_sub(x1, ro);
+            const double d = d_sub(d_div(d_add(x1, x0), 2.0), d_div(d_add(oc[2], oc[0]), 2.0));
+            return fabs(d) > d_mul(lvl[0], c.tolerance_posxy_deviation);
+        }
+        case HG_STAGE_POSY: {
+            const double ro = d_div(d_mul(r, d_sub(y1, y0)), c.regression_height);
+            y0 = d_sub(y0, ro);
+            y1 = d_sub(y1, ro);
+            const double d = d_sub(d_div(d_add(y1, y0), 2.0), d_div(d_add(oc[3], oc[1]), 2.0));
+            return fabs(d) > d_mul(lvl[1], c.tolerance_posxy_deviation);
+        }
+        case HG_STAGE_PANG: {
+            ang = d_add(ang, r);
+            const double lim = d_mul(c.net_Dang, c.tolerance_angle_deviation);
+            return ang > d_add(oa, lim) || ang < d_sub(oa, lim);
+        }
+        default: {
+            const double ow = d_sub(x1, x0), oh = d_sub(y1, y0);
+            const double xc = d_div(d_add(x1, x0), 2.0), yc = d_div(d_add(y1, y0), 2.0);
+            const double w = d_mul(d_div(ow, r), c.desired_sampling), h = d_mul(d_div(oh, r), c.desired_sampling);
+            x0 = d_sub(xc, d_div(w, 2.0));
+            x1 = d_add(xc, d_div(w, 2.0));
+            y0 = d_sub(yc, d_div(h, 2.0));
+            y1 = d_add(yc, d_div(h, 2.0));
+            const double dx = d_sub(x0, x1), dy = d_sub(y0, y1);
+            const double ratio = d_div(__dsqrt_rn(d_add(d_mul(dx, dx), d_mul(dy, dy))), lvl[2]);
+            return ratio > d_mul(c.max_scale_radio, c.tolerance_scale_deviation) || ratio < d_div(c.min_scale_radio, c.tolerance_scale_deviation);
+        }
+    }
+}
+
 __global__ void k_cascade_update(int type, hg_cascade_consts c, int64_t n, double* __restrict__ coords, double* __restrict__ angles,
                                  const double* __restrict__ reg, const int32_t* __restrict__ orig_index, const double* __restrict__ orig_coords,
                                  const double* __restrict__ orig_angles, const double* __restrict__ orig_level, uint8_t* __restrict__ discard) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double x0 = coords[i * 4], y0 = coords[i * 4 + 1], x1 = coords[i * 4 + 2], y1 = coords[i * 4 + 3], ang = angles[i];
-    const double r = reg[i];
     const int32_t oi = orig_index[i];
-    bool wrong = false;
-    switch (type) {
-        case HG_STAGE_DISC:        // coordinates untouched (face_analysis.py:804-805); discard on the cut-off (:881-882)
-            wrong = r >= c.cut_off_face;
-            break;
-        case HG_STAGE_POSX: {      // :806-812, :846-856
-            const double ro = __ddiv_rn(__dmul_rn(r, __dsub_rn(x1, x0)), c.regression_width);
-            x0 = __dsub_rn(x0, ro);
-            x1 = __dsub_rn(x1, ro);
-            const double d = __dsub_rn(__ddiv_rn(__dadd_rn(x1, x0), 2.0), __ddiv_rn(__dadd_rn(orig_coords[oi * 4 + 2], orig_coords[oi * 4]), 2.0));
-            wrong = fabs(d) > __dmul_rn(orig_level[oi * 3], c.tolerance_posxy_deviation);
-            break;
-        }
-        case HG_STAGE_POSY: {      // :813-819, :857-867
-            const double ro = __ddiv_rn(__dmul_rn(r, __dsub_rn(y1, y0)), c.regression_height);
-            y0 = __dsub_rn(y0, ro);
-            y1 = __dsub_rn(y1, ro);
-            const double d = __dsub_rn(__ddiv_rn(__dadd_rn(y1, y0), 2.0), __ddiv_rn(__dadd_rn(orig_coords[oi * 4 + 3], orig_coords[oi * 4 + 1]), 2.0));
-            wrong = fabs(d) > __dmul_rn(orig_level[oi * 3 + 1], c.tolerance_posxy_deviation);
-            break;
-        }
-        case HG_STAGE_PANG: {      // :820-821, :868-872
-            ang = __dadd_rn(ang, r);
-            const double lim = __dmul_rn(c.net_Dang, c.tolerance_angle_deviation), oa = orig_angles[oi];
-            wrong = ang > __dadd_rn(oa, lim) || ang < __dsub_rn(oa, lim);
-            break;
-        }
-        case HG_STAGE_SCALE: {     // :822-835, :873-880
-            const double ow = __dsub_rn(x1, x0), oh = __dsub_rn(y1, y0);
-            const double xc = __ddiv_rn(__dadd_rn(x1, x0), 2.0), yc = __ddiv_rn(__dadd_rn(y1, y0), 2.0);
-            const double w = __dmul_rn(__ddiv_rn(ow, r), c.desired_sampling), h = __dmul_rn(__ddiv_rn(oh, r), c.desired_sampling);
-            x0 = __dsub_rn(xc, __ddiv_rn(w, 2.0));
-            x1 = __dadd_rn(xc, __ddiv_rn(w, 2.0));
-            y0 = __dsub_rn(yc, __ddiv_rn(h, 2.0));
-            y1 = __dadd_rn(yc, __ddiv_rn(h, 2.0));
-            const double dx = __dsub_rn(x0, x1), dy = __dsub_rn(y0, y1);
-            const double side = __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-            const double ratio = __ddiv_rn(side, orig_level[oi * 3 + 2]);
-            wrong = ratio > __dmul_rn(c.max_scale_radio, c.tolerance_scale_deviation) || ratio < __ddiv_rn(c.min_scale_radio, c.tolerance_scale_deviation);
-            break;
-        }
-    }
+    const bool wrong = update_one(type, c, x0, y0, x1, y1, ang, reg[i], orig_coords + (size_t)oi * 4, orig_angles[oi], orig_level + (size_t)oi * 3);
     coords[i * 4] = x0; coords[i * 4 + 1] = y0; coords[i * 4 + 2] = x1; coords[i * 4 + 3] = y1;
     angles[i] = ang;
     discard[i] = wrong ? 1 : 0;
@@ -141,7 +148,7 @@ __global__ void __launch_bounds__(256) k_gather_rows(const char* __restrict__ sr
 }
 
 // One cascade stage's glue in ONE launch of ONE workgroup (a frame has at most a few thousand candidates): update + discard
-// test per candidate (same arithmetic as k_cascade_update), order-preserving compaction, and the gather of every small
+// test per candidate (update_one, as k_cascade_update), order-preserving compaction, and the gather of every small
 // per-candidate array into the other half of its ping-pong pair.  The candidate count comes from device memory (the previous
 // stage's output), so stages chain without a host round trip; the new count goes to device memory and, for the caller that
 // wants it, to a pinned host word.
@@ -155,44 +162,6 @@ struct StageArrays {
     int32_t *count_in, *count_out;
     int32_t k_feat, cur, n_max;
 };
-
-__device__ __forceinline__ bool update_one(int type, const hg_cascade_consts& c, double& x0, double& y0, double& x1, double& y1, double& ang,
-                                            double r, const double* oc, double oa, const double* lvl) {
-    switch (type) {
-        case HG_STAGE_DISC: return r >= c.cut_off_face;
-        case HG_STAGE_POSX: {
-            const double ro = __ddiv_rn(__dmul_rn(r, __dsub_rn(x1, x0)), c.regression_width);
-            x0 = __dsub_rn(x0, ro);
-            x1 = __dsub_rn(x1, ro);
-            const double d = __dsub_rn(__ddiv_rn(__dadd_rn(x1, x0), 2.0), __ddiv_rn(__dadd_rn(oc[2], oc[0]), 2.0));
-            return fabs(d) > __dmul_rn(lvl[0], c.tolerance_posxy_deviation);
-        }
-        case HG_STAGE_POSY: {
-            const double ro = __ddiv_rn(__dmul_rn(r, __dsub_rn(y1, y0)), c.regression_height);
-            y0 = __dsub_rn(y0, ro);
-            y1 = __dsub_rn(y1, ro);
-            const double d = __dsub_rn(__ddiv_rn(__dadd_rn(y1, y0), 2.0), __ddiv_rn(__dadd_rn(oc[3], oc[1]), 2.0));
-            return fabs(d) > __dmul_rn(lvl[1], c.tolerance_posxy_deviation);
-        }
-        case HG_STAGE_PANG: {
-            ang = __dadd_rn(ang, r);
-            const double lim = __dmul_rn(c.net_Dang, c.tolerance_angle_deviation);
-            return ang > __dadd_rn(oa, lim) || ang < __dsub_rn(oa, lim);
-        }
-        default: {
-            const double ow = __dsub_rn(x1, x0), oh = __dsub_rn(y1, y0);
-            const double xc = __ddiv_rn(__dadd_rn(x1, x0), 2.0), yc = __ddiv_rn(__dadd_rn(y1, y0), 2.0);
-            const double w = __dmul_rn(__ddiv_rn(ow, r), c.desired_sampling), h = __dmul_rn(__ddiv_rn(oh, r), c.desired_sampling);
-            x0 = __dsub_rn(xc, __ddiv_rn(w, 2.0));
-            x1 = __dadd_rn(xc, __ddiv_rn(w, 2.0));
-            y0 = __dsub_rn(yc, __ddiv_rn(h, 2.0));
-            y1 = __dadd_rn(yc, __ddiv_rn(h, 2.0));
-            const double dx = __dsub_rn(x0, x1), dy = __dsub_rn(y0, y1);
-            const double ratio = __ddiv_rn(__dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))), lvl[2]);
-            return ratio > __dmul_rn(c.max_scale_radio, c.tolerance_scale_deviation) || ratio < __ddiv_rn(c.min_scale_radio, c.tolerance_scale_deviation);
-        }
-    }
-}
 
 // What the host polls instead of synchronising the stream (pinned, device-visible): word 0 = survivor count, word 1 = sequence
 // number of the stage that wrote it (written last, system scope).  A stream synchronisation costs the caller 20-40 us before it
@@ -231,7 +200,7 @@ __global__ void k_cascade_init(int n, const double* __restrict__ orig_coords, do
 // frame were 97 KB of pageable host memory copied per frame): level L holds ny x nx windows, y-major, at
 // numpy.linspace(0, stop, n) positions — i * (stop / (n - 1)), the last one `stop` itself, a single one 0.0 — and a window is
 // (posX, posY, posX + pw - 1, posY + ph - 1)  (face_analysis.py:630-646, :661-669; grid.level_boxes).  float64 in numpy's
-// operation order, no contraction: the boxes equal the host's bit for bit (tests/test_cascade.py).
+// operation order, no contraction (pragma above): the boxes equal the host's bit for bit (tests/test_cascade.py).
 constexpr int kMaxLevels = 32;
 struct LevelTable {
     int32_t n_levels, pad;
@@ -253,10 +222,10 @@ __global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coor
     auto lin = [](int j, int num, double stop) -> double {
         if (num <= 1 || j == 0) return 0.0;
         if (j == num - 1) return stop;
-        return __dmul_rn((double)j, __ddiv_rn(stop, (double)(num - 1)));
+        return d_mul((double)j, d_div(stop, (double)(num - 1)));
     };
     const double x0 = lin(ix, V.nx, V.x_stop), y0 = lin(iy, V.ny, V.y_stop);
-    const double b[4] = {x0, y0, __dsub_rn(__dadd_rn(x0, V.patch_w), 1.0), __dsub_rn(__dadd_rn(y0, V.patch_h), 1.0)};
+    const double b[4] = {x0, y0, d_sub(d_add(x0, V.patch_w), 1.0), d_sub(d_add(y0, V.patch_h), 1.0)};
     for (int q = 0; q < 4; ++q) orig_coords[(size_t)i * 4 + q] = b[q];
     orig_level[(size_t)i * 3] = V.max_dx;
     orig_level[(size_t)i * 3 + 1] = V.max_dy;

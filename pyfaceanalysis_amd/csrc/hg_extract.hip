@@ -16,7 +16,8 @@
 // (Geometry.c) gives that pixel's source: 16.16 fixed-point coefficients A0..A5 from the matrix Image.rotate builds
 // (cos / sin of -radians(angle % 360) rounded to 15 decimals), xs = (A2 + yr A1 + xr A0) >> 16, ys likewise.  The integer
 // sums are PIL's running sums in closed form.  Multiples of 180 degrees take PIL's "scaling" branch (sin rounds to 0) with
-// its floating running sums.  The coefficients are computed on the device in double precision without contraction; the
+// its floating running sums.  The coefficients are computed on the device in double precision without contraction (the pragma
+// below: PIL computes m2 = m0 (-cx) + m1 (-cy) + cx in Python, where a fused multiply-add would move it by an ulp); the
 // one place this can differ from the host's libm is the last bit of cos / sin before the 15-decimal rounding, which
 // moves a fixed-point coefficient only if it sits within 7e-11 of a rounding boundary.  Rotated frames must stay inside
 // PIL's fixed-point range (|source coordinate| < 32768), otherwise the window is left 0.
@@ -41,7 +42,15 @@ struct hg_patcher {
 
 namespace hg { void set_last_error(const std::string& s); }
 
+// No contraction anywhere below: under hipcc's -ffp-contract=fast-honor-pragmas the __dadd_rn / __dmul_rn of the HIP headers are plain
+// operators, so a multiply feeding an add may become one fma.  The helpers are defined under the pragma: each operation rounds on its
+// own, as PIL's C doubles and Python floats do (tests/test_fp_contract.py checks the fma count).
+#pragma clang fp contract(off)
 namespace {
+__device__ __forceinline__ double d_add(double a, double b) { return a + b; }
+__device__ __forceinline__ double d_sub(double a, double b) { return a - b; }
+__device__ __forceinline__ double d_mul(double a, double b) { return a * b; }
+__device__ __forceinline__ double d_div(double a, double b) { return a / b; }
 
 // Source index tables, one entry per thread.  PIL steps the source coordinate by repeated addition
 // (o += a per output pixel); to land on the same pixel in every case each thread repeats that sum from the start
@@ -59,9 +68,9 @@ __device__ __forceinline__ int32_t extent_entry(const double* __restrict__ box, 
     int k = 0;
     for (; k + 8 <= i; k += 8) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) o = __dadd_rn(o, a);
+        for (int u = 0; u < 8; ++u) o = d_add(o, a);
     }
-    for (; k < i; ++k) o = __dadd_rn(o, a);
+    for (; k < i; ++k) o = d_add(o, a);
     const int v = o < 0.0 ? -1 : (int)o;
     return (v >= 0 && v < lim) ? v : -1;
 }
@@ -212,10 +221,10 @@ struct RotCoef {
 };
 
 __device__ __forceinline__ double round15(double v) {       // Python round(v, 15) for |v| <= 1
-    return __ddiv_rn(rint(__dmul_rn(v, 1e15)), 1e15);
+    return d_div(rint(d_mul(v, 1e15)), 1e15);
 }
 __device__ __forceinline__ int32_t fix16(double v) {        // Geometry.c FIX(): FLOOR(v * 65536 + 0.5)
-    const double x = __dadd_rn(__dmul_rn(v, 65536.0), 0.5);
+    const double x = d_add(d_mul(v, 65536.0), 0.5);
     return x >= 0.0 ? (int32_t)x : (int32_t)floor(x);
 }
 
@@ -225,13 +234,13 @@ __device__ __forceinline__ RotCoef rot_coef_of(const double* __restrict__ boxes,
     if (a < 0.0) a += 360.0;
     if (a == 360.0) a = 0.0;
     if (a != 0.0 && isfinite(a)) {
-        const double cx = __dmul_rn(__dadd_rn(boxes[b * 4], boxes[b * 4 + 2]), 0.5), cy = __dmul_rn(__dadd_rn(boxes[b * 4 + 1], boxes[b * 4 + 3]), 0.5);
-        const double r = -__dmul_rn(a, 3.14159265358979323846 / 180.0);       // -math.radians(angle)
+        const double cx = d_mul(d_add(boxes[b * 4], boxes[b * 4 + 2]), 0.5), cy = d_mul(d_add(boxes[b * 4 + 1], boxes[b * 4 + 3]), 0.5);
+        const double r = -d_mul(a, 3.14159265358979323846 / 180.0);       // -math.radians(angle)
         const double c = round15(cos(r)), sn = round15(sin(r));
         const double m0 = c, m1 = sn, m3 = -sn, m4 = c;
         // transform(-cx, -cy, matrix) = (a x + b y) + c, then += center: every operation rounded on its own
-        const double m2 = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m0, -cx), __dmul_rn(m1, -cy)), 0.0), cx);
-        const double m5 = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m3, -cx), __dmul_rn(m4, -cy)), 0.0), cy);
+        const double m2 = d_add(d_add(d_add(d_mul(m0, -cx), d_mul(m1, -cy)), 0.0), cx);
+        const double m5 = d_add(d_add(d_add(d_mul(m3, -cx), d_mul(m4, -cy)), 0.0), cy);
         if (m1 == 0.0 && m3 == 0.0) {
             rc.mode = 2;
             rc.m0 = m0; rc.m2 = m2; rc.m4 = m4; rc.m5 = m5;
@@ -241,14 +250,14 @@ __device__ __forceinline__ RotCoef rot_coef_of(const double* __restrict__ boxes,
             const double xs[2] = {0.0, (double)fw}, ys[2] = {0.0, (double)fh};
             for (int i = 0; i < 2; ++i)
                 for (int j = 0; j < 2; ++j) {
-                    const double u = __dadd_rn(__dadd_rn(__dmul_rn(xs[i], m0), __dmul_rn(ys[j], m1)), m2);
-                    const double v = __dadd_rn(__dadd_rn(__dmul_rn(xs[i], m3), __dmul_rn(ys[j], m4)), m5);
+                    const double u = d_add(d_add(d_mul(xs[i], m0), d_mul(ys[j], m1)), m2);
+                    const double v = d_add(d_add(d_mul(xs[i], m3), d_mul(ys[j], m4)), m5);
                     ok = ok && fabs(u) < 32768.0 && fabs(v) < 32768.0;
                 }
             rc.mode = ok ? 1 : 3;
             rc.A[0] = fix16(m0); rc.A[1] = fix16(m1); rc.A[3] = fix16(m3); rc.A[4] = fix16(m4);
-            rc.A[2] = fix16(__dadd_rn(__dadd_rn(m2, __dmul_rn(m0, 0.5)), __dmul_rn(m1, 0.5)));
-            rc.A[5] = fix16(__dadd_rn(__dadd_rn(m5, __dmul_rn(m3, 0.5)), __dmul_rn(m4, 0.5)));
+            rc.A[2] = fix16(d_add(d_add(m2, d_mul(m0, 0.5)), d_mul(m1, 0.5)));
+            rc.A[5] = fix16(d_add(d_add(m5, d_mul(m3, 0.5)), d_mul(m4, 0.5)));
         }
     }
     return rc;
@@ -269,8 +278,8 @@ __device__ __forceinline__ void gather_rot_row(const FT* __restrict__ frame, int
     double yo = 0.0;
     int ys2 = -1;
     if (rc.mode == 2 && yr >= 0) {      // ImagingScaleAffine on the rotated frame: yo = a5 + a4 / 2, then += a4 per row
-        yo = __dadd_rn(rc.m5, __dmul_rn(rc.m4, 0.5));
-        for (int k = 0; k < yr; ++k) yo = __dadd_rn(yo, rc.m4);
+        yo = d_add(rc.m5, d_mul(rc.m4, 0.5));
+        for (int k = 0; k < yr; ++k) yo = d_add(yo, rc.m4);
         ys2 = yo < 0.0 ? -1 : (int)yo;
         if (ys2 >= fh) ys2 = -1;
     }
@@ -285,8 +294,8 @@ __device__ __forceinline__ void gather_rot_row(const FT* __restrict__ frame, int
                 const int64_t yy = (int64_t)rc.A[5] + (int64_t)yr * rc.A[4] + (int64_t)xr * rc.A[3];
                 xs = (int)(xx >> 16); ys = (int)(yy >> 16);
             } else if (rc.mode == 2) {
-                double xo = __dadd_rn(rc.m2, __dmul_rn(rc.m0, 0.5));
-                for (int k = 0; k < xr; ++k) xo = __dadd_rn(xo, rc.m0);
+                double xo = d_add(rc.m2, d_mul(rc.m0, 0.5));
+                for (int k = 0; k < xr; ++k) xo = d_add(xo, rc.m0);
                 xs = xo < 0.0 ? -1 : (int)xo;
                 ys = ys2;
             }

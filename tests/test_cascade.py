@@ -306,11 +306,12 @@ def test_config3_full_pyramid_1080p(native_lib, nets):
     def regress(k, sl):
         return stages[k].classifier.regression(np.ascontiguousarray(sl[:, :stages[k].classifier.input_dim]))
     want = CR.run_cascade([s.name for s in stages], [s.flow is not None for s in stages], boxes, level, pipe, extract, execute, regress)
-    # (the host loop and the device loop compute in different precisions between the network calls: decisions agree, numbers to 1e-3)
+    # (both loops read the same device features and the same device regression; the glue is float64 in numpy's order on both sides,
+    # so the survivors' numbers agree bit for bit, as in the 160x90 case)
     known = [i for i, c in enumerate(got["counts"]) if c >= 0]
     assert [got["counts"][i] for i in known] == [want["counts"][i] for i in known], (got["counts"], want["counts"])
     assert np.array_equal(got["orig_index"], want["orig_index"])
-    assert np.allclose(got["coords"], want["coords"], rtol=0, atol=1e-3) and np.allclose(got["angles"], want["angles"], rtol=0, atol=1e-3)
+    assert np.array_equal(got["coords"], want["coords"]) and np.array_equal(got["angles"], want["angles"])
     # several frames in flight (bench.py `frames_in_flight`): cascades with their own flow handles, one stream and one host
     # thread each, at the same time — every one of them must return exactly what the cascade returns on its own
     import threading

@@ -78,6 +78,22 @@ def test_eye_boxes_against_restatement(setup):
 
 
 @pytest.mark.gpu
+def test_eye_boxes_against_reference_fixture(setup):
+    """hg_eyes_boxes_device against compute_approximate_eye_boxes_coordinates itself (tests/golden/reference_glue.npz): random boxes,
+    angles 0, +-90, +-180, +-24.75, tiny, denormal-small and -0.0.  Bit for bit where the angle is zero (cos / sin exact); elsewhere
+    within the ulps that device cos / sin may differ from libm by, as above."""
+    import os
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_glue.npz"))
+    boxes, angles = g["eye_boxes"], g["eye_angles"]
+    got = setup["loc"].eye_boxes(boxes, angles)
+    want = np.concatenate([g["eye_left"], g["eye_right"]])
+    zero = np.concatenate([angles == 0.0] * 2)
+    assert zero.sum() >= 8 and np.array_equal(got[zero], want[zero])
+    scale = np.abs(np.concatenate([boxes] * 2)).max(axis=1, keepdims=True)
+    assert ulp_close(got[~zero], want[~zero], scale[~zero])
+
+
+@pytest.mark.gpu
 def test_patches_bit_exact_against_pil_rule_and_restated_contrast(setup):
     from oracle import pil_restate
     s = setup

@@ -131,3 +131,22 @@ def test_frame_to_features_pipeline(native_lib, nets):
     ref = oracle.execute_flow(nodes, xr)
     y = Flow(nodes).execute(x)
     assert np.abs(y - ref).max() <= 1e-4 * np.abs(ref).max()
+
+
+@pytest.mark.gpu
+def test_rotated_windows_on_fixed_point_boundaries_match_pil(native_lib):
+    """Box centres placed (tests/golden/make_reference_glue.py) where PIL's 16.16 offset A2 = FIX(m2 + ...) or A5 changes, and with it
+    the source of a sampled pixel, if m2 = m0 (-cx) + m1 (-cy) + cx (m5 likewise) were computed with a fused multiply-add
+    (tests/test_reference_glue.py checks with PIL that every one of these windows changes under a fused m2 / m5).  The device must
+    round each operation on its own, as Python does, and give PIL's windows."""
+    from pyfaceanalysis_amd.patches import Patcher
+    from tests.test_reference_glue import load, rotation_frame
+    g = load()
+    frame, boxes, angs = rotation_frame(g), g["rot_boxes"], g["rot_angles"]
+    p = Patcher()
+    for size in ((64, 64), (37, 21)):
+        ref = _pil_rotated_windows(frame, boxes, angs, size)
+        got = p.extract(frame, boxes, size, dtype=np.uint8, delta_angs=angs)
+        bad = np.nonzero((got != ref).any(axis=1))[0]
+        assert bad.size == 0, (size, [(int(i), float(angs[i]), int((got[i] != ref[i]).sum())) for i in bad])
+    p.close()
