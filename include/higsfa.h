@@ -209,7 +209,15 @@ int hg_patcher_extract_device(hg_patcher* p, const void* frame_dev, int frame_dt
 /* The same for boxes the caller declares UNCHANGED between calls (key != 0; e.g. the prescale's whole-frame box, the first-stage
  * grid of a frame size, which depend on the frame's size only — face_analysis.py:630-669): the index tables are built on the first
  * call with a key (and whenever n or a size differs from what the key was built for) and reused afterwards.  Unrotated windows.
- * key = 0: hg_patcher_extract_device. */
+ * key = 0: hg_patcher_extract_device.
+ * The contract the tables rest on:
+ *  - THE KEY DETERMINES THE BOXES.  A table is found by (key, n, out_w, out_h, frame_w, frame_h); boxes_dev is read only when a
+ *    table is built and never compared afterwards.  Two calls with equal key, n and sizes but different boxes get the first call's
+ *    windows.  (The cascade hashes everything its boxes are computed from: the level table, or the frame and prescaled sizes.)
+ *  - ONE STREAM PER PATCHER.  A patcher keeps four tables and replaces them round-robin, by a launch on the calling stream; only a
+ *    table that has to grow waits for that stream first.  Calls on one patcher must therefore be ordered on one stream (or by the
+ *    caller's own events): a launch on a second stream may read a table while it is rewritten.  More than four keys in rotation
+ *    are correct but rebuild a table on every call. */
 int hg_patcher_extract_keyed_device(hg_patcher* p, uint64_t key, const void* frame_dev, int frame_dtype, int frame_h, int frame_w,
                                     int64_t ld, const double* boxes_dev, int64_t n, int out_w, int out_h, void* out_dev,
                                     int out_dtype, int64_t ldo, void* stream);

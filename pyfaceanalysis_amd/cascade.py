@@ -93,7 +93,7 @@ class DeviceCascade(object):
         self.patcher = Patcher(self.device)
         self._h = None
         self._levels = {}        # (frame size, smallest_face) -> level table (frame_levels)
-        self._prescale = {}      # frame size -> (box tensor, output tensor) of the prescale step
+        self._prescale = {}      # (frame size, prescaled size) -> (box tensor, output tensor) of the prescale step
         self._frames = {}        # (frame size, smallest_face, prescale size) -> everything detect_frame needs per call
         for st in self.stages:
             if st.classifier.input_dim > self.k:
@@ -133,16 +133,22 @@ class DeviceCascade(object):
 
     def prescale(self, frame, prescale_size=grid.PRESCALE_SIZE):
         """FaceDetectUpdated.py:551-556: shrink so that the larger side is <= prescale_size, ``Image.resize(NEAREST)`` —
-        PIL's nearest resize is the EXTENT rule over the whole frame, so the patcher does it (bit-exact vs PIL in the tests)."""
+        PIL's nearest resize is the EXTENT rule over the whole frame, so the patcher does it (bit-exact vs PIL in the tests).
+        A frame that needs no shrinking is returned as it is.  Otherwise the returned tensor lives with the cascade, one per
+        (frame size, prescaled size): it is valid until the next ``prescale()`` with the same frame size and the same prescaled
+        size on this cascade, which writes into it again — a caller that keeps a prescaled frame longer clones it."""
+        from .eyes import check_frame
         t = self.torch
+        check_frame(t, frame, self.dev)
         fh, fw = int(frame.shape[0]), int(frame.shape[1])
         pw, ph = grid.prescaled_size(fw, fh, prescale_size)
         if (pw, ph) == (fw, fh):
             return frame
-        if (fw, fh) not in self._prescale:      # the box of the whole frame and the output live with the cascade: no per-frame upload / allocation
-            self._prescale[(fw, fh)] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
-                                        t.empty((ph, pw), dtype=t.uint8, device=self.dev))
-        whole, small = self._prescale[(fw, fh)]
+        key = (fw, fh, pw, ph)
+        if key not in self._prescale:      # the box of the whole frame and the output live with the cascade: no per-frame upload / allocation
+            self._prescale[key] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
+                                   t.empty((ph, pw), dtype=t.uint8, device=self.dev))
+        whole, small = self._prescale[key]
         self.patcher.extract_device(frame.data_ptr(), np.uint8, fh, fw, frame.stride(0), whole.data_ptr(), 1, (pw, ph), small.data_ptr(),
                                     np.uint8, pw * ph, stream=t.cuda.current_stream(self.dev).cuda_stream)
         return small
@@ -187,14 +193,15 @@ class DeviceCascade(object):
     def detect_frame(self, frame, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
         """prescale + detect as ONE host call (hg_cascade_detect_frame_device): what the reference does per image between loading
         it and writing its detections (FaceDetectUpdated.py:551-561 prescale, :589-600 grid, :665-766 stage loop).  Everything that
-        depends only on the frame size — prescaled size, level table, output buffers — is computed once and kept."""
+        depends only on the frame size — prescaled size, level table, output buffers — is computed once and kept; the frame itself
+        is checked on every call (the library is handed its raw pointer)."""
+        from .eyes import check_frame
         t, L = self.torch, _capi.lib()
+        check_frame(t, frame, self.dev)
         fh, fw = int(frame.shape[0]), int(frame.shape[1])
         key = (fw, fh, float(smallest_face), int(prescale_size or 0))
         plan = self._frames.get(key)
         if plan is None:
-            if frame.dtype != t.uint8 or frame.device != self.dev or frame.stride(1) != 1:
-                raise ValueError("frame must be a uint8 tensor on %s with contiguous rows" % (self.dev,))
             pw, ph = grid.prescaled_size(fw, fh, prescale_size) if prescale_size else (fw, fh)
             pre = (pw, ph) if (pw, ph) != (fw, fh) else (0, 0)
             levels, n_levels, n0 = frame_levels(pw, ph, smallest_face, self.pipeline, (self.w, self.h))

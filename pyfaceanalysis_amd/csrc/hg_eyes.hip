@@ -382,6 +382,9 @@ void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w
     *n_out = 0;
     if (n_before_purge) *n_before_purge = 0;
     if (n == 0) return;
+    // before any workspace pointer is taken: eyes_run reserves too, but its arguments below are evaluated first — on a handle's
+    // first faces they were null (no rows written, the purge read an uninitialised count) and on growth they were the freed buffers
+    e->reserve(n);
     eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st);
     launch_purge((const double*)e->rows.p, n, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st);
     HG_HIP(hipMemcpyAsync(e->host_words, e->count.p, 8, hipMemcpyDeviceToHost, st));

@@ -144,7 +144,7 @@ __device__ __forceinline__ void tail_layer(const TailParams& P, const TailStage&
 #endif
 #pragma unroll
             for (int k = 0; k < KB; ++k) {
-                const int nk = nks[k] & 255, r0 = nks[k] >> 8;      // (r0 > 0: a packed remainder block of the layer below)
+                const int nk = nks[k] & 255, r0 = (nks[k] >> 8) & 255;      // (r0 > 0: a packed remainder block of the layer below)
                 if (nks[k] == 4) {      // a whole block: four k-steps, no branch between them
 #pragma unroll
                     for (int r = 0; r < 4; ++r)

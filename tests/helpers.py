@@ -336,3 +336,22 @@ def subtree_fuzz_net(seed):
         if w * h == 1:
             break
     return flow
+
+
+# Frame sizes of the mixed-size stream tests (tests/test_frame_stream_gpu.py), with what grid.py gives for FACE_PIPELINE, 64x64
+# sub-images, smallest_face = 0.1 and prescale_size = 1000: (frame w, frame h) -> (prescaled w, prescaled h, pyramid levels, windows).
+# Pinned on the CPU by tests/test_grid_patches.py::test_frame_stream_premises; the GPU tests rest on three facts it states — several
+# frames have the same window count, two frames share a grid, and the window count spans 99 .. 5148.
+FRAME_STREAM = {
+    (64, 64): (64, 64, 6, 99),               # smallest: first in the stream, everything grows after it
+    (97, 131): (97, 131, 7, 397),            # odd sizes, no prescale
+    (320, 240): (320, 240, 10, 1308),        # same n as the next two, another frame
+    (640, 480): (640, 480, 10, 1308),        # same n, other tables
+    (3648, 2736): (1000, 750, 10, 1308),     # prescaled; same n again
+    (1280, 720): (1000, 562, 10, 1738),      # the prescaled size of 1920x1080: same grid key, another prescale key
+    (1920, 1080): (1000, 562, 10, 1738),     # the benchmark's frame
+    (1080, 1920): (562, 1000, 10, 1820),     # transposed
+    (1001, 1000): (1000, 999, 10, 978),      # prescale by one pixel
+    (2000, 300): (1000, 150, 9, 5148),       # largest n: the cascade's buffers grow
+}
+FRAME_STREAM_600 = {(2000, 300): (600, 90, 7, 1703)}      # the same with prescale_size = 600

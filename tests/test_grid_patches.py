@@ -150,3 +150,31 @@ def test_rotated_windows_on_fixed_point_boundaries_match_pil(native_lib):
         bad = np.nonzero((got != ref).any(axis=1))[0]
         assert bad.size == 0, (size, [(int(i), float(angs[i]), int((got[i] != ref[i]).sum())) for i in bad])
     p.close()
+
+
+def test_frame_stream_premises():
+    """What tests/test_frame_stream_gpu.py takes for granted about its ten frame sizes (helpers.FRAME_STREAM: FACE_PIPELINE, 64x64
+    sub-images, smallest_face = 0.1, prescale 1000): prescaled size, pyramid levels and first-stage windows of every frame, and the
+    three facts the stream is built on — frames with EQUAL window counts but different grids (a keyed index table matched on n alone
+    would be reused wrongly), two frames that SHARE a grid after the prescale (same grid key, different prescale keys), and window
+    counts from 99 to 5148 (buffers that grow, then hold much smaller frames).  If grid.py changes any of it, this fails first."""
+    from tests.helpers import FRAME_STREAM, FRAME_STREAM_600
+    from pyfaceanalysis_amd.cascade import frame_levels
+
+    def facts(w, h, prescale_size):
+        pw, ph = grid.prescaled_size(w, h, prescale_size)
+        levels = grid.frame_boxes(pw, ph, 0.1, pipeline=grid.FACE_PIPELINE, subimage_size=(64, 64))
+        n = sum(len(b) for _, b in levels)
+        assert frame_levels(pw, ph, 0.1, grid.FACE_PIPELINE, (64, 64))[1:] == (len(levels), n)      # the table the device gets says the same
+        return pw, ph, len(levels), n
+    assert len(FRAME_STREAM) == 10
+    for (w, h), want in FRAME_STREAM.items():
+        assert facts(w, h, 1000) == want, (w, h)
+    for (w, h), want in FRAME_STREAM_600.items():
+        assert facts(w, h, 600) == want, (w, h)
+    n_of = {size: v[3] for size, v in FRAME_STREAM.items()}
+    assert n_of[(320, 240)] == n_of[(640, 480)] == n_of[(3648, 2736)] == 1308
+    assert len({FRAME_STREAM[s][:2] for s in ((320, 240), (640, 480), (3648, 2736))}) == 3       # equal n, three different grids
+    assert FRAME_STREAM[(1280, 720)] == FRAME_STREAM[(1920, 1080)]                                # one grid for two frame sizes
+    assert min(n_of.values()) == n_of[(64, 64)] == 99 and max(n_of.values()) == n_of[(2000, 300)] == 5148
+    assert len({v[:2] for v in FRAME_STREAM.values()}) == 9                                       # nine distinct grids in all
