@@ -373,6 +373,53 @@ int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* 
                                          int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, int32_t* stage_counts,
                                          int64_t* rows_executed, void* stream);
 
+/* --- Tracking one face across a stream of frames (the reference's track_single_face mode) ---------------------------------
+ * Once a frame has produced a face, its first purged detection is carried over (FaceDetectUpdated.py:1189-1195) and the next
+ * frame searches NINE windows instead of the pyramid: one sampling value from the size of that box (face_analysis.py:576-585),
+ * the box's corner and one horizontal separation step to either side, all at the box's own y (:611-623); the product of the two
+ * position lists (:661-669) is the three distinct windows three times over, y-major, and the duplicates reach the purge as in the
+ * reference.  A tracked frame that finds nothing sends the following frame back to the full grid.
+ *   sampling  = (0.5 |x1 - x0| + 0.5 |y1 - y0|) * 1.0 / subimage_width
+ *   patch     = (subimage_width * sampling, subimage_height * sampling)
+ *   sepx      = net_Dx * 2.0 * patch_w / regression_width;   posX = (x0, x0 + sepx, x0 - sepx), posY = (y0, y0, y0)
+ *   window    = (posX, posY, posX + patch_w - 1, posY + patch_h - 1)
+ *   level     = (net_Dx * patch_w / regression_width, net_Dy * patch_h / regression_height, sqrt(patch_w^2 + patch_h^2))
+ * float64 in that operation order, no contraction: bit for bit the reference's (tests/golden/reference_tracking.npz). */
+typedef struct hg_tracked_consts {
+    double subimage_width, subimage_height;      /* the cascade's sub-image size                              */
+    double regression_width, regression_height;  /* Pipeline header: 128 128                                  */
+    double net_Dx, net_Dy;                       /* Pipeline header: 40 20                                    */
+} hg_tracked_consts;
+/* The nine windows alone, for inspection: face_dev (4 doubles ON THE DEVICE: x0, y0, x1, y1) -> boxes_dev (9, 4) and level_dev (9, 3),
+ * float64 on the device.  Enqueued on `stream`. */
+int hg_cascade_tracked_grid_device(int device, const hg_tracked_consts* consts, const double* face_dev, double* boxes_dev, double* level_dev,
+                                   void* stream);
+/* The tracker: created from a cascade and an eye handle on one device (both stay owned by the caller and must outlive it; consts'
+ * sub-image size must be the cascade's).  It owns, on the device, the tracked box and its found flag, and remembers the size of the
+ * prescaled frame the box belongs to.
+ * hg_tracker_step_frame_device takes the arguments of hg_cascade_detect_faces_frame_device and returns the same rows.
+ *   - No face held, or the prescaled frame size differs from the one the face was found at: exactly what
+ *     hg_cascade_detect_faces_frame_device runs (*used_tracked_grid = 0); then row 0's box, if there is a row, becomes the tracked
+ *     face.  A change of the prescaled size DROPS the tracked face — its coordinates mean nothing on another size; the reference
+ *     has no such case (it applies the box to whatever frame comes next).
+ *   - Otherwise the tracked frame (*used_tracked_grid = 1): the nine windows are built on the device from the box the previous
+ *     frame's purge left there, and the whole frame — grid, every stage group, eyes, purge, hand-over of the new tracked face — is
+ *     enqueued back to back.  Every launch is sized by the bound 9 (the eye launches by 18); the kernels take the live count from
+ *     device memory; rows between the live count and the bound are given a defined window.  No survivor count is read back:
+ *     stage_counts[] is -1 throughout, and the call ends with ONE host wait that fetches the kept count, the rows and the flag.
+ *     `levels` is not read.  *rows_executed counts 9 rows per network-owning stage.
+ * The box is carried only if its four numbers are finite.  The box is in the coordinates of the prescaled frame the cascade read and
+ * is applied to the next prescaled frame, as in the reference.  One stream per handle, as for the patcher: a step must not run
+ * while another step of the same tracker, or any call on its cascade or eye handle, is in flight; one frame at a time.
+ * hg_tracker_reset forgets the face (the next step uses the full grid).  Synchronous. */
+typedef struct hg_tracker hg_tracker;
+int hg_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, hg_tracker** out);
+void hg_tracker_free(hg_tracker* t);
+int hg_tracker_reset(hg_tracker* t);
+int hg_tracker_step_frame_device(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h,
+                                 const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out,
+                                 int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid, void* stream);
+
 /* --- SFA training step for one layer of nodes (BASELINE.json configs[4]) -----
  * Not on the reference's path (it never trains, face_analysis.py:451-479); restates
  * mdp.nodes.SFANode train/stop_training per node k over input columns conn[k*d .. (k+1)*d):

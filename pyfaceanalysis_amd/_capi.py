@@ -43,6 +43,10 @@ class HgEyeConsts(C.Structure):         # hg_eye_consts (include/higsfa.h)
                                           "target_mean", "target_std")] + [(n, C.c_int32) for n in ("eye_w", "eye_h", "n_features", "reserved")]
 
 
+class HgTrackedConsts(C.Structure):     # hg_tracked_consts (include/higsfa.h)
+    _fields_ = [(n, C.c_double) for n in ("subimage_width", "subimage_height", "regression_width", "regression_height", "net_Dx", "net_Dy")]
+
+
 HG_STAGE = {"Disc": 0, "PosX": 1, "PosY": 2, "PAng": 3, "Scale": 4}
 
 
@@ -126,6 +130,12 @@ def lib():
         "hg_purge_detections_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_cascade_detect_faces_frame_device": (C.c_int, [vp, vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
                                                            C.POINTER(i64), vp, C.POINTER(i64), vp]),
+        "hg_cascade_tracked_grid_device": (C.c_int, [i32, C.POINTER(HgTrackedConsts), vp, vp, vp, vp]),
+        "hg_tracker_create": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), C.POINTER(vp)]),
+        "hg_tracker_free": (None, [vp]),
+        "hg_tracker_reset": (C.c_int, [vp]),
+        "hg_tracker_step_frame_device": (C.c_int, [vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
+                                                   C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(C.c_int), vp]),
         "hg_sfa_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_pca_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_train_apply_device": (C.c_int, [vp, i32, i64, i64, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, i64, i32]),
@@ -149,6 +159,7 @@ EXPORTED_SYMBOLS = (
     "hg_cascade_detect_levels_device", "hg_cascade_detect_frame_device", "hg_cascade_grid_device", "hg_gauss_regression_multi_device",
     "hg_sfa_train_layer", "hg_pca_train_layer", "hg_train_apply_device",
     "hg_eyes_create", "hg_eyes_free", "hg_eyes_locate_device", "hg_eyes_boxes_device", "hg_purge_detections_device", "hg_cascade_detect_faces_frame_device",
+    "hg_cascade_tracked_grid_device", "hg_tracker_create", "hg_tracker_free", "hg_tracker_reset", "hg_tracker_step_frame_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

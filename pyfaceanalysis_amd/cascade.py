@@ -80,6 +80,18 @@ def frame_levels(im_width, im_height, smallest_face, pipeline, subimage_size):
     return arr, len(svals), sum(arr[i].nx * arr[i].ny for i in range(len(svals)))
 
 
+def tracked_windows(box, pipeline, subimage_size):
+    """The nine windows of a frame that follows a found face (grid.tracked_boxes; the reference's ``track_single_face`` branch)
+    with, per window, (max_Dx_diff, max_Dy_diff, base_side) — the layout ``frame_windows`` returns.  ``box``: (x0, y0, x1, y1) of the
+    previous frame's first purged detection, in the coordinates of the prescaled frame.  What k_cascade_init_tracked writes on the
+    device, bit for bit (tests/test_tracking_gpu.py)."""
+    p = dict(pipeline)
+    sw, sh = subimage_size
+    _, _, pw, ph, max_dx, max_dy = grid.tracked_positions(box, sw, sh, p["regression_width"], p["regression_height"], p["net_Dx"], p["net_Dy"])
+    boxes = grid.tracked_boxes(box, sw, sh, p["regression_width"], p["regression_height"], p["net_Dx"], p["net_Dy"])
+    return boxes, np.tile([max_dx, max_dy, math.sqrt(pw ** 2 + ph ** 2)], (9, 1))
+
+
 class DeviceCascade(object):
     def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0):
         import torch

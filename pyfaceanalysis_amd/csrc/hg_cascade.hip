@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 
 #include "hg_common.hpp"
@@ -21,6 +22,9 @@ namespace hg {
 void set_last_error(const std::string& s);
 void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
                      const double* conf, int64_t n, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st);
+void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
+                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts, hipStream_t st);
+void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts);
 int eyes_device(const hg_eyes* e);
 }
 
@@ -161,6 +165,7 @@ struct StageArrays {
     int32_t* map;
     int32_t *count_in, *count_out;
     int32_t k_feat, cur, n_max;
+    int32_t pad_to;      // > 0 (a tracked frame): rows [new count, pad_to) of the nxt arrays get a defined window (k_cascade_group)
 };
 
 // What the host polls instead of synchronising the stream (pinned, device-visible): word 0 = survivor count, word 1 = sequence
@@ -236,6 +241,72 @@ __global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coor
         neg[i] = 0.0;
         conf[i] = 0.0;
         oidx[i] = i;
+    }
+}
+
+// The start of a TRACKED frame (the reference's track_single_face branch with a face found on the previous frame): nine windows from
+// the four doubles of the tracked box, which the previous frame's last kernel left in device memory — one sampling value from the
+// box's size (face_analysis.py:576-585), posX = (x0, x0 + sepx, x0 - sepx), posY = (y0, y0, y0) (:611-623), their product y-major
+// (:661-669: the three distinct windows, three times), the level constants (:650-651, FaceDetectUpdated.py:603-604).  float64 in the
+// reference's operation order, no contraction (pragma above): equal to grid.tracked_boxes / cascade.tracked_windows and to the
+// reference's own outputs bit for bit (tests/golden/reference_tracking.npz).  One workgroup; writes what k_cascade_init_grid writes.
+constexpr int kTracked = 9;
+__global__ void k_cascade_init_tracked(hg_tracked_consts t, const double* __restrict__ face, double* __restrict__ orig_coords, double* __restrict__ orig_level,
+                                       double* __restrict__ coords, double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf,
+                                       int32_t* __restrict__ oidx, int32_t* __restrict__ count) {
+    const int i = threadIdx.x;
+    if (i == 0 && count) *count = kTracked;
+    if (i >= kTracked) return;
+    const double fx0 = face[0], fy0 = face[1], fx1 = face[2], fy1 = face[3];
+    const double face_size = d_add(d_mul(0.5, fabs(d_sub(fx1, fx0))), d_mul(0.5, fabs(d_sub(fy1, fy0))));      // :582
+    const double s = d_div(d_mul(face_size, 1.0), t.subimage_width);                                                // :583
+    const double pw = d_mul(t.subimage_width, s), ph = d_mul(t.subimage_height, s);                                   // :612-613
+    const double sepx = d_div(d_mul(d_mul(t.net_Dx, 2.0), pw), t.regression_width);                               // :615
+    const int ix = i % 3;                                                                                                // y-major, three per row
+    const double x0 = ix == 0 ? fx0 : (ix == 1 ? d_add(fx0, sepx) : d_sub(fx0, sepx)), y0 = fy0;                   // :622-623
+    const double b[4] = {x0, y0, d_sub(d_add(x0, pw), 1.0), d_sub(d_add(y0, ph), 1.0)};                       // :668
+    for (int q = 0; q < 4; ++q) orig_coords[(size_t)i * 4 + q] = b[q];
+    orig_level[(size_t)i * 3] = d_div(d_mul(t.net_Dx, pw), t.regression_width);                                      // :650
+    orig_level[(size_t)i * 3 + 1] = d_div(d_mul(t.net_Dy, ph), t.regression_height);                                 // :651
+    orig_level[(size_t)i * 3 + 2] = __dsqrt_rn(d_add(d_mul(pw, pw), d_mul(ph, ph)));                            // FaceDetectUpdated.py:603-604
+    if (coords) {
+        for (int q = 0; q < 4; ++q) coords[(size_t)i * 4 + q] = b[q];
+        angles[i] = 0.0;
+        neg[i] = 0.0;
+        conf[i] = 0.0;
+        oidx[i] = i;
+    }
+}
+
+// The last kernel of a tracker's frame: row 0 of the purged rows becomes the tracked face (FaceDetectUpdated.py:1189-1195) — its box
+// goes into the tracker's device state, where the next frame's k_cascade_init_tracked reads it, with the found flag (a box that is
+// not finite is not carried) — and, for a tracked frame, everything the host needs goes to pinned memory: the kept rows, the two
+// counts, the flag, and last the sequence number the host waits for.  counts: {faces after the discard, faces after the purge}.
+struct TrackerResults {
+    int32_t* words;      // pinned: {kept, before the purge, found, sequence number}; null: no read-back (the host has the rows already)
+    double* rows;        // pinned: [cap][10]
+    int32_t cap;
+};
+__global__ void __launch_bounds__(128) k_tracker_handover(const double* __restrict__ purged, const int32_t* __restrict__ counts, double* __restrict__ box,
+                                                          int32_t* __restrict__ found, TrackerResults R, int seq) {
+    const int tid = threadIdx.x;
+    const int kept = counts[1];
+    bool ok = kept > 0;
+    if (ok)
+        for (int q = 0; q < 4; ++q) ok = ok && isfinite(purged[q]);
+    if (ok && tid < 4) box[tid] = purged[tid];
+    if (tid == 0) *found = ok ? 1 : 0;
+    if (!R.words) return;
+    const int nrow = kept < R.cap ? kept : R.cap;
+    for (int q = tid; q < nrow * 10; q += blockDim.x) R.rows[q] = purged[q];
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+        R.words[0] = kept;
+        R.words[1] = counts[0];
+        R.words[2] = ok ? 1 : 0;
+        __threadfence_system();
+        __hip_atomic_store(R.words + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -339,6 +410,19 @@ __global__ void __launch_bounds__(1024) k_cascade_group(GroupDesc G, hg_cascade_
     for (int e = tid; e < cnt * kf; e += blockDim.x) {
         const int j = e / kf, f = e - j * kf;
         A.sl[nxt][(size_t)j * kf + f] = A.sl[cur][(size_t)A.map[j] * kf + f];
+    }
+    // A tracked frame sizes the next launches by its bound, not by this count: the rows between them, which a compaction leaves as
+    // they were, get a defined, finite window (the frame's first pixel, no rotation) and zero features, so that the extraction, the
+    // network and the regression of the next group read defined data; the next glue launch skips them by the device count.
+    if (A.pad_to > cnt) {
+        for (int j = cnt + tid; j < A.pad_to; j += blockDim.x) {
+            A.coords[nxt][(size_t)j * 4] = 0.0; A.coords[nxt][(size_t)j * 4 + 1] = 0.0; A.coords[nxt][(size_t)j * 4 + 2] = 1.0; A.coords[nxt][(size_t)j * 4 + 3] = 1.0;
+            A.angles[nxt][j] = 0.0;
+            A.neg_angles[j] = 0.0;
+            A.oidx[nxt][j] = 0;
+            A.conf[nxt][j] = 0.0;
+        }
+        for (int e = cnt * kf + tid; e < A.pad_to * kf; e += blockDim.x) A.sl[nxt][e] = 0.0f;
     }
     if (H.cap > 0 && cnt <= H.cap) {      // last group: the survivors themselves, for the host (nxt[] is complete: barrier)
         __syncthreads();
@@ -630,12 +714,29 @@ uint64_t key_of(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
     return h ? h : 1;
 }
 
+// A TRACKED frame (`B`): the windows are the nine of k_cascade_init_tracked, built from the box at B->face_dev, and the candidate
+// count never visits the host.  Nine bounds it from the start, so every launch of every group is sized by nine and the glue kernels
+// take the live count from the device word they already carry (A.count_in under A.n_max); no poll_count runs, stage_counts is -1
+// throughout, and nothing is copied out: the survivors stay in coords[*final_buf] ..., their count in *B->final_count, for the eye
+// step (eyes_frame_tail_bounded).  Rows between the live count and the bound: k_cascade_group gives them a defined window and
+// zero features after every compaction (A.pad_to), so each extraction reads finite boxes and each network defined pixels; the
+// sub-images carried over a Disc stage are gathered by the device count (k_gather_rows) and the rows past it keep earlier bytes —
+// any byte is a pixel, rows are independent, and the next glue launch skips them by the count.  A live count of 0 is a normal
+// case: every later launch runs on nine filler rows and compacts none.
+struct Bounded {
+    const double* face_dev;
+    hg_tracked_consts tc;
+    const int32_t* final_count;      // out
+};
+
 void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
                  const LevelTable* T, int64_t n0, double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence,
-                 int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr) {
+                 int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr,
+                 Bounded* B = nullptr) {
     if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
     if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
-    if (n0 > 0 && (!frame_dev || (!T && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
+    if (n0 > 0 && (!frame_dev || (!T && !B && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
+    if (B && (n0 != kTracked || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
     set_dev(c->device);
     hipStream_t st = (hipStream_t)stream;
     const int ns = (int)c->stages.size();
@@ -646,7 +747,11 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         return;
     }
     c->reserve(n0);
-    if (T) {
+    if (B) {
+        hipLaunchKernelGGL(k_cascade_init_tracked, 1, 64, 0, st, B->tc, B->face_dev, (double*)c->orig_coords.p, (double*)c->orig_level.p,
+                           (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
+                           (int32_t*)c->count.p);
+    } else if (T) {
         hipLaunchKernelGGL(k_cascade_init_grid, (unsigned)((n0 + 255) / 256), 256, 0, st, *T, (double*)c->orig_coords.p, (double*)c->orig_level.p,
                            (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
                            (int32_t*)c->count.p);
@@ -754,10 +859,11 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         A.k_feat = c->k;
         A.cur = cur;
         A.n_max = (int32_t)n_bound;
+        A.pad_to = B ? (int32_t)n_bound : 0;
         // the host needs the exact count where it shrinks and sizes the next launches: after every group with a Disc stage (the
         // read-back is a poll of a pinned word, cheap enough for the small stages too), and at the end
         const bool last = k + m == ns;
-        const bool want_count = any_disc || last;
+        const bool want_count = !B && (any_disc || last);      // a tracked frame: the bound sizes the launches, nothing is read back
         const int32_t seq = want_count ? ++c->seq : 0;
         HostResults Hk{};
         if (n_bound > 2 * kChunk) {      // many frames' windows: one workgroup per kChunk candidates, two launches
@@ -766,7 +872,7 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
             hipLaunchKernelGGL(k_cascade_group_mark, chunks, 1024, 0, st, G, c->base, A, c->cap, (int32_t*)c->chunk_count.p);
             hipLaunchKernelGGL(k_cascade_group_scatter, chunks, 1024, 0, st, m, A, (const int32_t*)c->chunk_count.p, want_count ? c->host_count : nullptr, seq);
         } else {
-            if (last && n_bound <= hg_cascade::kResCap) {
+            if (last && !B && n_bound <= hg_cascade::kResCap) {
                 Hk = H;
                 Hk.cap = hg_cascade::kResCap;
                 results_on_host = true;
@@ -789,6 +895,13 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
             for (int s = 0; s < m && stage_counts; ++s) stage_counts[k + s] = -1;      // not read back (no stage of the group discards by a cut-off: bound of the last Disc stage)
         }
         k += m;
+    }
+    if (B) {      // the survivors and their count stay on the device
+        B->final_count = (const int32_t*)c->count.p + cnt_slot;
+        *n_out = n_bound;
+        if (rows_executed) *rows_executed = rows;
+        if (final_buf) *final_buf = cur;
+        return;
     }
     if (n_bound > out_cap) hg::fail(HG_ERR_ARG, "%lld detections but room for %lld", (long long)n_bound, (long long)out_cap);
     if (n_bound > 0 && results_on_host) {      // written by the last group's kernel before it published the count
@@ -918,3 +1031,160 @@ int hg_cascade_grid_device(int device, const hg_cascade_level* levels, int n_lev
 
 }  // extern "C"
 
+// ---- tracking one face across a frame stream (include/higsfa.h) ---------------------------------------------------------------
+struct hg_tracker {
+    hg_cascade* c = nullptr;
+    hg_eyes* e = nullptr;
+    hg_tracked_consts tc{};
+    hg::DevBuf state;                // device: tracked box (4 doubles), then the found flag (int32)
+    bool found = false;              // host mirror of the flag: decides which path the next step takes
+    int w = 0, h = 0;                // prescaled frame size the box belongs to
+    char* host_res = nullptr;        // pinned: words {kept, before the purge, found, sequence number} at 0, rows at 64
+    int32_t seq = 0;
+    static constexpr int kRows = kTracked + 1;      // the purge may keep n + 1 rows
+    double* box_dev() const { return (double*)state.p; }
+    int32_t* found_dev() const { return (int32_t*)((char*)state.p + 32); }
+};
+
+namespace {
+void check_finite_consts(const hg_tracked_consts& t) {
+    const double v[6] = {t.subimage_width, t.subimage_height, t.regression_width, t.regression_height, t.net_Dx, t.net_Dy};
+    for (double x : v)
+        if (!(x > 0.0) || !std::isfinite(x)) hg::fail(HG_ERR_ARG, "tracked-grid constants must be positive and finite");
+}
+}  // namespace
+
+extern "C" {
+
+int hg_cascade_tracked_grid_device(int device, const hg_tracked_consts* consts, const double* face_dev, double* boxes_dev, double* level_dev, void* stream) {
+    return guarded([&] {
+        if (!consts || !face_dev || !boxes_dev || !level_dev) hg::fail(HG_ERR_ARG, "null argument");
+        check_finite_consts(*consts);
+        set_dev(device);
+        hipLaunchKernelGGL(k_cascade_init_tracked, 1, 64, 0, (hipStream_t)stream, *consts, face_dev, boxes_dev, level_dev, (double*)nullptr, (double*)nullptr,
+                           (double*)nullptr, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        HG_HIP(hipGetLastError());
+    });
+}
+
+int hg_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, hg_tracker** out) {
+    return guarded([&] {
+        if (!out) hg::fail(HG_ERR_ARG, "null output handle pointer");
+        *out = nullptr;
+        if (!c || !e || !consts) hg::fail(HG_ERR_ARG, "null argument");
+        check_finite_consts(*consts);
+        if (consts->subimage_width != (double)c->w || consts->subimage_height != (double)c->h)
+            hg::fail(HG_ERR_ARG, "tracked-grid sub-image %g x %g, the cascade's is %d x %d", consts->subimage_width, consts->subimage_height, c->w, c->h);
+        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+        set_dev(c->device);
+        auto t = std::make_unique<hg_tracker>();
+        t->c = c;
+        t->e = e;
+        t->tc = *consts;
+        t->state.alloc(48);
+        HG_HIP(hipMemset(t->state.p, 0, 48));
+        HG_HIP(hipHostMalloc((void**)&t->host_res, 64 + (size_t)hg_tracker::kRows * 80, hipHostMallocDefault));
+        memset(t->host_res, 0, 64);
+        *out = t.release();
+    });
+}
+
+void hg_tracker_free(hg_tracker* t) {
+    if (!t) return;
+    if (hipSetDevice(t->c->device) == hipSuccess && t->host_res) (void)hipHostFree(t->host_res);
+    delete t;
+}
+
+int hg_tracker_reset(hg_tracker* t) {
+    return guarded([&] {
+        if (!t) hg::fail(HG_ERR_ARG, "null tracker handle");
+        set_dev(t->c->device);
+        HG_HIP(hipMemset(t->found_dev(), 0, 4));      // steps are synchronous: nothing of this tracker is in flight
+        t->found = false;
+        t->w = t->h = 0;
+    });
+}
+
+int hg_tracker_step_frame_device(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h,
+                                 const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge,
+                                 int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid, void* stream) {
+    return guarded([&] {
+        if (!t || !n_out) hg::fail(HG_ERR_ARG, "null argument");
+        if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+        hg_cascade* c = t->c;
+        hg_eyes* e = t->e;
+        hipStream_t st = (hipStream_t)stream;
+        *n_out = 0;
+        if (n_before_purge) *n_before_purge = 0;
+        if (used_tracked_grid) *used_tracked_grid = 0;
+        const void* fr;
+        int fh, fw;
+        int64_t fld;
+        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
+        if (t->found && (fw != t->w || fh != t->h)) t->found = false;      // the box means nothing on another frame size
+        int64_t n = 0;
+        int cur = 0;
+        const double* purged = nullptr;
+        const int32_t* counts = nullptr;
+        if (!t->found) {
+            // what hg_cascade_detect_faces_frame_device runs, then row 0 (if any) becomes the tracked face
+            const LevelTable T = make_level_table(levels, n_levels);
+            const int64_t n0 = T.first[T.n_levels];
+            detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
+            hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
+                                out_rows, out_cap, n_out, n_before_purge, st);
+            bool ok = *n_out > 0;
+            for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(out_rows[q]);
+            if (ok) {      // the box goes from the purge's device rows into the tracker's state, in stream order before the next frame
+                hg::eyes_tail_buffers(e, &purged, &counts);
+                hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->found_dev(), TrackerResults{}, 0);
+                HG_HIP(hipGetLastError());
+            } else {
+                HG_HIP(hipMemsetAsync(t->found_dev(), 0, 4, st));
+            }
+            t->found = ok;
+            t->w = fw;
+            t->h = fh;
+            return;
+        }
+        // the tracked frame: everything enqueued back to back, one wait at the end
+        if (used_tracked_grid) *used_tracked_grid = 1;
+        Bounded B{};
+        B.face_dev = t->box_dev();
+        B.tc = t->tc;
+        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, nullptr, kTracked, nullptr, nullptr, nullptr, nullptr, kTracked, &n, stage_counts, rows_executed,
+                    stream, &cur, &B);
+        hg::eyes_frame_tail_bounded(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p,
+                                    kTracked, B.final_count, &purged, &counts, st);
+        TrackerResults R{};
+        R.words = (int32_t*)t->host_res;
+        R.rows = (double*)(t->host_res + 64);
+        R.cap = hg_tracker::kRows;
+        const int32_t seq = ++t->seq;
+        hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->found_dev(), R, seq);
+        HG_HIP(hipGetLastError());
+        // the one wait: the sequence word is polled (a stream synchronisation costs 20-40 us more, see publish_count); a deadline guards
+        // against a device that never answers
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 0; __atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) != seq; ++spins) {
+            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+                HG_HIP(hipStreamSynchronize(st));
+                if (__atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) == seq) break;
+                t->found = false;
+                hg::fail(HG_ERR_DEVICE, "tracked frame did not report its result");
+            }
+            __builtin_ia32_pause();
+        }
+        const int64_t kept = R.words[0];
+        if (n_before_purge) *n_before_purge = R.words[1];
+        t->found = R.words[2] != 0;
+        if (kept > out_cap || kept > R.cap) hg::fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)std::min<int64_t>(out_cap, R.cap));
+        if (kept > 0) {
+            if (!out_rows) hg::fail(HG_ERR_ARG, "null output rows");
+            memcpy(out_rows, R.rows, (size_t)kept * 80);
+        }
+        *n_out = kept;
+    });
+}
+
+}  // extern "C"

@@ -87,10 +87,20 @@ void set_dev(int device) {
 // compute_approximate_eye_boxes_coordinates(box, face_sampling=0.825, eye_sampling=2.3719, rot_angle=angle), face_analysis.py:61-135
 // (its body spells the two samplings as literals; here they are the constants, equal to them).  Left box -> row i, right box ->
 // row n + i; both patches are cut from the frame rotated by delta_ang = -1 * angle (face_analysis.py:1042, :782).
-__global__ void k_eye_boxes(int64_t n, const double* __restrict__ boxes, const double* __restrict__ angles, hg_eye_consts c,
-                            double* __restrict__ eboxes, double* __restrict__ dang) {
+// n_dev (nullable): the number of faces lives on the device and n is the host's bound of it (a tracked frame, hg_cascade.hip) — the
+// layout stays that of n faces, and the rows of the faces between the live count and n, whose boxes are whatever an earlier frame
+// left there, get one defined window (the frame's first pixel, no rotation): the extraction and the networks behind this kernel are
+// sized by n and must read finite boxes.
+__global__ void k_eye_boxes(int64_t n, const int32_t* __restrict__ n_dev, const double* __restrict__ boxes, const double* __restrict__ angles,
+                            hg_eye_consts c, double* __restrict__ eboxes, double* __restrict__ dang) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (n_dev && i >= *n_dev) {
+        const double filler[4] = {0.0, 0.0, 1.0, 1.0};
+        for (int q = 0; q < 4; ++q) eboxes[i * 4 + q] = eboxes[(n + i) * 4 + q] = filler[q];
+        if (dang) dang[i] = dang[n + i] = 0.0;
+        return;
+    }
     const double x0 = boxes[i * 4], y0 = boxes[i * 4 + 1], x1 = boxes[i * 4 + 2], y1 = boxes[i * 4 + 3], ang = angles[i];
     const double fc_x = d_div(d_add(x0, x1), 2.0), fc_y = d_div(d_add(y0, y1), 2.0);                          // :89-90
     const double two_fs = d_mul(2.0, c.face_sampling);
@@ -167,7 +177,8 @@ __device__ __forceinline__ void shift_eye(const double* b, double rx, double ry,
 // Too-far test, rotated shift and eye centres per face; then the order-preserving compaction of the faces kept
 // (FaceDetectUpdated.py:1010-1017; k_cascade_compact's ballot scan, one workgroup over chunks of its size) and the 10-column rows
 // (:1036-1041).  reg: [0, 2n) EyeLX, [reg_stride, reg_stride + 2n) EyeLY; row i left eye, n + i right eye.  Every output may be null.
-__global__ void __launch_bounds__(1024) k_eyes_glue(int64_t n, hg_eye_consts c, const double* __restrict__ boxes, const double* __restrict__ angles,
+// n_dev (nullable): only the first min(*n_dev, n) faces exist (k_eye_boxes); the layout stays that of n faces.
+__global__ void __launch_bounds__(1024) k_eyes_glue(int64_t n, const int32_t* __restrict__ n_dev, hg_eye_consts c, const double* __restrict__ boxes, const double* __restrict__ angles,
                                                     const double* __restrict__ conf, const double* __restrict__ eboxes, const double* __restrict__ reg,
                                                     int64_t reg_stride, double* __restrict__ ecoords, uint8_t* __restrict__ toofar,
                                                     double* __restrict__ rows, int32_t* __restrict__ count) {
@@ -176,11 +187,12 @@ __global__ void __launch_bounds__(1024) k_eyes_glue(int64_t n, hg_eye_consts c, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) base = 0;
     __syncthreads();
-    for (int64_t i0 = 0; i0 < n; i0 += blockDim.x) {
+    const int64_t live = (n_dev && *n_dev < n) ? (int64_t)*n_dev : n;
+    for (int64_t i0 = 0; i0 < live; i0 += blockDim.x) {
         const int64_t i = i0 + tid;
         int keep = 0;
         double e[4] = {0.0, 0.0, 0.0, 0.0};
-        if (i < n) {
+        if (i < live) {
             const double rxl = reg[i], rxr = reg[n + i], ryl = reg[reg_stride + i], ryr = reg[reg_stride + n + i];
             const bool far = fabs(rxl) >= c.tolerance || fabs(ryl) >= c.tolerance || fabs(rxr) >= c.tolerance || fabs(ryr) >= c.tolerance;
             const double rad = d_div(d_mul(-angles[i], M_PI), 180.0);                           // face_analysis.py:1096
@@ -335,9 +347,12 @@ void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, doubl
 }
 
 // The eye step for n faces on the device (n known on the host).  Outputs as in hg_eyes_locate_device; rows / count (nullable): the
-// discard and the row assembly as well (conf needed then).
+// discard and the row assembly as well (conf needed then).  n_dev (nullable): the face count stays on the device and n bounds it —
+// every launch is sized by n; k_eye_boxes gives the faces past the live count a defined window, so the extraction, the contrast
+// step and the networks read defined data in all 2n rows, and k_eyes_glue assembles the live faces only.
 void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles, const double* conf,
-              int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st) {
+              int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st,
+              const int32_t* n_dev = nullptr) {
     if (n == 0) {
         if (count) HG_HIP(hipMemsetAsync(count, 0, 4, st));
         return;
@@ -345,7 +360,7 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
     e->reserve(n);
     const hg_eye_consts& c = e->c;
     const int64_t wh = (int64_t)c.eye_w * c.eye_h, n2 = 2 * n;
-    hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
+    hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, n_dev, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
     HG_HIP(hipGetLastError());
     if (hg_patcher_extract_rotate_device(e->patcher, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p, (const double*)e->dang.p, n2,
                                          c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st) != HG_OK)
@@ -366,7 +381,7 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
             hg_gauss_regression_multi_device(&e->gy, 1, e->sl2.p, HG_F32, n2, k, rg + n2, n2, st) != HG_OK)
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
     }
-    hipLaunchKernelGGL(k_eyes_glue, 1, 1024, 0, st, n, c, boxes, angles, conf, (const double*)e->eboxes.p, (const double*)rg, n2, ecoords, toofar,
+    hipLaunchKernelGGL(k_eyes_glue, 1, 1024, 0, st, n, n_dev, c, boxes, angles, conf, (const double*)e->eboxes.p, (const double*)rg, n2, ecoords, toofar,
                        rows, count);
     HG_HIP(hipGetLastError());
 }
@@ -398,6 +413,27 @@ void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w
         HG_HIP(hipStreamSynchronize(st));
     }
     *n_out = kept;
+}
+
+// The same tail for a tracked frame (hg_tracker_step_frame_device): the survivor count is the device word *n_dev, at most n_bound; the
+// eye step, the discard, the rows and the purge are enqueued and NOTHING is read back — the caller's last kernel fetches what the host
+// needs.  *purged: the kept rows (room for n_bound + 1); *counts: {faces after the discard, faces after the purge}, both on the device.
+// A live count of 0 runs through every launch: k_eyes_glue and k_purge then write counts of 0.
+void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
+                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts, hipStream_t st) {
+    if (!e || !n_dev || n_bound < 1) fail(HG_ERR_ARG, "bad bounded eye step");
+    e->reserve(n_bound);      // before any workspace pointer is taken (see eyes_frame_tail)
+    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n_bound, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st,
+             n_dev);
+    launch_purge((const double*)e->rows.p, n_bound, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st);
+    *purged = (const double*)e->purged.p;
+    *counts = (const int32_t*)e->count.p;
+}
+
+// What the tracker's hand-over kernel reads after an ordinary frame's tail (eyes_frame_tail with n > 0): the same two buffers.
+void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts) {
+    *purged = (const double*)e->purged.p;
+    *counts = (const int32_t*)e->count.p;
 }
 
 int eyes_device(const hg_eyes* e) { return e ? e->device : -1; }
@@ -473,7 +509,7 @@ int hg_eyes_boxes_device(hg_eyes* e, const double* boxes_dev, const double* angl
         if (n > 0 && (!boxes_dev || !angles_dev || !eye_boxes_dev)) hg::fail(HG_ERR_ARG, "null data pointer");
         set_dev(e->device);
         if (n == 0) return;
-        hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream, n, boxes_dev, angles_dev, e->c, eye_boxes_dev,
+        hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream, n, (const int32_t*)nullptr, boxes_dev, angles_dev, e->c, eye_boxes_dev,
                            delta_angs_dev);
         HG_HIP(hipGetLastError());
     });

@@ -1,6 +1,6 @@
 """Sliding-window grid of the detection cascade: which sub-images reach the hot call.
 
-Restates (vectorised, adaptive non-tracking branch only) the three grid builders of the reference,
+Restates (vectorised; the adaptive branch and the tracking branch) the three grid builders of the reference,
 which decide N for every ``flow.execute`` call (SURVEY.md §2.1 "grid builders", Appendix B):
 
 * ``compute_sampling_values``                         face_analysis.py:575-607
@@ -9,8 +9,10 @@ which decide N for every ``flow.execute`` call (SURVEY.md §2.1 "grid builders",
 
 and the constants of ``Pipelines/Pipeline_experimental.txt:2`` / FaceDetectUpdated.py:84,110-111,121-122.
 These are O(N) host formulas; they are here so that a frame can be turned into the batches of
-BASELINE.json config 3 without the reference's script.  The tracking branches
-(``track_single_face``) and the non-adaptive branches are out of scope.
+BASELINE.json config 3 without the reference's script.  The tracking branch (``track_single_face`` with a face
+found on the previous frame: ``tracked_sampling_value``, ``tracked_boxes``; face_analysis.py:576-585, :611-623) is
+restated too, in plain float64 in the reference's operation order (tests/golden/reference_tracking.npz pins it bit for
+bit).  The non-adaptive branches are out of scope.
 """
 from __future__ import annotations
 
@@ -76,3 +78,34 @@ def frame_boxes(im_width, im_height, smallest_face=0.2, pipeline=None, subimage_
         levels.append((s, level_boxes(im_width, im_height, s, p["subimage_width"], p["subimage_height"],
                                       p["regression_width"], p["regression_height"], p["net_Dx"], p["net_Dy"])))
     return levels
+
+
+def tracked_sampling_value(box, subimage_width):
+    """The ONE sampling value of a frame that follows a found face (face_analysis.py:576-585): the mean of the tracked box's sides
+    over the sub-image width.  ``box``: (x0, y0, x1, y1) of the first purged detection of the previous frame."""
+    x0, y0, x1, y1 = (float(v) for v in box[:4])
+    face_size = 0.5 * abs(x1 - x0) + 0.5 * abs(y1 - y0)
+    return face_size * 1.0 / subimage_width
+
+
+def tracked_positions(box, subimage_width, subimage_height, regression_width, regression_height, net_Dx, net_Dy):
+    """posX (3), posY (3), patch width, patch height, max_Dx_diff, max_Dy_diff of the tracking branch (face_analysis.py:611-623,
+    :650-651): the box's corner and one horizontal separation step to either side, all three at the box's own y."""
+    x0, y0 = float(box[0]), float(box[1])
+    s = tracked_sampling_value(box, subimage_width)
+    pw, ph = subimage_width * s, subimage_height * s
+    sep_x = net_Dx * 2.0 * pw / regression_width
+    return ([x0, x0 + sep_x, x0 - sep_x], [y0, y0, y0], pw, ph, net_Dx * pw / regression_width, net_Dy * ph / regression_height)
+
+
+def tracked_boxes(box, subimage_width=None, subimage_height=None, regression_width=None, regression_height=None, net_Dx=None, net_Dy=None):
+    """(9, 4) windows of a tracked frame: the product of posX and posY (face_analysis.py:661-669), y-major — the three distinct
+    boxes (x, y0, x + pw - 1, y0 + ph - 1), three times over, because posY holds the same value three times.  The duplicates reach
+    the purge as they do in the reference.  Constants default to ``FACE_PIPELINE``'s."""
+    p = FACE_PIPELINE
+    sw = p["subimage_width"] if subimage_width is None else subimage_width
+    sh = p["subimage_height"] if subimage_height is None else subimage_height
+    xs, ys, pw, ph, _, _ = tracked_positions(box, sw, sh, p["regression_width"] if regression_width is None else regression_width,
+                                             p["regression_height"] if regression_height is None else regression_height,
+                                             p["net_Dx"] if net_Dx is None else net_Dx, p["net_Dy"] if net_Dy is None else net_Dy)
+    return np.array([[x, y, x + pw - 1, y + ph - 1] for y in ys for x in xs], dtype=np.float64)
