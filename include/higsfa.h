@@ -230,6 +230,28 @@ int hg_patcher_extract_rotate_device(hg_patcher* p, const void* frame_dev, int f
 int hg_patcher_extract_rotate(hg_patcher* p, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld,
                               const double* boxes, const double* delta_angs, int64_t n, int out_w, int out_h,
                               void* out, int out_dtype, int64_t ldo);
+/* The same windows with PIL's interpolation filters (FaceDetectUpdated.py:125 chooses one per cascade stage).  The codes are PIL's
+ * own, so a caller passes Image.BILINEAR straight through; any other code is HG_ERR_ARG.  filter = 0 is
+ * hg_patcher_extract_rotate(_device), bit for bit.  BILINEAR / BICUBIC follow ImagingGenericTransform with affine_transform
+ * (Geometry.c) for mode "L" images, every operation in double and rounded on its own:
+ *   source point   xs = a0 (ox + 0.5) + a1 (oy + 0.5) + a2, ys likewise; outside [0, W) x [0, H) the pixel is 0; otherwise
+ *                  x = floor(xs - 0.5), dx = (xs - 0.5) - x, the same for y.  EXTENT: a = ((x1-x0)/w, 0, x0, 0, (y1-y0)/h, y0).
+ *   BILINEAR       2 x 2 taps, columns clipped, row y + 1 repeated from row y where it does not exist; (uint8) truncation.
+ *   BICUBIC        a = -0.5, 4 x 4 taps, columns clipped, row y - 1 clipped, rows y .. y + 2 repeat the previous row's value where
+ *                  they do not exist; <= 0 -> 0, >= 255 -> 255, else truncation.
+ * A window with delta_ang % 360 != 0 is frame.rotate(delta_ang, F, center = box centre).transform((w, h), EXTENT, box, F) with the
+ * SAME filter F in both steps (the build's choice, as for NEAREST: cuicuilco's composition is not available): the intermediate is a
+ * uint8 image, each tap of the second step a filtered, quantised pixel of the rotated frame (0 where the rotation reads outside the
+ * source).  The rotation uses the matrix Image.rotate builds as doubles (the 16.16 fixed point belongs to NEAREST: no range limit).
+ * Frames: HG_U8 only — an HG_F32 frame with a filter other than NEAREST is HG_ERR_ARG (PIL's mode "F" rule is a different one).
+ * Outputs: the uint8 value, converted to out_dtype.  Tested bit for bit against PIL. */
+enum hg_filter { HG_FILTER_NEAREST = 0, HG_FILTER_BILINEAR = 2, HG_FILTER_BICUBIC = 3 };
+int hg_patcher_extract_filter_device(hg_patcher* p, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w,
+                                     int64_t ld, const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w,
+                                     int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
+int hg_patcher_extract_filter(hg_patcher* p, int filter, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld,
+                              const double* boxes, const double* delta_angs, int64_t n, int out_w, int out_h, void* out,
+                              int out_dtype, int64_t ldo);
 
 /* --- Cascade glue on the device (the reference's stage loop between two hot calls) -----------------
  * update_current_subimage_coordinates (face_analysis.py:803-840) + identify_patches_to_discard (:842-887) for n
@@ -282,6 +304,13 @@ int hg_cascade_create(const hg_cascade_stage* stages, int n_stages, int sub_w, i
                       const hg_cascade_consts* consts, const double* cut_offs_face, int n_cut_offs, int device,
                       hg_cascade** out);
 void hg_cascade_free(hg_cascade* c);
+/* The interpolation filter of every stage's extraction (enum hg_filter), indexed by the stage's serial exactly like cut_offs_face:
+ * interpolation_formats[network_serial], FaceDetectUpdated.py:125, :671, :686.  HG_ERR_ARG (and nothing changed) if a stage's
+ * serial is >= n or a code is unknown.  Before the first call every stage is NEAREST.  A stage that skips its extraction (the stage
+ * before it is a Disc stage, or it has no network, :674-684) reuses the previous patches: its entry has no effect, as in the
+ * reference.  The prescale stays NEAREST (:551-561).  Takes effect from the next detect / step call on this handle; setting it
+ * while a call on this handle is in flight on another thread or stream is the caller's error. */
+int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n);
 /* frame_dev: (frame_h, frame_w) uint8 on the device, row stride ld; boxes_host (n0, 4) / level_host (n0, 3): the first-stage
  * windows and their level constants.  Outputs (host, room for out_cap detections): final coordinates, angles, index of the
  * original window, Disc confidence; *n_out detections; stage_counts[n_stages] survivors after each stage (-1 where the count
@@ -346,6 +375,11 @@ typedef struct hg_eye_consts {
 int hg_eyes_create(hg_flow* flow_x, hg_gauss* clf_x, hg_flow* flow_y, hg_gauss* clf_y, const hg_eye_consts* consts, int device,
                    hg_eyes** out);
 void hg_eyes_free(hg_eyes* e);
+/* The filter of the eye patches (enum hg_filter; NEAREST until set): the reference hands find_Left_eyes / find_Right_eyes whatever
+ * the stage loop's last iteration left in interpolation_format (FaceDetectUpdated.py:671, :994, :1001).  The contrast step after the
+ * gather is unchanged.  HG_ERR_ARG for an unknown code.  Takes effect from the next call on this handle; setting it while a call on
+ * this handle is in flight on another thread or stream is the caller's error. */
+int hg_eyes_set_interpolation(hg_eyes* e, int filter);
 /* The eye step for n faces, BEFORE the discard: frame_dev (h, w) uint8 on the device, row stride ld; boxes_dev (n,4) and angles_dev (n)
  * float64 on the device.  Outputs (device): eye_coords_dev (n,4) = (eyeL_x, eyeL_y, eyeR_x, eyeR_y), too_far_dev (n) 0/1;
  * patches_dev (nullable) the contrast-normalised patches (2n, eye_w*eye_h) float32; reg_dev (nullable) the regressions (2, 2n) float64,

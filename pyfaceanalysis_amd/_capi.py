@@ -11,9 +11,12 @@ HG_U8, HG_F32, HG_F64 = 0, 1, 2
 HG_OK = 0
 HG_ERR_ARG, HG_ERR_FORMAT, HG_ERR_DIM, HG_ERR_DEVICE, HG_ERR_NOMEM, HG_ERR_STATE = -1, -2, -3, -4, -5, -6
 HG_PLAN_GENERIC, HG_PLAN_FUSED = 0, 1
+HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC = 0, 2, 3      # enum hg_filter: PIL's own codes (Image.NEAREST / BILINEAR / BICUBIC)
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below)
+_ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _lib = None
 
 
@@ -114,6 +117,10 @@ def lib():
         "hg_patcher_extract": (C.c_int, [vp, vp, i32, i32, i32, i64, vp, i64, i32, i32, vp, i32, i64]),
         "hg_patcher_extract_rotate_device": (C.c_int, [vp, vp, i32, i32, i32, i64, vp, vp, i64, i32, i32, vp, i32, i64, vp]),
         "hg_patcher_extract_rotate": (C.c_int, [vp, vp, i32, i32, i32, i64, vp, vp, i64, i32, i32, vp, i32, i64]),
+        "hg_patcher_extract_filter_device": (C.c_int, [vp, i32, vp, i32, i32, i32, i64, vp, vp, i64, i32, i32, vp, i32, i64, vp]),
+        "hg_patcher_extract_filter": (C.c_int, [vp, i32, vp, i32, i32, i32, i64, vp, vp, i64, i32, i32, vp, i32, i64]),
+        "hg_cascade_set_interpolation": (C.c_int, [vp, vp, i32]),
+        "hg_eyes_set_interpolation": (C.c_int, [vp, i32]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_gather_rows_device": (C.c_int, [i32, vp, vp, i64, vp, vp, i64, vp]),
@@ -141,7 +148,14 @@ def lib():
         "hg_train_apply_device": (C.c_int, [vp, i32, i64, i64, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, i64, i32]),
     }
     for name, (res, args) in sigs.items():
-        fn = getattr(L, name)
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
+            # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
+            if name in _ENTRIES_SINCE_FILTERS and os.environ.get("HIGSFA_LIB"):
+                continue
+            raise
         fn.restype = res
         fn.argtypes = args
     _lib = L
@@ -160,6 +174,7 @@ EXPORTED_SYMBOLS = (
     "hg_sfa_train_layer", "hg_pca_train_layer", "hg_train_apply_device",
     "hg_eyes_create", "hg_eyes_free", "hg_eyes_locate_device", "hg_eyes_boxes_device", "hg_purge_detections_device", "hg_cascade_detect_faces_frame_device",
     "hg_cascade_tracked_grid_device", "hg_tracker_create", "hg_tracker_free", "hg_tracker_reset", "hg_tracker_step_frame_device",
+    "hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,
@@ -177,6 +192,17 @@ def check(rc):
     if rc == HG_ERR_DIM:
         raise NodeException(msg)
     raise _EXC.get(rc, RuntimeError)("higsfa: " + msg)
+
+
+def filter_code(f):
+    """An interpolation filter as enum hg_filter; PIL's Image.NEAREST / BILINEAR / BICUBIC (ints or IntEnum members) pass straight through."""
+    try:
+        code = int(f)
+    except (TypeError, ValueError):
+        code = None
+    if code not in (HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC) or isinstance(f, (bool, float)):
+        raise ValueError("unknown interpolation filter %r (0 NEAREST, 2 BILINEAR, 3 BICUBIC)" % (f,))
+    return code
 
 
 def np_dtype_code(dt):

@@ -93,7 +93,10 @@ def tracked_windows(box, pipeline, subimage_size):
 
 
 class DeviceCascade(object):
-    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0):
+    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0, interpolation_formats=None):
+        """interpolation_formats: the filter of every stage's extraction, a sequence indexed by the stage's serial like
+        ``CUT_OFFS_FACE`` (FaceDetectUpdated.py:125, :671; PIL's codes 0 / 2 / 3); None: NEAREST everywhere.  The prescale is
+        NEAREST whatever this says (:551-561)."""
         import torch
         self.torch = torch
         self.stages = list(stages)
@@ -110,6 +113,12 @@ class DeviceCascade(object):
         for st in self.stages:
             if st.classifier.input_dim > self.k:
                 raise ValueError("stage %s: classifier reads %d features, cascade keeps %d" % (st.name, st.classifier.input_dim, self.k))
+        self.interpolation_formats = None
+        if interpolation_formats is not None:
+            self.interpolation_formats = [_capi.filter_code(f) for f in interpolation_formats]
+            for st in self.stages:
+                if st.serial >= len(self.interpolation_formats):
+                    raise ValueError("stage %s: interpolation_formats has %d entries" % (st.name, len(self.interpolation_formats)))
 
     def _consts(self):
         p = self.pipeline
@@ -141,6 +150,9 @@ class DeviceCascade(object):
         h = C.c_void_p()
         _capi.check(L.hg_cascade_create(arr, len(self.stages), self.w, self.h, self.k, C.byref(cc), cut, len(CUT_OFFS_FACE), self.device, C.byref(h)))
         self._h = h
+        if self.interpolation_formats is not None:
+            fmt = (C.c_int32 * len(self.interpolation_formats))(*self.interpolation_formats)
+            _capi.check(L.hg_cascade_set_interpolation(h, fmt, len(self.interpolation_formats)))
         return h
 
     def prescale(self, frame, prescale_size=grid.PRESCALE_SIZE):

@@ -611,6 +611,7 @@ struct hg_cascade {
     std::vector<hg_cascade_stage> stages;
     hg_cascade_consts base{};
     double cut_offs[10];
+    int32_t interp[10] = {};             // enum hg_filter per serial (hg_cascade_set_interpolation); NEAREST until set
     hg_patcher* patcher = nullptr;
     int64_t cap = 0;
     hg::DevBuf coords[2], angles[2], conf[2], oidx[2], sl[2], subs[2], neg, reg, discard, map, count, orig_coords, orig_level, orig_angles, chunk_count;
@@ -673,6 +674,18 @@ int hg_cascade_create(const hg_cascade_stage* stages, int n_stages, int sub_w, i
         c->host_count[0] = c->host_count[1] = 0;
         HG_HIP(hipHostMalloc((void**)&c->host_res, (size_t)hg_cascade::kResCap * 52, hipHostMallocDefault));
         *out = c.release();
+    });
+}
+
+int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n) {
+    return guarded([&] {
+        if (!c || !filters || n <= 0) hg::fail(HG_ERR_ARG, "null cascade handle or empty filter list");
+        for (int i = 0; i < n; ++i)
+            if (filters[i] != HG_FILTER_NEAREST && filters[i] != HG_FILTER_BILINEAR && filters[i] != HG_FILTER_BICUBIC)
+                hg::fail(HG_ERR_ARG, "entry %d: unknown interpolation filter %d (0 NEAREST, 2 BILINEAR, 3 BICUBIC)", i, filters[i]);
+        for (size_t k = 0; k < c->stages.size(); ++k)
+            if (c->stages[k].serial >= n) hg::fail(HG_ERR_ARG, "stage %d: serial %d has no interpolation filter", (int)k, c->stages[k].serial);
+        for (int i = 0; i < 10; ++i) c->interp[i] = i < n ? filters[i] : HG_FILTER_NEAREST;      // (serials are < 10: hg_cascade_create)
     });
 }
 
@@ -814,10 +827,10 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         if (!skip_extract) {
             // (the first stage's angles are all zero: the plain EXTENT kernel — a window with delta_ang == 0 is cut from the frame itself —
             // and where the windows come from the level table they are a function of that table alone: their index tables are kept)
-            const int rc = k == 0 ? hg_patcher_extract_keyed_device(c->patcher, T ? key_of(T, sizeof *T) : 0, frame_dev, HG_U8, frame_h, frame_w, ld,
-                                                                    (const double*)c->coords[cur].p, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
-                                  : hg_patcher_extract_rotate_device(c->patcher, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)c->coords[cur].p,
-                                                                     (const double*)c->neg.p, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st);
+            // the stage's filter: interpolation_formats[network_serial] (FaceDetectUpdated.py:671, :686)
+            const int rc = hg::patcher_extract(c->patcher, k == 0 && T ? key_of(T, sizeof *T) : 0, c->interp[S.serial], frame_dev, HG_U8, frame_h, frame_w, ld,
+                                               (const double*)c->coords[cur].p, k == 0 ? nullptr : (const double*)c->neg.p, n_bound, c->w, c->h,
+                                               c->subs[sb].p, HG_U8, (int64_t)row, st);
             if (rc != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         }
         if (S.flow) {

@@ -156,4 +156,11 @@ struct DevBuf {
     DevBuf& operator=(const DevBuf&) = delete;
 };
 
+// hg_extract.hip: the one place that chooses the extraction kernels, for the C entries and for hg_cascade.hip.  filter NEAREST: the
+// existing entries (hg_patcher_extract_keyed_device when key != 0 and there are no angles, else hg_patcher_extract_rotate_device);
+// BILINEAR / BICUBIC: the filtered tables and gathers, with the same per-key table reuse for unrotated boxes (key = 0: none).
+int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w, int64_t ld,
+                    const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo,
+                    void* stream);
+
 }  // namespace hg

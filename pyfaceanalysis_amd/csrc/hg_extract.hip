@@ -21,6 +21,10 @@
 // one place this can differ from the host's libm is the last bit of cos / sin before the 15-decimal rounding, which
 // moves a fixed-point coefficient only if it sits within 7e-11 of a rounding boundary.  Rotated frames must stay inside
 // PIL's fixed-point range (|source coordinate| < 32768), otherwise the window is left 0.
+//
+// The reference's other filters (interpolation_formats, FaceDetectUpdated.py:125: BILINEAR, BICUBIC) are the second half of this
+// file ("BILINEAR / BICUBIC windows"): PIL's generic affine transform in doubles, the same composition for rotated windows with
+// the stage's filter in both steps.
 #include <hip/hip_runtime.h>
 
 #include "hg_common.hpp"
@@ -34,8 +38,10 @@ struct hg_patcher {
         uint64_t key = 0;
         int64_t n = 0;
         int out_w = 0, out_h = 0, frame_w = 0, frame_h = 0;
+        int filtered = 0;       // 1: the tables are FiltEnt (BILINEAR / BICUBIC), 0: NEAREST indices
         hg::DevBuf tabs;
     };
+    hg::DevBuf ftabs, frot;     // BILINEAR / BICUBIC: coordinate tables and rotation matrices of unkeyed calls
     Keyed keyed[4];
     int keyed_next = 0;
 };
@@ -228,19 +234,27 @@ __device__ __forceinline__ int32_t fix16(double v) {        // Geometry.c FIX():
     return x >= 0.0 ? (int32_t)x : (int32_t)floor(x);
 }
 
-__device__ __forceinline__ RotCoef rot_coef_of(const double* __restrict__ boxes, const double* __restrict__ angs, int64_t b, int fw, int fh) {
-    RotCoef rc{};
+// The matrix Image.rotate(angle, center = centre of box b) builds, m[0..5]; false: angle % 360 == 0 (or not finite), no rotation
+__device__ __forceinline__ bool rot_matrix(const double* __restrict__ boxes, const double* __restrict__ angs, int64_t b, double* m) {
     double a = fmod(angs[b], 360.0);                 // Python's float %: result carries the divisor's sign
     if (a < 0.0) a += 360.0;
     if (a == 360.0) a = 0.0;
-    if (a != 0.0 && isfinite(a)) {
-        const double cx = d_mul(d_add(boxes[b * 4], boxes[b * 4 + 2]), 0.5), cy = d_mul(d_add(boxes[b * 4 + 1], boxes[b * 4 + 3]), 0.5);
-        const double r = -d_mul(a, 3.14159265358979323846 / 180.0);       // -math.radians(angle)
-        const double c = round15(cos(r)), sn = round15(sin(r));
-        const double m0 = c, m1 = sn, m3 = -sn, m4 = c;
-        // transform(-cx, -cy, matrix) = (a x + b y) + c, then += center: every operation rounded on its own
-        const double m2 = d_add(d_add(d_add(d_mul(m0, -cx), d_mul(m1, -cy)), 0.0), cx);
-        const double m5 = d_add(d_add(d_add(d_mul(m3, -cx), d_mul(m4, -cy)), 0.0), cy);
+    if (!(a != 0.0 && isfinite(a))) return false;
+    const double cx = d_mul(d_add(boxes[b * 4], boxes[b * 4 + 2]), 0.5), cy = d_mul(d_add(boxes[b * 4 + 1], boxes[b * 4 + 3]), 0.5);
+    const double r = -d_mul(a, 3.14159265358979323846 / 180.0);       // -math.radians(angle)
+    const double c = round15(cos(r)), sn = round15(sin(r));
+    m[0] = c; m[1] = sn; m[3] = -sn; m[4] = c;
+    // transform(-cx, -cy, matrix) = (a x + b y) + c, then += center: every operation rounded on its own
+    m[2] = d_add(d_add(d_add(d_mul(m[0], -cx), d_mul(m[1], -cy)), 0.0), cx);
+    m[5] = d_add(d_add(d_add(d_mul(m[3], -cx), d_mul(m[4], -cy)), 0.0), cy);
+    return true;
+}
+
+__device__ __forceinline__ RotCoef rot_coef_of(const double* __restrict__ boxes, const double* __restrict__ angs, int64_t b, int fw, int fh) {
+    RotCoef rc{};
+    double m[6];
+    if (rot_matrix(boxes, angs, b, m)) {
+        const double m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5];
         if (m1 == 0.0 && m3 == 0.0) {
             rc.mode = 2;
             rc.m0 = m0; rc.m2 = m2; rc.m4 = m4; rc.m5 = m5;
@@ -380,6 +394,206 @@ __global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict_
     }
 }
 
+// ---- BILINEAR / BICUBIC windows (include/higsfa.h, hg_patcher_extract_filter_device) --------------------------------------------
+// PIL's ImagingGenericTransform with affine_transform and bilinear_filter8 / bicubic_filter8 (Geometry.c), for uint8 frames.  An
+// EXTENT window is separable: the source coordinate of output column ox depends on ox alone, so a box has a table of w + h
+// entries as for NEAREST, each holding the integer part and the fraction of its coordinate (`i` = kFiltOutside where PIL's range test
+// leaves the output pixel 0).  Unlike the NEAREST tables these are closed forms, one multiply-add per entry: PIL evaluates the affine
+// map per pixel, it has no running sum here.
+struct FiltEnt {
+    double d;       // fraction: (xs - 0.5) - floor(xs - 0.5)
+    int32_t i;      // floor(xs - 0.5), in [-1, size - 1]
+    int32_t pad;
+};
+constexpr int32_t kFiltOutside = INT32_MIN;
+
+// Image.rotate's matrix as doubles (the 16.16 fixed point is NEAREST's); rotated = 0: angle % 360 == 0, the window is cut from the frame itself
+struct RotAff {
+    double m[6];
+    int32_t rotated, pad;
+};
+
+__device__ __forceinline__ FiltEnt filter_coord(double s, int lim) {
+    FiltEnt e;
+    e.pad = 0;
+    if (!(s >= 0.0 && s < (double)lim)) {       // (a NaN coordinate is outside too: nothing below may turn it into an index)
+        e.i = kFiltOutside;
+        e.d = 0.0;
+        return e;
+    }
+    s = d_sub(s, 0.5);
+    e.i = s < 0.0 ? (int)floor(s) : (int)s;      // Geometry.c FLOOR()
+    e.d = d_sub(s, (double)e.i);
+    return e;
+}
+
+// a0 xin + a1 yin + a2 with a = ((x1 - x0) / w, 0, x0, 0, (y1 - y0) / h, y0): the zero product adds nothing to the sum
+__device__ __forceinline__ FiltEnt filter_entry(const double* __restrict__ box, int e, int w, int h, int fw, int fh) {
+    const int axis = e >= w ? 1 : 0, i = axis ? e - w : e;
+    const double lo = box[axis], hi = box[2 + axis];
+    const double a = d_div(d_sub(hi, lo), (double)(axis ? h : w));
+    return filter_coord(d_add(d_mul(a, d_add((double)i, 0.5)), lo), axis ? fh : fw);
+}
+
+__global__ void k_filter_tables(const double* __restrict__ boxes, int64_t n, int w, int h, int fw, int fh, FiltEnt* __restrict__ tabs,
+                                const double* __restrict__ angs, RotAff* __restrict__ rot) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wh = w + h;
+    if (id >= n * wh) return;
+    const int64_t b = id / wh;
+    const int e = (int)(id - b * wh);
+    tabs[b * wh + e] = filter_entry(boxes + b * 4, e, w, h, fw, fh);
+    if (angs && e == 0) {
+        RotAff ra{};
+        ra.rotated = rot_matrix(boxes, angs, b, ra.m) ? 1 : 0;
+        rot[b] = ra;
+    }
+}
+
+__device__ __forceinline__ double bicubic(double v1, double v2, double v3, double v4, double d) {      // Geometry.c BICUBIC(), a = -0.5
+    const double p1 = v2;
+    const double p2 = d_add(-v1, v3);
+    const double p3 = d_sub(d_add(d_mul(2.0, d_sub(v1, v2)), v3), v4);
+    const double p4 = d_add(d_sub(d_add(-v1, v2), v3), v4);
+    return d_add(p1, d_mul(d, d_add(p2, d_mul(d, d_add(p3, d_mul(d, p4))))));
+}
+
+// One filtered, quantised pixel at (x + dx, y + dy) of a W x H uint8 image whose pixels come from tap(column, row); every
+// coordinate handed to tap lies inside the image.
+template <int F, typename Tap>
+__device__ __forceinline__ uint8_t filter_sample(Tap&& tap, int x, double dx, int y, double dy, int W, int H) {
+    auto clipx = [&](int v) { return v < 0 ? 0 : v < W ? v : W - 1; };
+    if constexpr (F == HG_FILTER_BILINEAR) {
+        const int x0 = clipx(x), x1 = clipx(x + 1);
+        auto row = [&](int yy) {
+            const double p0 = tap(x0, yy), p1 = tap(x1, yy);
+            return d_add(p0, d_mul(d_sub(p1, p0), dx));
+        };
+        const double v1 = row(y < 0 ? 0 : y);
+        const double v2 = y + 1 < H ? row(y + 1) : v1;
+        return (uint8_t)(int)d_add(v1, d_mul(d_sub(v2, v1), dy));
+    } else {
+        const int x0 = clipx(x - 1), x1 = clipx(x), x2 = clipx(x + 1), x3 = clipx(x + 2);
+        auto row = [&](int yy) { return bicubic(tap(x0, yy), tap(x1, yy), tap(x2, yy), tap(x3, yy), dx); };
+        const double r1 = row(y - 1 < 0 ? 0 : y - 1);
+        const double r2 = y >= 0 ? row(y) : r1;          // (y <= H - 1 always)
+        const double r3 = y + 1 < H ? row(y + 1) : r2;
+        const double r4 = y + 2 < H ? row(y + 2) : r3;
+        const double v = bicubic(r1, r2, r3, r4, dy);
+        return v <= 0.0 ? (uint8_t)0 : v >= 255.0 ? (uint8_t)255 : (uint8_t)(int)v;
+    }
+}
+
+// Pixel (xr, yr) of frame.rotate(angle, F, center): affine_transform with the rotation's matrix, then the filter on the frame
+template <int F>
+__device__ __forceinline__ uint8_t rot_pixel(const uint8_t* __restrict__ frame, int64_t ld, int W, int H, const double* m, int xr, int yr) {
+    const double xin = d_add((double)xr, 0.5), yin = d_add((double)yr, 0.5);
+    const FiltEnt ex = filter_coord(d_add(d_add(d_mul(m[0], xin), d_mul(m[1], yin)), m[2]), W);
+    const FiltEnt ey = filter_coord(d_add(d_add(d_mul(m[3], xin), d_mul(m[4], yin)), m[5]), H);
+    if (ex.i == kFiltOutside || ey.i == kFiltOutside) return 0;
+    return filter_sample<F>([&](int xc, int yc) { return (double)frame[(int64_t)yc * ld + xc]; }, ex.i, ex.d, ey.i, ey.d, W, H);
+}
+
+// Unrotated windows: a workgroup per (group of output rows, box), a thread per output pixel
+template <int F, typename OT>
+__global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict__ frame, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+                                                        int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo) {
+    const int y = blockIdx.x * blockDim.y + threadIdx.y;
+    if (y >= h) return;
+    for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
+        const FiltEnt* t = tabs + b * (w + h);
+        const FiltEnt ey = t[w + y];
+        OT* dst = out + b * ldo + (int64_t)y * w;
+        for (int x = threadIdx.x; x < w; x += blockDim.x) {
+            const FiltEnt ex = t[x];
+            uint8_t v = 0;
+            if (ex.i != kFiltOutside && ey.i != kFiltOutside)
+                v = filter_sample<F>([&](int xc, int yc) { return (double)frame[(int64_t)yc * ld + xc]; }, ex.i, ex.d, ey.i, ey.d, fw, fh);
+            dst[x] = (OT)v;
+        }
+    }
+}
+
+// Rotated windows: frame.rotate(angle, F, center).transform((w, h), EXTENT, box, F).  Each tap of the second step is a pixel of the
+// rotated frame, itself 2 x 2 / 4 x 4 source reads and a quantisation: composed naively, 16 / 256 source reads per output pixel.  A
+// workgroup takes a 16 x 16 tile of output pixels; the taps of the tile cover a rectangle of the rotated frame (from the tile's
+// table entries), and when that rectangle is small enough it is computed ONCE into LDS as uint8 and the tile filters from there.  A
+// tile of a window shrunk so much that its taps are sparse in the rectangle computes each tap where it is used instead.  Both paths
+// give the same bytes (rot_pixel either way).  The limit is counted in the tile's own taps taken one by one (256 x 4 or 256 x 16
+// rotated pixels) and was settled by measurement (profiles/r08_filter_times.txt, 300 windows of 128 x 128 at 17 degrees):
+//   BILINEAR stages a rectangle of at most 1 x its taps (1024 pixels: windows shrunk up to 1.9 x).  Staging up to 2 x was slower:
+//     windows cut from 320 pixels (41 x 41 per tile) 0.121 ms staged against 0.098 ms tap by tap.
+//   BICUBIC stages up to 2 x its taps (8192 pixels, kFiltPatch bytes: windows shrunk up to 5.4 x).  A 128-pixel window cut from 576
+//     pixels of a 1000-pixel frame (75 x 75 per tile, 5625 rotated pixels against the 4096 of the taps) took 1.100 ms staged against
+//     1.237 ms tap by tap, although it computes more rotated pixels: tap by tap, sixteen threads compute the same rotated pixel
+//     at the same time and every one of them reads the frame from L2, where the staged tile reads LDS.
+constexpr int kFiltTile = 16, kFiltPatch = 256 * 16 * 2;
+template <int F, typename OT>
+__global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __restrict__ frame, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+                                                            const RotAff* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo,
+                                                            int tiles_x) {
+    constexpr int LO = F == HG_FILTER_BICUBIC ? 1 : 0, HI = F == HG_FILTER_BICUBIC ? 2 : 1, TAPS = (LO + HI + 1) * (LO + HI + 1);
+    constexpr int kStageLimit = TAPS * kFiltTile * kFiltTile * (F == HG_FILTER_BICUBIC ? 2 : 1);      // rotated pixels; see above
+    static_assert(kStageLimit <= kFiltPatch, "the staged rectangle must fit the LDS patch");
+    __shared__ uint8_t patch[kFiltPatch];
+    __shared__ int rng[4];
+    const int tx = threadIdx.x & (kFiltTile - 1), ty = threadIdx.x / kFiltTile;
+    const int ox = (int)(blockIdx.x % tiles_x) * kFiltTile + tx, oy = (int)(blockIdx.x / tiles_x) * kFiltTile + ty;
+    const bool live = ox < w && oy < h;
+    auto clip = [](int v, int lim) { return v < 0 ? 0 : v < lim ? v : lim - 1; };
+    auto frame_tap = [&](int xc, int yc) { return (double)frame[(int64_t)yc * ld + xc]; };
+    for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {      // (every thread of the workgroup takes every trip: barriers below)
+        const FiltEnt* t = tabs + b * (w + h);
+        FiltEnt ex, ey;
+        ex.i = ey.i = kFiltOutside;
+        ex.d = ey.d = 0.0;
+        if (live) {
+            ex = t[ox];
+            ey = t[w + oy];
+        }
+        const bool inside = ex.i != kFiltOutside && ey.i != kFiltOutside;
+        const RotAff ra = rot[b];
+        uint8_t v = 0;
+        if (!ra.rotated) {
+            if (inside) v = filter_sample<F>(frame_tap, ex.i, ex.d, ey.i, ey.d, fw, fh);
+        } else {
+            __syncthreads();      // the previous box's reads of patch / rng are done
+            if (threadIdx.x == 0) {
+                rng[0] = rng[2] = INT32_MAX;
+                rng[1] = rng[3] = INT32_MIN;
+            }
+            __syncthreads();
+            // the tile's first row holds all its columns and its first column all its rows (both exist: the tile does)
+            if (ty == 0 && ex.i != kFiltOutside) {
+                atomicMin(&rng[0], clip(ex.i - LO, fw));
+                atomicMax(&rng[1], clip(ex.i + HI, fw));
+            }
+            if (tx == 0 && ey.i != kFiltOutside) {
+                atomicMin(&rng[2], clip(ey.i - LO, fh));
+                atomicMax(&rng[3], clip(ey.i + HI, fh));
+            }
+            __syncthreads();
+            const int xlo = rng[0], xhi = rng[1], ylo = rng[2], yhi = rng[3];
+            // (an axis none of whose entries is inside the frame leaves its range at INT32_MAX / INT32_MIN: tested before any difference is taken)
+            const bool any = xhi >= xlo && yhi >= ylo;
+            const int pw = any ? xhi - xlo + 1 : 0, ph = any ? yhi - ylo + 1 : 0;
+            const bool staged = any && (int64_t)pw * ph <= kStageLimit;
+            if (staged) {
+                const int np = pw * ph;      // <= kFiltPatch
+                for (int idx = threadIdx.x; idx < np; idx += blockDim.x) {
+                    const int py = idx / pw, px = idx - py * pw;
+                    patch[idx] = rot_pixel<F>(frame, ld, fw, fh, ra.m, xlo + px, ylo + py);
+                }
+                __syncthreads();
+                if (inside) v = filter_sample<F>([&](int xc, int yc) { return (double)patch[(yc - ylo) * pw + (xc - xlo)]; }, ex.i, ex.d, ey.i, ey.d, fw, fh);
+            } else if (inside) {
+                v = filter_sample<F>([&](int xc, int yc) { return (double)rot_pixel<F>(frame, ld, fw, fh, ra.m, xc, yc); }, ex.i, ex.d, ey.i, ey.d, fw, fh);
+            }
+        }
+        if (live) out[b * ldo + (int64_t)oy * w + ox] = (OT)v;
+    }
+}
+
 // (Round 4 also measured tables + coefficients + gather as ONE launch, a workgroup per box building its tables and coefficients in
 // LDS: 48.6 us against 38.5 for the first stage's 1738 windows and 25 against 21 for a few hundred — one thread's double-precision
 // fmod / cos / sin and the dependent additions of the tables sit on every workgroup's critical path instead of being spread over
@@ -443,6 +657,30 @@ void launch_gather_rot(const void* frame, int64_t ld, int fw, int fh, const int3
     }
 }
 
+template <int F>
+void launch_filter(const uint8_t* frame, int64_t ld, int fw, int fh, const FiltEnt* tabs, const RotAff* rot, int64_t n, int w, int h, void* out, int out_dtype,
+                   int64_t ldo, hipStream_t st) {
+    const unsigned ny = (unsigned)std::min<int64_t>(n, 65535);
+    if (rot) {
+        const int tiles_x = (w + kFiltTile - 1) / kFiltTile, tiles_y = (h + kFiltTile - 1) / kFiltTile;      // <= 256 each (check_args)
+        const dim3 grid((unsigned)(tiles_x * tiles_y), ny);
+        switch (out_dtype) {
+            case HG_U8: hipLaunchKernelGGL((k_filter_gather_rot<F, uint8_t>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (uint8_t*)out, ldo, tiles_x); break;
+            case HG_F32: hipLaunchKernelGGL((k_filter_gather_rot<F, float>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (float*)out, ldo, tiles_x); break;
+            default: hipLaunchKernelGGL((k_filter_gather_rot<F, double>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (double*)out, ldo, tiles_x); break;
+        }
+        return;
+    }
+    const unsigned tx = w >= 256 ? 256 : w >= 128 ? 128 : w >= 64 ? 64 : 32;
+    const dim3 thr(tx, 256 / tx);
+    const dim3 grid((unsigned)((h + thr.y - 1) / thr.y), ny);
+    switch (out_dtype) {
+        case HG_U8: hipLaunchKernelGGL((k_filter_gather<F, uint8_t>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (uint8_t*)out, ldo); break;
+        case HG_F32: hipLaunchKernelGGL((k_filter_gather<F, float>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (float*)out, ldo); break;
+        default: hipLaunchKernelGGL((k_filter_gather<F, double>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (double*)out, ldo); break;
+    }
+}
+
 void check_args(const hg_patcher* p, const void* frame, int frame_dtype, int fh, int fw, int64_t ld, const double* boxes, int64_t n,
                 int w, int h, const void* out, int out_dtype, int64_t ldo) {
     if (!p) hg::fail(HG_ERR_ARG, "null patcher handle");
@@ -452,6 +690,12 @@ void check_args(const hg_patcher* p, const void* frame, int frame_dtype, int fh,
     if (w <= 0 || h <= 0 || w > 4096 || h > 4096) hg::fail(HG_ERR_ARG, "bad sub-image size");
     if (n < 0 || ldo < (int64_t)w * h) hg::fail(HG_ERR_ARG, "bad batch geometry");
     if (n > 0 && (!frame || !boxes || !out)) hg::fail(HG_ERR_ARG, "null data pointer");
+}
+
+void check_filter(int filter, int frame_dtype) {
+    if (filter != HG_FILTER_NEAREST && filter != HG_FILTER_BILINEAR && filter != HG_FILTER_BICUBIC)
+        hg::fail(HG_ERR_ARG, "unknown interpolation filter %d (0 NEAREST, 2 BILINEAR, 3 BICUBIC)", filter);
+    if (filter != HG_FILTER_NEAREST && frame_dtype != HG_U8) hg::fail(HG_ERR_ARG, "BILINEAR / BICUBIC windows need an HG_U8 frame");
 }
 
 }  // namespace
@@ -522,13 +766,13 @@ int hg_patcher_extract_keyed_device(hg_patcher* p, uint64_t key, const void* fra
         if ((n_ent + 255) / 256 > 0x7fffffffll) hg::fail(HG_ERR_ARG, "too many boxes");
         hg_patcher::Keyed* K = nullptr;
         for (auto& k : p->keyed)
-            if (k.key == key && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
+            if (k.key == key && !k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
         if (!K) {      // first use of this key (or its shape changed): build the tables, in stream order, into a buffer of their own
             K = &p->keyed[p->keyed_next];
             p->keyed_next = (p->keyed_next + 1) % 4;
             if (K->tabs.p && (size_t)n_ent * 4 > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
             K->tabs.alloc((size_t)n_ent * 4);
-            K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h;
+            K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 0;
             hipLaunchKernelGGL(k_extent_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (int32_t*)K->tabs.p,
                                (const double*)nullptr, (RotCoef*)nullptr);
         }
@@ -545,9 +789,17 @@ int hg_patcher_extract_device(hg_patcher* p, const void* frame_dev, int frame_dt
                                             ldo, stream);
 }
 
-int hg_patcher_extract_rotate(hg_patcher* p, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld, const double* boxes,
+int hg_patcher_extract_filter_device(hg_patcher* p, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w, int64_t ld,
+                                     const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype,
+                                     int64_t ldo, void* stream) {
+    return hg::patcher_extract(p, 0, filter, frame_dev, frame_dtype, frame_h, frame_w, ld, boxes_dev, delta_angs_dev, n, out_w, out_h, out_dev, out_dtype, ldo,
+                               stream);
+}
+
+int hg_patcher_extract_filter(hg_patcher* p, int filter, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld, const double* boxes,
                               const double* delta_angs, int64_t n, int out_w, int out_h, void* out, int out_dtype, int64_t ldo) {
     return guarded([&] {
+        check_filter(filter, frame_dtype);
         check_args(p, frame, frame_dtype, frame_h, frame_w, ld, boxes, n, out_w, out_h, out, out_dtype, ldo);
         if (n == 0) return;
         HG_HIP(hipSetDevice(p->device));
@@ -558,12 +810,16 @@ int hg_patcher_extract_rotate(hg_patcher* p, const void* frame, int frame_dtype,
         if (delta_angs) p->angles.upload(delta_angs, (size_t)n * 8);
         const size_t row = (size_t)out_w * out_h;
         p->out.alloc((size_t)n * row * os);
-        int rc = hg_patcher_extract_rotate_device(p, p->frame.p, frame_dtype, frame_h, frame_w, frame_w, (const double*)p->boxes.p,
-                                                  delta_angs ? (const double*)p->angles.p : nullptr, n, out_w, out_h, p->out.p, out_dtype,
-                                                  (int64_t)row, nullptr);
+        int rc = hg::patcher_extract(p, 0, filter, p->frame.p, frame_dtype, frame_h, frame_w, frame_w, (const double*)p->boxes.p,
+                                     delta_angs ? (const double*)p->angles.p : nullptr, n, out_w, out_h, p->out.p, out_dtype, (int64_t)row, nullptr);
         if (rc != HG_OK) hg::fail(rc, "%s", hg_last_error());
         HG_HIP(hipMemcpy2D(out, (size_t)ldo * os, p->out.p, row * os, row * os, (size_t)n, hipMemcpyDeviceToHost));
     });
+}
+
+int hg_patcher_extract_rotate(hg_patcher* p, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld, const double* boxes,
+                              const double* delta_angs, int64_t n, int out_w, int out_h, void* out, int out_dtype, int64_t ldo) {
+    return hg_patcher_extract_filter(p, HG_FILTER_NEAREST, frame, frame_dtype, frame_h, frame_w, ld, boxes, delta_angs, n, out_w, out_h, out, out_dtype, ldo);
 }
 
 int hg_patcher_extract(hg_patcher* p, const void* frame, int frame_dtype, int frame_h, int frame_w, int64_t ld, const double* boxes,
@@ -572,3 +828,55 @@ int hg_patcher_extract(hg_patcher* p, const void* frame, int frame_dtype, int fr
 }
 
 }  // extern "C"
+
+namespace hg {
+// The single dispatch (hg_common.hpp): every C entry of this file that takes a filter, and the cascade's stage loop, come through here.
+// NEAREST goes to the entries it always went to; BILINEAR and BICUBIC share a coordinate table (it holds coordinates, not taps), kept
+// per key under the contract of hg_patcher_extract_keyed_device (key != 0: unrotated boxes the caller declares unchanged).
+int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w, int64_t ld,
+                    const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo,
+                    void* stream) {
+    if (filter == HG_FILTER_NEAREST)
+        return key && !delta_angs_dev
+                   ? hg_patcher_extract_keyed_device(p, key, frame_dev, frame_dtype, frame_h, frame_w, ld, boxes_dev, n, out_w, out_h, out_dev, out_dtype, ldo, stream)
+                   : hg_patcher_extract_rotate_device(p, frame_dev, frame_dtype, frame_h, frame_w, ld, boxes_dev, delta_angs_dev, n, out_w, out_h, out_dev, out_dtype,
+                                                      ldo, stream);
+    return guarded([&] {
+        check_filter(filter, frame_dtype);
+        check_args(p, frame_dev, frame_dtype, frame_h, frame_w, ld, boxes_dev, n, out_w, out_h, out_dev, out_dtype, ldo);
+        if (n == 0) return;
+        HG_HIP(hipSetDevice(p->device));
+        hipStream_t st = (hipStream_t)stream;
+        const int64_t n_ent = n * (out_w + out_h);
+        if ((n_ent + 255) / 256 > 0x7fffffffll) fail(HG_ERR_ARG, "too many boxes");
+        const FiltEnt* tabs = nullptr;
+        if (key && !delta_angs_dev) {
+            hg_patcher::Keyed* K = nullptr;
+            for (auto& k : p->keyed)
+                if (k.key == key && k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
+            if (!K) {
+                K = &p->keyed[p->keyed_next];
+                p->keyed_next = (p->keyed_next + 1) % 4;
+                if (K->tabs.p && (size_t)n_ent * sizeof(FiltEnt) > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
+                K->tabs.alloc((size_t)n_ent * sizeof(FiltEnt));
+                K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 1;
+                hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)K->tabs.p,
+                                   (const double*)nullptr, (RotAff*)nullptr);
+            }
+            tabs = (const FiltEnt*)K->tabs.p;
+        } else {
+            p->ftabs.alloc((size_t)n_ent * sizeof(FiltEnt));
+            if (delta_angs_dev) p->frot.alloc((size_t)n * sizeof(RotAff));
+            hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)p->ftabs.p,
+                               delta_angs_dev, delta_angs_dev ? (RotAff*)p->frot.p : nullptr);
+            tabs = (const FiltEnt*)p->ftabs.p;
+        }
+        const RotAff* rot = delta_angs_dev ? (const RotAff*)p->frot.p : nullptr;
+        if (filter == HG_FILTER_BILINEAR)
+            launch_filter<HG_FILTER_BILINEAR>((const uint8_t*)frame_dev, ld, frame_w, frame_h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+        else
+            launch_filter<HG_FILTER_BICUBIC>((const uint8_t*)frame_dev, ld, frame_w, frame_h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+        HG_HIP(hipGetLastError());
+    });
+}
+}  // namespace hg

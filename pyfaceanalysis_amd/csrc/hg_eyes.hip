@@ -35,6 +35,7 @@ struct hg_eyes {
     hg_gauss *gx = nullptr, *gy = nullptr;
     hg_eye_consts c{};
     hg_patcher* patcher = nullptr;
+    int filter = HG_FILTER_NEAREST;      // of the eye patches (hg_eyes_set_interpolation)
     int64_t cap = 0;       // faces the buffers hold
     hg::DevBuf eboxes, dang, pu8, pf32, sl, sl2, reg, ecoords, toofar, rows, purged, scratch, count;
     int32_t* host_words = nullptr;       // pinned: {faces after the discard, faces after the purge}
@@ -362,7 +363,7 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
     const int64_t wh = (int64_t)c.eye_w * c.eye_h, n2 = 2 * n;
     hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, n_dev, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
     HG_HIP(hipGetLastError());
-    if (hg_patcher_extract_rotate_device(e->patcher, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p, (const double*)e->dang.p, n2,
+    if (hg_patcher_extract_filter_device(e->patcher, e->filter, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p, (const double*)e->dang.p, n2,
                                          c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st) != HG_OK)
         hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
     float* pf = patches ? patches : (float*)e->pf32.p;
@@ -476,6 +477,15 @@ int hg_eyes_create(hg_flow* flow_x, hg_gauss* clf_x, hg_flow* flow_y, hg_gauss* 
         if (hg_patcher_create(device, &e->patcher) != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         HG_HIP(hipHostMalloc((void**)&e->host_words, 64, hipHostMallocDefault));
         *out = e.release();
+    });
+}
+
+int hg_eyes_set_interpolation(hg_eyes* e, int filter) {
+    return guarded([&] {
+        if (!e) hg::fail(HG_ERR_ARG, "null eye handle");
+        if (filter != HG_FILTER_NEAREST && filter != HG_FILTER_BILINEAR && filter != HG_FILTER_BICUBIC)
+            hg::fail(HG_ERR_ARG, "unknown interpolation filter %d (0 NEAREST, 2 BILINEAR, 3 BICUBIC)", filter);
+        e->filter = filter;
     });
 }
 

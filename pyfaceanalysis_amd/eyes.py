@@ -28,8 +28,11 @@ TOLERANCE_XY_EYE = 9.0         # face_analysis.py:1018
 
 class EyeLocator(object):
     def __init__(self, flow_x, clf_x, flow_y, clf_y, *, contrast, eye_size=(64, 64), regression_size=(64, 64), tolerance=TOLERANCE_XY_EYE,
-                 n_features=None, device=0):
+                 n_features=None, device=0, interpolation=0):
+        """interpolation: the filter of the eye patches (PIL's codes 0 / 2 / 3) — the reference passes what its stage loop's last
+        iteration left in interpolation_format (FaceDetectUpdated.py:671, :994)."""
         import torch
+        self.interpolation = _capi.filter_code(interpolation)
         self.torch = torch
         self.flow_x, self.clf_x, self.flow_y, self.clf_y = flow_x, clf_x, flow_y, clf_y
         self.contrast = (float(contrast[0]), float(contrast[1]))
@@ -68,6 +71,8 @@ class EyeLocator(object):
             _capi.check(_capi.lib().hg_eyes_create(self.flow_x._handle().h, self.clf_x._handle(self.clf_x.avg_labels), self.flow_y._handle().h,
                                                    self.clf_y._handle(self.clf_y.avg_labels), C.byref(cc), self.device, C.byref(h)))
             self._h = h
+            if self.interpolation != _capi.HG_FILTER_NEAREST:
+                _capi.check(_capi.lib().hg_eyes_set_interpolation(h, self.interpolation))
         return self._h
 
     def _faces(self, boxes, angles):

@@ -5,8 +5,10 @@
 
 same pixels as ``PIL.Image.transform((w, h), EXTENT, box, NEAREST)`` — of the frame itself, or for a window with
 a non-zero ``delta_ang`` of ``frame.rotate(delta_ang, NEAREST, center=box centre)`` (the composition rule is the
-build's: hg_extract.hip header) — returned as the (N, w*h) row-major matrix ``flow.execute`` takes.  No CPU path:
-needs the HIP library and a GPU.
+build's: hg_extract.hip header) — returned as the (N, w*h) row-major matrix ``flow.execute`` takes.  ``interpolation``
+chooses the filter the reference chooses per stage (``interpolation_formats``, FaceDetectUpdated.py:125): PIL's codes 0 NEAREST,
+2 BILINEAR, 3 BICUBIC, the same pixels as PIL with that filter in ``transform`` and, for a rotated window, in ``rotate`` too;
+BILINEAR / BICUBIC read uint8 frames only.  No CPU path: needs the HIP library and a GPU.
 """
 from __future__ import annotations
 
@@ -29,12 +31,16 @@ class Patcher(object):
             self._h = h
         return self._h
 
-    def extract(self, frame, boxes, out_size, dtype=np.float64, delta_angs=None):
+    def extract(self, frame, boxes, out_size, dtype=np.float64, delta_angs=None, interpolation=0):
         """frame: (H, W) uint8 or float32; boxes: (N, 4) (x0, y0, x1, y1); out_size: (w, h); delta_angs: (N,) degrees,
-        what the reference passes as ``-1 * curr_angles`` (face_analysis.py:782)."""
+        what the reference passes as ``-1 * curr_angles`` (face_analysis.py:782); interpolation: 0 / 2 / 3 (uint8 frames only
+        unless 0)."""
+        filt = _capi.filter_code(interpolation)
         frame = np.asarray(frame)
         if frame.ndim != 2:
             raise ValueError("frame must be a 2-d (H, W) array")
+        if filt != _capi.HG_FILTER_NEAREST and frame.dtype != np.uint8:
+            raise ValueError("BILINEAR / BICUBIC windows need a uint8 frame")
         if frame.dtype not in (np.uint8, np.float32):
             frame = frame.astype(np.float32)
         frame = np.ascontiguousarray(frame)
@@ -51,18 +57,21 @@ class Patcher(object):
         if code is None:
             raise ValueError("dtype must be uint8, float32 or float64")
         if n:
-            _capi.check(_capi.lib().hg_patcher_extract_rotate(
-                self._handle(), frame.ctypes.data_as(C.c_void_p), _capi.np_dtype_code(frame.dtype), frame.shape[0], frame.shape[1],
+            _capi.check(_capi.lib().hg_patcher_extract_filter(
+                self._handle(), filt, frame.ctypes.data_as(C.c_void_p), _capi.np_dtype_code(frame.dtype), frame.shape[0], frame.shape[1],
                 frame.shape[1], boxes.ctypes.data_as(C.c_void_p), None if angs is None else angs.ctypes.data_as(C.c_void_p), n, w, h,
                 out.ctypes.data_as(C.c_void_p), code, w * h))
         return out
 
     def extract_device(self, frame_ptr, frame_dtype, frame_h, frame_w, ld, boxes_ptr, n, out_size, out_ptr, out_dtype, ldo, stream=0,
-                       delta_angs_ptr=None):
+                       delta_angs_ptr=None, interpolation=0):
         """Raw device pointers (ints); enqueued on ``stream``, no synchronisation."""
+        filt = _capi.filter_code(interpolation)
+        if filt != _capi.HG_FILTER_NEAREST and np.dtype(frame_dtype) != np.uint8:
+            raise ValueError("BILINEAR / BICUBIC windows need a uint8 frame")
         w, h = int(out_size[0]), int(out_size[1])
-        _capi.check(_capi.lib().hg_patcher_extract_rotate_device(
-            self._handle(), C.c_void_p(frame_ptr), _capi.np_dtype_code(frame_dtype), int(frame_h), int(frame_w), int(ld),
+        _capi.check(_capi.lib().hg_patcher_extract_filter_device(
+            self._handle(), filt, C.c_void_p(frame_ptr), _capi.np_dtype_code(frame_dtype), int(frame_h), int(frame_w), int(ld),
             C.c_void_p(boxes_ptr), C.c_void_p(delta_angs_ptr) if delta_angs_ptr else None, int(n), w, h, C.c_void_p(out_ptr),
             _capi.np_dtype_code(out_dtype), int(ldo), C.c_void_p(stream)))
 
