@@ -14,7 +14,8 @@
  * hg_last_error() returns a thread-local message for the last failure on the calling thread.
  *
  * Threading: one hg_flow may be used by one thread at a time; different flows are
- * independent.  The library keeps no global mutable state besides the last-error string.
+ * independent.  The library keeps no global mutable state besides the last-error string and the two lane streams per device
+ * (hg_lane_stream_id), which are created once under a lock and never changed.
  * There is NO CPU execution path: without a usable HIP device hg_flow_to_device /
  * hg_flow_execute* fail with HG_ERR_DEVICE.
  */
@@ -123,6 +124,36 @@ int hg_flow_execute_sharded(hg_flow* f, const void* x, int x_dtype, int64_t n, i
 int hg_flow_execute_device(hg_flow* f, const void* x_dev, int x_dtype, int64_t n, int64_t ldx,
                            void* y_dev, int y_dtype, int64_t y_cols, int64_t ldy, void* stream);
 
+/* --- Step lanes: two steps in flight through ONE flow handle -----------------------------------------------
+ * A step's eight launches ramp up and tail off; two independent batches that share the chip fill each other's ramps.  A lane is
+ * one copy of everything a call WRITES (activation workspace, tile-queue counters, error word) over the handle's one copy of
+ * what it only reads (weights, tables, plans), plus a stream of its own.  hg_flow_set_lanes(f, n), n = 1 or 2, after
+ * hg_flow_to_device: HG_ERR_STATE (and the handle stays serial) where the plan keeps one set of state — the generic plan does.
+ * It first waits for whatever the handle has in flight on a lane.  hg_flow_reserve sizes every lane; workspace_bytes in hg_info is
+ * their sum.  The two lane streams exist once per device and process and are shared by all flows on the device (which hardware
+ * queue a stream lands on depends on how many the process created before it); hg_lane_stream_id returns the stream of (device,
+ * lane) as an integer (it is a hipStream_t), creating the pair on first use.
+ *
+ * hg_flow_step_lane_device(f, lane, x, ..., y, ..., ready_stream): records the lane's "ready" event on ready_stream and makes the
+ * lane's stream wait for it — so everything enqueued on ready_stream so far (the producer of x, the last reader of y) precedes the
+ * step — then enqueues exactly the launches of hg_flow_execute_device on the lane's stream with the lane's state, then records the
+ * lane's "done" event there.  Returns without synchronising; the features are NOT ordered on ready_stream: wait for the done event
+ * (hg_flow_lane_done_event: a hipEvent_t owned by the handle, device scope like hg_event_create's, re-recorded by the lane's next
+ * step) or call hg_flow_lane_join(f, lane, stream), which makes `stream` wait for the lane's last step (a no-op before the first).
+ * A lane whose workspace must grow first waits for its own last step (and freeing the old buffers drains the device).  Never profiled.
+ * hg_flow_execute_device keeps its contract — lane 0's state, the caller's stream, strictly ordered there; it waits for a lane-0
+ * step that is still in flight.  A lane-0 step that follows it is ordered behind it only through ready_stream.
+ * hg_flow_check_errors reads every lane's error word (meaningful after a synchronisation); hg_flow_free first waits for every
+ * lane.  One thread per handle, as for every other call. */
+int hg_flow_set_lanes(hg_flow* f, int n);
+int hg_flow_lanes(const hg_flow* f, int* n);
+int hg_flow_step_lane_device(hg_flow* f, int lane, const void* x_dev, int x_dtype, int64_t n, int64_t ldx,
+                             void* y_dev, int y_dtype, int64_t y_cols, int64_t ldy, void* ready_stream);
+int hg_flow_lane_done_event(hg_flow* f, int lane, void** ev);
+int hg_flow_lane_join(hg_flow* f, int lane, void* stream);
+int hg_flow_check_errors(hg_flow* f);
+int hg_lane_stream_id(int device, int lane, uint64_t* id);
+
 /* Device-scope events for callers that overlap a collective with the next batch (pyfaceanalysis_amd/sharded.py: the RCCL
  * all-gather of the features on a side stream, ordered against the kernels in both directions).  Created with
  * hipEventDisableTiming | hipEventDisableSystemFence: recording one does not write the caches back to system scope the way
@@ -141,6 +172,9 @@ int hg_stream_wait_event(void* stream, void* ev);
 /* 1 when everything the event was last recorded behind has completed, 0 when not yet (never blocks); < 0: hg_status.
  * Lets the host skip a wait that would only put a barrier packet in front of the next launch (measured: 4.5 us). */
 int hg_event_query(void* ev);
+/* Blocks the calling thread until everything the event was last recorded behind has completed (the host learns THAT the work is
+ * done; what it then reads goes through a copy or a kernel of its own, as after any device-scope event). */
+int hg_event_synchronize(void* ev);
 
 /* How the last hg_flow_execute of this handle moved the caller's rows (FaceDetectUpdated.py:699 hands over a host ndarray,
  * face_analysis.py:786): *transport = 1 — packer threads stored the wire rows straight into device memory, which is done only

@@ -15,8 +15,10 @@ HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC = 0, 2, 3      # enum h
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below)
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters and the step lanes
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
+_ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
+                        "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
 _lib = None
 
 
@@ -91,12 +93,20 @@ def lib():
         "hg_flow_execute": (C.c_int, [vp, vp, i32, i64, i64, vp, i32, i64, i64]),
         "hg_flow_execute_sharded": (C.c_int, [vp, vp, i32, i64, i64, vp, i32, i64, i64, C.POINTER(C.c_int), i32]),
         "hg_flow_execute_device": (C.c_int, [vp, vp, i32, i64, i64, vp, i32, i64, i64, vp]),
+        "hg_flow_set_lanes": (C.c_int, [vp, i32]),
+        "hg_flow_lanes": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "hg_flow_step_lane_device": (C.c_int, [vp, i32, vp, i32, i64, i64, vp, i32, i64, i64, vp]),
+        "hg_flow_lane_done_event": (C.c_int, [vp, i32, C.POINTER(vp)]),
+        "hg_flow_lane_join": (C.c_int, [vp, i32, vp]),
+        "hg_flow_check_errors": (C.c_int, [vp]),
+        "hg_lane_stream_id": (C.c_int, [i32, i32, C.POINTER(C.c_uint64)]),
         "hg_event_create": (C.c_int, [C.POINTER(vp)]),
         "hg_event_create_on": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
         "hg_event_destroy": (None, [vp]),
         "hg_event_record": (C.c_int, [vp, vp]),
         "hg_stream_wait_event": (C.c_int, [vp, vp]),
         "hg_event_query": (C.c_int, [vp]),
+        "hg_event_synchronize": (C.c_int, [vp]),
         "hg_flow_host_transport": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "hg_host_pack_probe": (C.c_int, [vp, i32, i64, i64, i64, i32, C.POINTER(C.c_double)]),
         "hg_host_store_probe": (C.c_int, [i32, sz, i32, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
@@ -153,7 +163,7 @@ def lib():
         except AttributeError:
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
-            if name in _ENTRIES_SINCE_FILTERS and os.environ.get("HIGSFA_LIB"):
+            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -175,6 +185,8 @@ EXPORTED_SYMBOLS = (
     "hg_eyes_create", "hg_eyes_free", "hg_eyes_locate_device", "hg_eyes_boxes_device", "hg_purge_detections_device", "hg_cascade_detect_faces_frame_device",
     "hg_cascade_tracked_grid_device", "hg_tracker_create", "hg_tracker_free", "hg_tracker_reset", "hg_tracker_step_frame_device",
     "hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation",
+    "hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join", "hg_flow_check_errors",
+    "hg_lane_stream_id", "hg_event_synchronize",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

@@ -208,6 +208,34 @@ struct Replica {
     }
 };
 
+// Lane streams (hg_flow_step_lane_device): two per device and process, created on first use, shared by every flow on the
+// device and never destroyed.  Streams compete for the device's few hardware queues, and which queue a new stream lands on
+// depends on how many the process created before it (profiles/r04_rccl_world1.txt: the same hand-off costs 12-17 us inside
+// one queue and 35 across two) — so the choice is made once per process, not once per flow.
+constexpr int kLanes = 2;
+std::mutex g_lane_mu;
+struct LaneStreams {
+    hipStream_t s[kLanes] = {};
+};
+LaneStreams g_lane_streams[64];
+
+hipStream_t lane_stream(int device, int lane) {      // the calling thread's current device is `device`
+    if (device < 0 || device >= 64) hg::fail(HG_ERR_DEVICE, "device %d outside 0..63", device);
+    if (lane < 0 || lane >= kLanes) hg::fail(HG_ERR_ARG, "lane %d outside 0..%d", lane, kLanes - 1);
+    std::lock_guard<std::mutex> lock(g_lane_mu);
+    LaneStreams& ls = g_lane_streams[device];
+    if (!ls.s[0])
+        for (int l = 0; l < kLanes; ++l) HG_HIP(hipStreamCreateWithFlags(&ls.s[l], hipStreamNonBlocking));
+    return ls.s[lane];
+}
+
+// Per flow and lane: "x is ready and y may be rewritten" (recorded on the caller's stream, waited for by the lane's stream) and
+// "the lane's last step is done" (the other way).  Device scope: they order device work on one device, nothing the host reads.
+struct LaneCtl {
+    hipEvent_t ready = nullptr, done = nullptr;
+    bool stepped = false;      // `done` has been recorded at least once
+};
+
 }  // namespace
 
 struct hg_flow {
@@ -224,6 +252,23 @@ struct hg_flow {
                                          // queues even where the host could store into device memory
     std::vector<hipEvent_t> events;
     std::vector<hg::StageProfile> prof;
+    int n_lanes = 1;                     // hg_flow_set_lanes
+    LaneCtl lane[kLanes];
+
+    // nothing of this handle is left in flight on a lane stream (current device: the flow's)
+    void drain_lanes() {
+        if (n_lanes < 2 || device < 0) return;
+        for (int l = 0; l < n_lanes; ++l)
+            if (lane[l].stepped) (void)hipStreamSynchronize(lane_stream(device, l));
+    }
+    void drop_lanes() {
+        for (LaneCtl& c : lane) {
+            if (c.ready) (void)hipEventDestroy(c.ready);
+            if (c.done) (void)hipEventDestroy(c.done);
+            c = LaneCtl();
+        }
+        n_lanes = 1;
+    }
 
     void need_device() const {
         if (device < 0) hg::fail(HG_ERR_DEVICE, "flow is not on a device: call hg_flow_to_device first");
@@ -234,7 +279,14 @@ struct hg_flow {
         events.clear();
     }
     ~hg_flow() {
-        if (device >= 0 && hipSetDevice(device) == hipSuccess) drop_events();
+        if (device >= 0 && hipSetDevice(device) == hipSuccess) {
+            try {
+                drain_lanes();      // un-waited lane steps still read the weights and write the workspaces freed below
+            } catch (...) {
+            }
+            drop_lanes();
+            drop_events();
+        }
         main.destroy();
         for (auto& r : shards) r->destroy();
     }
@@ -679,6 +731,7 @@ int hg_flow_reserve(hg_flow* f, int64_t max_rows) {
         if (max_rows < 0) hg::fail(HG_ERR_ARG, "negative row count");
         f->need_device();
         f->set_device();
+        f->drain_lanes();      // a workspace that grows is freed first: no lane step may still be using it
         f->exec->reserve(max_rows);
     });
 }
@@ -689,7 +742,116 @@ int hg_flow_execute_device(hg_flow* f, const void* x, int x_dtype, int64_t n, in
         check_exec_args(f, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy);
         f->need_device();
         f->set_device();
+        // lane 0's state on the caller's stream: a lane-0 step the caller has not joined yet goes first
+        if (f->n_lanes > 1 && f->lane[0].stepped && hipEventQuery(f->lane[0].done) != hipSuccess) {
+            (void)hipGetLastError();
+            HG_HIP(hipStreamWaitEvent((hipStream_t)stream, f->lane[0].done, 0));
+        }
         run_on_device(f, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, (hipStream_t)stream);
+    });
+}
+
+int hg_flow_set_lanes(hg_flow* f, int n) {
+    return guarded([&] {
+        if (!f) hg::fail(HG_ERR_ARG, "null flow handle");
+        if (n < 1 || n > kLanes) hg::fail(HG_ERR_ARG, "lanes %d outside 1..%d", n, kLanes);
+        f->need_device();
+        f->set_device();
+        if (n == f->n_lanes) return;
+        f->drain_lanes();
+        if (!f->exec->set_lanes(n)) hg::fail(HG_ERR_STATE, "this flow's plan keeps one set of per-call state: it cannot run %d lanes", n);
+        if (n == 1) {
+            f->drop_lanes();
+            return;
+        }
+        try {
+            for (int l = 0; l < n; ++l) {
+                (void)lane_stream(f->device, l);
+                HG_HIP(hipEventCreateWithFlags(&f->lane[l].ready, hipEventDisableTiming | hipEventDisableSystemFence));
+                HG_HIP(hipEventCreateWithFlags(&f->lane[l].done, hipEventDisableTiming | hipEventDisableSystemFence));
+            }
+        } catch (...) {
+            f->drop_lanes();
+            (void)f->exec->set_lanes(1);
+            throw;
+        }
+        f->n_lanes = n;
+    });
+}
+
+int hg_flow_lanes(const hg_flow* f, int* n) {
+    return guarded([&] {
+        if (!f || !n) hg::fail(HG_ERR_ARG, "null argument");
+        *n = f->n_lanes;
+    });
+}
+
+int hg_flow_step_lane_device(hg_flow* f, int lane, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype,
+                             int64_t y_cols, int64_t ldy, void* ready_stream) {
+    return guarded([&] {
+        check_exec_args(f, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy);
+        f->need_device();
+        if (f->n_lanes < 2) hg::fail(HG_ERR_STATE, "flow has no lanes: call hg_flow_set_lanes first");
+        if (lane < 0 || lane >= f->n_lanes) hg::fail(HG_ERR_ARG, "lane %d outside 0..%d", lane, f->n_lanes - 1);
+        f->set_device();
+        LaneCtl& c = f->lane[lane];
+        const hipStream_t ls = lane_stream(f->device, lane);
+        HG_HIP(hipEventRecord(c.ready, (hipStream_t)ready_stream));
+        HG_HIP(hipStreamWaitEvent(ls, c.ready, 0));
+        try {
+            if (n > 0) f->exec->run_lane(lane, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, ls);
+        } catch (...) {      // whatever was launched before the failure still gets its "done"
+            if (hipEventRecord(c.done, ls) == hipSuccess) c.stepped = true;
+            throw;
+        }
+        HG_HIP(hipEventRecord(c.done, ls));
+        c.stepped = true;
+    });
+}
+
+int hg_flow_lane_done_event(hg_flow* f, int lane, void** ev) {
+    return guarded([&] {
+        if (!f || !ev) hg::fail(HG_ERR_ARG, "null argument");
+        if (f->n_lanes < 2 || lane < 0 || lane >= f->n_lanes) hg::fail(HG_ERR_ARG, "lane %d outside the flow's %d lane(s)", lane, f->n_lanes);
+        *ev = (void*)f->lane[lane].done;
+    });
+}
+
+int hg_flow_lane_join(hg_flow* f, int lane, void* stream) {
+    return guarded([&] {
+        if (!f) hg::fail(HG_ERR_ARG, "null flow handle");
+        if (f->n_lanes < 2 || lane < 0 || lane >= f->n_lanes) hg::fail(HG_ERR_ARG, "lane %d outside the flow's %d lane(s)", lane, f->n_lanes);
+        if (!f->lane[lane].stepped) return;      // no step yet: nothing to wait for
+        f->set_device();
+        HG_HIP(hipStreamWaitEvent((hipStream_t)stream, f->lane[lane].done, 0));
+    });
+}
+
+int hg_flow_check_errors(hg_flow* f) {
+    return guarded([&] {
+        if (!f) hg::fail(HG_ERR_ARG, "null flow handle");
+        f->exec->check_errors();
+    });
+}
+
+int hg_lane_stream_id(int device, int lane, uint64_t* id) {
+    return guarded([&] {
+        if (!id) hg::fail(HG_ERR_ARG, "null id pointer");
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) hg::fail(HG_ERR_DEVICE, "no HIP device available");
+        if (device < 0 || device >= count) hg::fail(HG_ERR_DEVICE, "device %d out of range (0..%d)", device, count - 1);
+        int cur = -1;
+        HG_HIP(hipGetDevice(&cur));
+        HG_HIP(hipSetDevice(device));      // a stream belongs to the device that is current when it is created
+        hipStream_t s = nullptr;
+        try {
+            s = lane_stream(device, lane);
+        } catch (...) {
+            if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+            throw;
+        }
+        if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+        *id = (uint64_t)(uintptr_t)s;
     });
 }
 
@@ -700,6 +862,7 @@ int hg_flow_execute(hg_flow* f, const void* x, int x_dtype, int64_t n, int64_t l
         f->need_device();
         f->set_device();
         if (n == 0) return;
+        f->drain_lanes();      // the host path runs on lane 0's state
         run_host_rows(f, f->main, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy);
     });
 }
@@ -820,6 +983,13 @@ int hg_stream_wait_event(void* stream, void* ev) {
     return guarded([&] {
         if (!ev) hg::fail(HG_ERR_ARG, "null event");
         HG_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0));
+    });
+}
+
+int hg_event_synchronize(void* ev) {
+    return guarded([&] {
+        if (!ev) hg::fail(HG_ERR_ARG, "null event");
+        HG_HIP(hipEventSynchronize((hipEvent_t)ev));
     });
 }
 

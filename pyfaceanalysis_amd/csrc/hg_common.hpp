@@ -103,7 +103,19 @@ public:
     // Enqueue on `stream`.  When ev != nullptr it holds n_stages()+1 events to record around stages.
     virtual void run(const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype,
                      int64_t y_cols, int64_t ldy, hipStream_t stream, hipEvent_t* ev) = 0;
-    virtual void check_errors() {}                // after a synchronisation: did a kernel of an earlier run report a failure?
+    // Lanes (hg_flow_set_lanes): n copies of everything a call WRITES — activation workspace, tile-queue counters and their
+    // host-tracked base, the host-visible error word — over one copy of what it only reads (weights, tables, plans), so that
+    // run_lane(0, ...) and run_lane(1, ...) may be in flight on two streams at once.  run() is run_lane(0, ...).  false: this
+    // plan keeps one set of state (the caller stays serial).  Only called while nothing of this executor is in flight.
+    virtual bool set_lanes(int n) { return n == 1; }
+    virtual int lanes() const { return 1; }
+    // Never profiled.  A lane whose workspace has to grow waits for `stream` first: the lane's earlier steps ran there.
+    virtual void run_lane(int lane, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols,
+                          int64_t ldy, hipStream_t stream) {
+        if (lane != 0) fail(HG_ERR_STATE, "this plan has one lane");
+        run(x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, stream, nullptr);
+    }
+    virtual void check_errors() {}                // after a synchronisation: did a kernel of an earlier run (any lane) report a failure?
     virtual void release() = 0;                   // free device memory
 };
 

@@ -1002,6 +1002,23 @@ struct HostStage {
     DevBuf d_afrag, d_bias, d_kb1tab, d_chunks, d_runs, d_piece, d_koff, d_kmean, d_kcol;
 };
 
+// Counters of the dynamic tile queues (16 words apart); zeroed once, then only ever advanced.  One set per kernel that
+// uses them (every launch advances all of ITS counters by the same amount).
+struct WorkQueue {
+    DevBuf ctr;
+    uint32_t base = 0;
+};
+
+// What one call writes (Executor::set_lanes): two calls on two lanes share nothing they store to.
+constexpr int kMaxLanes = 2;
+struct Lane {
+    DevBuf bufA, bufB;                    // activation workspace (fragment order), ping-pong
+    int64_t cap_rows = 0;
+    WorkQueue wq_front, wq_direct, wq_direct_wg;
+    int32_t* err_host = nullptr;          // error word the polling kernels write (device_error_word)
+    int32_t* err_dev = nullptr;
+};
+
 class FusedExecutor : public Executor {
 public:
     FusedExecutor(const TNode& root, std::vector<FStage>&& fs, const FusedOptions& opt) : opt_(opt), out_dim_(root.out_dim) {
@@ -1330,7 +1347,11 @@ public:
         return t;
     }
     int64_t padded_flops_per_row() const override { return padded_flops_; }
-    int64_t workspace_bytes() const override { return (int64_t)(bufA_.bytes + bufB_.bytes); }
+    int64_t workspace_bytes() const override {      // every lane's
+        int64_t t = 0;
+        for (int l = 0; l < n_lanes_; ++l) t += (int64_t)(lanes_[l].bufA.bytes + lanes_[l].bufB.bytes);
+        return t;
+    }
 
     void to_device() override {
         for (auto& s : stages_) {
@@ -1363,25 +1384,47 @@ public:
             n_cus_ = prop.multiProcessorCount;
     }
 
-    void reserve(int64_t rows) override {
-        int64_t tiles = (rows + 15) / 16;
-        size_t need = (size_t)tiles * max_nb_ * 1024;
-        bufA_.alloc(need);
-        bufB_.alloc(need);
-        cap_rows_ = std::max(cap_rows_, tiles * 16);
+    void reserve(int64_t rows) override {      // every lane
+        for (int l = 0; l < n_lanes_; ++l) reserve_lane(lanes_[l], rows);
     }
+
+    // Lanes (Executor::set_lanes): everything a call writes lives in a Lane; stages_, sub_runs_ and the tables are shared and
+    // only read once to_device() has run.  The lane of the call being enqueued is passed down to whatever touches its state.
+    bool set_lanes(int n) override {
+        if (n < 1 || n > kMaxLanes) return false;
+        for (int l = n; l < n_lanes_; ++l) release_lane(lanes_[l]);
+        for (int l = n_lanes_; l < n; ++l) reserve_lane(lanes_[l], lanes_[0].cap_rows);
+        n_lanes_ = n;
+        return true;
+    }
+    int lanes() const override { return n_lanes_; }
 
     void run(const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
              hipStream_t st, hipEvent_t* ev) override {
-        check_device_error();      // of an earlier call: the word is host memory the kernels write through
-        if (n > cap_rows_) reserve(n);
-        // (Cutting a batch into row ranges on separate streams, plain or staggered, was measured and dropped: 0.69-0.84 ms
-        // against 0.65 at N = 4096 — DESIGN.md §6.1.)
-        run_range(x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, st, ev, (f32x4*)bufA_.p, (f32x4*)bufB_.p);
+        run_in(lanes_[0], x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, st, ev);
+    }
+    void run_lane(int lane, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
+                  hipStream_t st) override {
+        if (lane < 0 || lane >= n_lanes_) fail(HG_ERR_ARG, "lane %d outside 0..%d", lane, n_lanes_ - 1);
+        run_in(lanes_[lane], x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, st, nullptr);
     }
 
-    void run_range(const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
-                   hipStream_t st, hipEvent_t* ev, f32x4* bufA, f32x4* bufB) {
+    void run_in(Lane& L, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
+                hipStream_t st, hipEvent_t* ev) {
+        check_device_error();      // of an earlier call: the word is host memory the kernels write through
+        if (n > L.cap_rows) {
+            // the buffers about to be freed may still be read by this lane's last step, which ran on `st`.  The other lane's
+            // buffers are not touched, but its step is drained as well: freeing device memory synchronises the whole device
+            if (n_lanes_ > 1) HG_HIP(hipStreamSynchronize(st));
+            reserve_lane(L, n);
+        }
+        // (Cutting a batch into row ranges on separate streams, plain or staggered, was measured and dropped: 0.69-0.84 ms
+        // against 0.65 at N = 4096 — DESIGN.md §6.1.)
+        run_range(L, x, x_dtype, n, ldx, y, y_dtype, y_cols, ldy, st, ev);
+    }
+
+    void run_range(Lane& L, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
+                   hipStream_t st, hipEvent_t* ev) {
         const int n_tiles = (int)((n + 15) / 16);
         const int sub_set = pick_sub_set(n_tiles);
         int e = 0;
@@ -1390,8 +1433,8 @@ public:
                 for (int i = 0; i < k; ++i) HG_HIP(hipEventRecord(ev[e++], st));
         };
         record(1);
-        f32x4* cur = bufA;
-        f32x4* nxt = bufB;
+        f32x4* cur = (f32x4*)L.bufA.p;
+        f32x4* nxt = (f32x4*)L.bufB.p;
         for (int si = 0; si < (int)stages_.size(); ++si) {
             if (tail_begin_ >= 0 && si == tail_start(n_tiles)) {
                 launch_top(si, cur, n_tiles, y, y_dtype, y_cols, ldy, n, st);
@@ -1417,7 +1460,7 @@ public:
             else if (s.kind == 2)
                 launch_igsfa(s, P, n_tiles, si, st);
             else if (s.from_x)
-                covered = launch_front(s, P, x, x_dtype, ldx, n, n_tiles, cur, st) ? 2 : 1;
+                covered = launch_front(L, s, P, x, x_dtype, ldx, n, n_tiles, cur, st) ? 2 : 1;
             else if (s.kind == 3)
                 launch_prod(s, P, n_tiles, st);
             else if (!launch_splitm(s, P, n_tiles, st))
@@ -1432,14 +1475,8 @@ public:
     }
 
     void release() override {
-        bufA_.free();
-        bufB_.free();
-        wq_front_.ctr.free();
-        wq_direct_.ctr.free();
-        wq_direct_wg_.ctr.free();
-        if (err_host_) (void)hipHostFree(err_host_);
-        err_host_ = nullptr;
-        err_dev_ = nullptr;
+        for (Lane& L : lanes_) release_lane(L);
+        n_lanes_ = 1;
         d_col_base_.free();
         d_col_of_.free();
         for (SubRun& r : sub_runs_)
@@ -1448,10 +1485,29 @@ public:
             s.d_afrag.free(); s.d_bias.free(); s.d_kb1tab.free(); s.d_chunks.free();
             s.d_runs.free(); s.d_piece.free(); s.d_koff.free(); s.d_kmean.free(); s.d_kcol.free(); s.d_gcol.free(); s.d_etab.free(); s.d_pack_slot.free();
         }
-        cap_rows_ = 0;
     }
 
 private:
+    void reserve_lane(Lane& L, int64_t rows) {
+        int64_t tiles = (rows + 15) / 16;
+        size_t need = (size_t)tiles * max_nb_ * 1024;
+        L.bufA.alloc(need);
+        L.bufB.alloc(need);
+        L.cap_rows = std::max(L.cap_rows, tiles * 16);
+    }
+    void release_lane(Lane& L) {
+        L.bufA.free();
+        L.bufB.free();
+        L.wq_front.ctr.free();
+        L.wq_direct.ctr.free();
+        L.wq_direct_wg.ctr.free();
+        L.wq_front.base = L.wq_direct.base = L.wq_direct_wg.base = 0;
+        if (L.err_host) (void)hipHostFree(L.err_host);
+        L.err_host = nullptr;
+        L.err_dev = nullptr;
+        L.cap_rows = 0;
+    }
+
     // resident workgroups per CU for (kernel, block size, LDS) — cached occupancy query
     int resident_blocks(StageFn fn, int threads, size_t lds) {
         set_lds_limit(fn, lds);
@@ -1464,12 +1520,6 @@ private:
         return nb;
     }
 
-    // Counters of the dynamic tile queues (16 words apart); zeroed once, then only ever advanced.  One set per kernel that
-    // uses them (every launch advances all of ITS counters by the same amount).
-    struct WorkQueue {
-        DevBuf ctr;
-        uint32_t base = 0;
-    };
     uint32_t* work_counters(WorkQueue& q, int n, hipStream_t st) {
         const size_t need = (size_t)n * 64;
         if (q.ctr.bytes < need) {
@@ -1485,18 +1535,19 @@ private:
     // Error word shared with the kernels that poll (k_chain, k_stage01d with the workgroup queue): pinned, device-mapped
     // host memory, so the host can look at it without synchronising.  A poll only runs out on a bug; the run that hit it
     // produced wrong features, and every later call on this flow fails loudly.
-    int32_t* device_error_word() {
-        if (!err_host_) {
-            HG_HIP(hipHostMalloc((void**)&err_host_, 64, hipHostMallocMapped));
-            *err_host_ = 0;
-            HG_HIP(hipHostGetDevicePointer((void**)&err_dev_, err_host_, 0));
+    int32_t* device_error_word(Lane& L) {
+        if (!L.err_host) {
+            HG_HIP(hipHostMalloc((void**)&L.err_host, 64, hipHostMallocMapped));
+            *L.err_host = 0;
+            HG_HIP(hipHostGetDevicePointer((void**)&L.err_dev, L.err_host, 0));
         }
-        return err_dev_;
+        return L.err_dev;
     }
     void check_errors() override { check_device_error(); }
-    void check_device_error() {
-        if (err_host_ && *(volatile int32_t*)err_host_ != 0)
-            fail(HG_ERR_DEVICE, "fused: a bounded poll in a persistent kernel ran out (code %d); the features of that call are invalid", (int)*err_host_);
+    void check_device_error() {      // every lane's word
+        for (const Lane& L : lanes_)
+            if (L.err_host && *(volatile int32_t*)L.err_host != 0)
+                fail(HG_ERR_DEVICE, "fused: a bounded poll in a persistent kernel ran out (code %d); the features of that call are invalid", (int)*L.err_host);
     }
 
     void set_lds_limit(StageFn fn, size_t bytes) {
@@ -2226,7 +2277,7 @@ private:
 
     // Stage 0, which reads the caller's rows.  Returns true where stage 1 ran fused in the same launch (k_stage01d / k_stage01p,
     // writing out1 where its own launch would); else k_stage0p (persistent) or k_stage0.
-    bool launch_front(const HostStage& s, StageParams& P, const void* x, int x_dtype, int64_t ldx, int64_t n, int n_tiles, f32x4* out1,
+    bool launch_front(Lane& L, const HostStage& s, StageParams& P, const void* x, int x_dtype, int64_t ldx, int64_t n, int n_tiles, f32x4* out1,
                       hipStream_t st) {
         P.chunks = (const DChunk*)s.d_chunks.p;
         P.runs = (const DRun*)s.d_runs.p;
@@ -2276,9 +2327,9 @@ private:
                 stamps_begin(P, P.n_chunks * P.tile_parts, 12, st);
             }
 #endif
-            P.err = device_error_word();
+            P.err = device_error_word(L);
             {   // k_stage01p: one queue of tile groups per chunk; k_stage01d: one queue of tiles per layer-1 node (or per chunk)
-                WorkQueue& wq = direct ? (wgq ? wq_direct_wg_ : wq_direct_) : wq_front_;
+                WorkQueue& wq = direct ? (wgq ? L.wq_direct_wg : L.wq_direct) : L.wq_front;
                 P.work_ctr = work_counters(wq, direct && !wgq ? stages_[1].n_nodes : P.n_chunks, st);
                 P.work_base = wq.base;
                 wq.base += (uint32_t)groups2;      // what this launch adds to every counter (StageParams::work_ctr)
@@ -2840,13 +2891,12 @@ private:
     bool s0_transpose_ = false, fuse01_ = false;
     std::vector<HostStage> stages_;
     std::vector<int32_t> col_base_, col_of_;
-    DevBuf d_col_base_, d_col_of_, bufA_, bufB_;
+    DevBuf d_col_base_, d_col_of_;
+    Lane lanes_[kMaxLanes];
+    int n_lanes_ = 1;
     int tail_begin_ = -1;         // first stage of the top-of-hierarchy launch (k_tail); -1: none
     int tail_act_blocks_ = 0, tail_e_blocks_ = 0;
     std::vector<SubRun> sub_runs_;      // k_subtree runs (short batches)
-    WorkQueue wq_front_, wq_direct_, wq_direct_wg_;
-    int32_t* err_host_ = nullptr;
-    int32_t* err_dev_ = nullptr;
 #ifdef HIGSFA_DIAG
     DevBuf stamp_buf_;
     int stamp_blocks_ = 0;
@@ -2854,7 +2904,7 @@ private:
     std::map<const void*, size_t> lds_set_;
     std::map<std::tuple<const void*, int, size_t>, int> occ_;
     int max_nb_ = 0;
-    int64_t padded_flops_ = 0, cap_rows_ = 0;
+    int64_t padded_flops_ = 0;
     int n_cus_ = 256;
 };
 

@@ -237,6 +237,40 @@ class Flow(object):
             h.h, C.c_void_p(x_ptr), _capi.np_dtype_code(x_dtype), int(n), int(ldx), C.c_void_p(y_ptr),
             _capi.np_dtype_code(y_dtype), int(y_cols), int(ldy), C.c_void_p(stream)))
 
+    # --- step lanes (include/higsfa.h "Step lanes"; used by pyfaceanalysis_amd.sharded.ShardedFlow) --------------------------
+    def set_lanes(self, n, nodenr=None):
+        """Give the handle ``n`` (1 or 2) copies of its per-call state.  False, and the handle stays serial, where the plan
+        cannot (the generic plan) or the loaded library has no lanes."""
+        fn = getattr(_capi.lib(), "hg_flow_set_lanes", None)
+        if fn is None:
+            return int(n) == 1
+        return fn(self._handle(nodenr).h, int(n)) == _capi.HG_OK
+
+    def lanes(self, nodenr=None):
+        n = C.c_int(1)
+        _capi.check(_capi.lib().hg_flow_lanes(self._handle(nodenr).h, C.byref(n)))
+        return n.value
+
+    def step_lane_device(self, lane, x_ptr, x_dtype, n, ldx, y_ptr, y_dtype, y_cols, ldy, ready_stream=0, nodenr=None):
+        """``execute_device`` on the lane's own stream and state, ordered behind everything enqueued on ``ready_stream`` so far;
+        the features are ordered by ``lane_done_event`` / ``lane_join``, not on ``ready_stream``."""
+        _capi.check(_capi.lib().hg_flow_step_lane_device(
+            self._handle(nodenr).h, int(lane), C.c_void_p(x_ptr), _capi.np_dtype_code(x_dtype), int(n), int(ldx), C.c_void_p(y_ptr),
+            _capi.np_dtype_code(y_dtype), int(y_cols), int(ldy), C.c_void_p(ready_stream)))
+
+    def lane_done_event(self, lane, nodenr=None):
+        """Raw handle (hipEvent_t, owned by the flow) of the event the lane's last step recorded."""
+        ev = C.c_void_p()
+        _capi.check(_capi.lib().hg_flow_lane_done_event(self._handle(nodenr).h, int(lane), C.byref(ev)))
+        return ev
+
+    def lane_join(self, lane, stream=0, nodenr=None):
+        """Make ``stream`` wait for the lane's last step."""
+        _capi.check(_capi.lib().hg_flow_lane_join(self._handle(nodenr).h, int(lane), C.c_void_p(stream)))
+
+    def check_errors(self, nodenr=None):
+        _capi.check(_capi.lib().hg_flow_check_errors(self._handle(nodenr).h))
+
     def close(self):
         for h in self._handles.values():
             h.close()

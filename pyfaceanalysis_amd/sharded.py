@@ -46,6 +46,29 @@ def _side_stream(torch, device):
     return _SIDE_STREAMS[key]
 
 
+class _LaneEvent(object):
+    """A lane's "done" event (hipEvent_t owned by the flow's native handle) with the part of ``torch.cuda.Event``'s surface a
+    consumer of ``ShardedFlow.done_event`` needs: ``synchronize()``, ``query()``, ``wait(stream)`` — the last is what
+    ``torch.cuda.Stream.wait_event`` calls.  Valid while the flow is open and until the lane's next step re-records it, i.e. for
+    the two most recent steps."""
+
+    def __init__(self, capi, flow, torch, device, handle):
+        self._capi, self._flow, self._torch, self._device, self._h = capi, flow, torch, device, handle
+
+    def query(self):
+        q = self._capi.lib().hg_event_query(self._h)
+        if q < 0:
+            self._capi.check(q)
+        return q == 1
+
+    def synchronize(self):
+        self._capi.check(self._capi.lib().hg_event_synchronize(self._h))
+
+    def wait(self, stream=None):
+        st = self._torch.cuda.current_stream(self._device) if stream is None else stream
+        self._capi.check(self._capi.lib().hg_stream_wait_event(st.cuda_stream, self._h))
+
+
 class ShardedFlow(object):
     """One rank's share of a sharded ``flow.execute``.
 
@@ -76,6 +99,19 @@ class ShardedFlow(object):
     RCCL's all-gather does, but until a run on more than one GPU has confirmed it the caller must ask for it: ``bench.py``
     does, after ``verify_against_blocking_gather`` has passed on every rank.  The two events in the other direction
     ("the gather has finished READING buffer b": an order, no data) are always device-scope.
+
+    Step lanes (``for_flow`` on a GPU, fused plan): consecutive steps are independent batches, so step i runs
+    on lane ``i & 1`` of the flow's native handle — its own workspace, tile queues and stream over the one copy of the weights
+    — and the chip runs steps i and i + 1 side by side: 9 % more steps per second at 4096 rows, each step taking 1.8 times as
+    long from its first launch to its last (``HIGSFA_STEP_LANES=1`` where one step's latency matters more).
+    ``self.stream`` orders the INPUT of a step as before (everything enqueued
+    on it when ``step`` is called precedes the step), and ``step`` joins lane b into ``self.stream`` before it touches
+    ``ys[b]`` again, so "valid only until step i + 2" holds.  THE ONE CONTRACT CHANGE: without a collective, a step's
+    features are no longer ordered on ``self.stream`` at the moment ``step`` returns; wait for ``done_event(i)`` — then the
+    lane's own event, with ``synchronize()``, ``query()`` and ``stream.wait_event(ev)`` — or call ``wait()``.  With a collective
+    the gather waits for the lane (side stream) or runs behind the kernels on the lane's stream ("same"), and ``done_event``
+    is what it was.  ``HIGSFA_STEP_LANES=1``, a plan that cannot separate its state (the generic plan) or a CPU device keep the
+    serial path, where a step's features ARE ordered on ``self.stream``.
     """
 
     def __init__(self, execute_local, n_cols, rows, device=None, collective=None, light_events=None, gather_stream="side"):
@@ -97,6 +133,7 @@ class ShardedFlow(object):
         self.y_alls = [mk(self.rows * self.world), mk(self.rows * self.world)] if self.collective else None
         self._n = 0
         self._filled = [0, 0]          # rows of ys[b] that may hold features of an earlier step
+        self.lanes = 1                 # 2: steps alternate between the flow's two lanes (for_flow)
         if gather_stream not in ("side", "same"):
             raise ValueError("gather_stream must be 'side' or 'same'")
         self.gather_stream = gather_stream
@@ -125,19 +162,57 @@ class ShardedFlow(object):
                 self._recorded = [False, False]
 
     @classmethod
-    def for_flow(cls, flow, n_cols, rows, device, collective=None, light_events=None, gather_stream="side"):
-        """Bind ``flow.execute_device`` (pyfaceanalysis_amd.flow.Flow on this rank's GPU)."""
+    def for_flow(cls, flow, n_cols, rows, device, collective=None, light_events=None, gather_stream="side", lanes=None):
+        """Bind ``flow.execute_device`` (pyfaceanalysis_amd.flow.Flow on this rank's GPU).  ``lanes``: 2 (the default on a GPU;
+        ``HIGSFA_STEP_LANES`` overrides the default) runs consecutive steps on the flow's two lanes where its plan has them, 1
+        keeps every step on ``self.stream``."""
+        import os
         import numpy as np
         import torch
         np_dt = {torch.float32: np.float32, torch.float64: np.float64, torch.uint8: np.uint8}
+        if lanes is None:
+            try:
+                lanes = int(os.environ.get("HIGSFA_STEP_LANES", "") or 2)
+            except ValueError:      # not a number: the default
+                lanes = 2
+        want_lanes = int(lanes) >= 2 and torch.device(device).type == "cuda"
+        have_lanes = want_lanes and flow.set_lanes(2)      # a plan without lanes: today's path, silently
         flow.reserve(rows)
 
-        def run(x_block, y_out, stream):
+        def check(x_block, y_out):
             if x_block.stride(1) != 1 or y_out.stride() != (n_cols, 1):
                 raise ValueError("ShardedFlow: x rows and the feature buffer must be contiguous")
+
+        def run(x_block, y_out, stream):
+            check(x_block, y_out)
             flow.execute_device(x_block.data_ptr(), np_dt[x_block.dtype], x_block.shape[0], x_block.stride(0),
                                 y_out.data_ptr(), np.float32, n_cols, n_cols, stream=stream)
-        return cls(run, n_cols, rows, device=device, collective=collective, light_events=light_events, gather_stream=gather_stream)
+
+        def run_lane(lane, x_block, y_out, ready_stream):
+            check(x_block, y_out)
+            flow.step_lane_device(lane, x_block.data_ptr(), np_dt[x_block.dtype], x_block.shape[0], x_block.stride(0),
+                                  y_out.data_ptr(), np.float32, n_cols, n_cols, ready_stream=ready_stream)
+        sf = cls(run, n_cols, rows, device=device, collective=collective, light_events=light_events, gather_stream=gather_stream)
+        if have_lanes:
+            sf._use_lanes(flow, run_lane)
+        return sf
+
+    def _use_lanes(self, flow, run_lane):
+        import ctypes as C
+        from . import _capi
+        torch = self.torch
+        self._capi = _capi
+        self._lane_flow, self._run_lane = flow, run_lane
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.lane_stream_ids = []
+        for lane in range(2):
+            sid = C.c_uint64()
+            _capi.check(_capi.lib().hg_lane_stream_id(int(dev_index), lane, C.byref(sid)))
+            self.lane_stream_ids.append(int(sid.value))
+        # the collective "on the kernels' own stream" runs on the lane's stream
+        self._lane_streams = [torch.cuda.ExternalStream(sid, device=self.device) for sid in self.lane_stream_ids] if self.collective else None
+        self._lane_events = [_LaneEvent(_capi, flow, torch, self.device, flow.lane_done_event(lane)) for lane in range(2)]
+        self.lanes = 2
 
     def step(self, x_local):
         """Enqueue one pass over this rank's block; returns the (world*rows, n_cols) gathered features
@@ -153,8 +228,54 @@ class ShardedFlow(object):
                 return self._step(x_local, b, m)
         return self._step(x_local, b, m)
 
+    def _step_lanes(self, x_local, b, m):
+        """Step i on lane b = i & 1 (class docstring).  Order of the hand-offs:
+        lane b's last step (i - 2) -> self.stream [join] -> zero_ of stale rows -> (side stream: gather i - 2 has read ys[b]) ->
+        "ready" recorded on self.stream inside the native call -> lane b's stream -> kernels -> "done" -> gather / consumer."""
+        torch, capi = self.torch, self._capi
+        L = capi.lib()
+        s = self.stream.cuda_stream
+        self._lane_flow.lane_join(b, s)
+        if m < self._filled[b]:
+            with torch.cuda.stream(self.stream):
+                self.ys[b][m:self._filled[b]].zero_()
+        self._filled[b] = m
+        side = self.collective and self.gather_stream == "side"
+        if side and self._recorded[b]:
+            # the gather of step i - 2 read ys[b]: it must be done before this step's kernels write there.  It almost always is:
+            # ask first (a wait that is not needed still costs a barrier packet)
+            q = L.hg_event_query(self._light[b])
+            if q < 0:
+                capi.check(q)
+            if q == 0:
+                capi.check(L.hg_stream_wait_event(s, self._light[b]))
+        self._run_lane(b, x_local, self.ys[b][:m], s)      # m == 0: the events only
+        if not self.collective:
+            return self.ys[b]
+        if not side:
+            # "same": behind the kernels on THEIR stream, which is the lane's; y_alls[b] is rewritten by step i + 2 on this stream too
+            ls = self._lane_streams[b]
+            with torch.cuda.stream(ls):
+                gather_features(self.ys[b], self.y_alls[b])
+                self.gathered[b].record(ls)
+            return self.y_alls[b]
+        if self.light_events:
+            done = self._lane_events[b]._h
+        else:      # the hand-off that carries the features at system scope, as the caller asked: an ordinary event behind the lane's step
+            capi.check(L.hg_event_record(self._light[2], self.lane_stream_ids[b]))
+            done = self._light[2]
+        capi.check(L.hg_stream_wait_event(self.comm.cuda_stream, done))
+        with torch.cuda.stream(self.comm):
+            gather_features(self.ys[b], self.y_alls[b])
+            capi.check(L.hg_event_record(self._light[b], self.comm.cuda_stream))
+            self._recorded[b] = True
+            self.gathered[b].record(self.comm)
+        return self.y_alls[b]
+
     def _step(self, x_local, b, m):
         torch = self.torch
+        if self.lanes == 2:
+            return self._step_lanes(x_local, b, m)
         if m < self._filled[b]:         # a fuller step used this buffer before: its rows m.. must not be published again
             if self.cuda:
                 with torch.cuda.stream(self.stream):
@@ -229,13 +350,18 @@ class ShardedFlow(object):
 
     def done_event(self, step_index=None):
         """The event recorded after the gather of step ``step_index`` (default: the last one enqueued); only the
-        two most recent steps have one.  ``None`` on CPU or without a collective (then the result of a step is
-        ordered on ``self.stream`` itself)."""
+        two most recent steps have one.  Without a collective: the step's lane's own "done" event where steps run on lanes
+        (``synchronize()``, ``query()``, ``stream.wait_event(ev)``), else ``None`` — on CPU or on the serial path
+        (``HIGSFA_STEP_LANES=1``, the generic plan) the result of a step is ordered on ``self.stream`` itself, there is no event to
+        wait for, and the call stays valid: a consumer treats ``None`` as "already ordered on ``self.stream``"; ``wait()`` works on
+        every path."""
         last = self._n - 1
         i = last if step_index is None else int(step_index)
         if not (last - 1 <= i <= last) or i < 0:
             raise ValueError("step %d: only the two most recent steps (%d, %d) still own a buffer" % (i, last - 1, last))
-        return self.gathered[i & 1] if (self.cuda and self.collective) else None
+        if self.cuda and self.collective:
+            return self.gathered[i & 1]
+        return self._lane_events[i & 1] if self.lanes == 2 else None
 
     def close(self):
         if getattr(self, "_light", None):
