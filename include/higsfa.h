@@ -345,7 +345,8 @@ void hg_cascade_free(hg_cascade* c);
  * reference.  The prescale stays NEAREST (:551-561).  Takes effect from the next detect / step call on this handle; setting it
  * while a call on this handle is in flight on another thread or stream is the caller's error. */
 int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n);
-/* frame_dev: (frame_h, frame_w) uint8 on the device, row stride ld; boxes_host (n0, 4) / level_host (n0, 3): the first-stage
+/* frame_dev: (frame_h, frame_w) uint8 on the device, row stride ld >= frame_w (a pitched buffer, a crop of a larger frame); this
+ * and every entry below that reads a frame returns HG_ERR_ARG for ld < frame_w before it launches or writes anything; boxes_host (n0, 4) / level_host (n0, 3): the first-stage
  * windows and their level constants.  Outputs (host, room for out_cap detections): final coordinates, angles, index of the
  * original window, Disc confidence; *n_out detections; stage_counts[n_stages] survivors after each stage (-1 where the count
  * was not read back); *rows_executed rows pushed through flows.  Synchronous. */

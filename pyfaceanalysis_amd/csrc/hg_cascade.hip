@@ -742,6 +742,13 @@ struct Bounded {
     const int32_t* final_count;      // out
 };
 
+// Every frame-reading entry of this file refuses a bad frame as a bad ARGUMENT, before it launches or writes anything: a row stride
+// below the width (a broadcast view has 0) would have every row read its neighbours' pixels.
+void check_frame_geometry(int frame_h, int frame_w, int64_t ld) {
+    if (frame_h <= 0 || frame_w <= 0 || ld < frame_w)
+        hg::fail(HG_ERR_ARG, "bad frame geometry: %d rows of %d pixels, %lld apart", frame_h, frame_w, (long long)ld);
+}
+
 void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
                  const LevelTable* T, int64_t n0, double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence,
                  int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr,
@@ -749,6 +756,8 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
     if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
     if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
     if (n0 > 0 && (!frame_dev || (!T && !B && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
+    // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
+    if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
     if (B && (n0 != kTracked || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
     set_dev(c->device);
     hipStream_t st = (hipStream_t)stream;
@@ -945,6 +954,7 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
     fld = ld;
     if (prescale_w > 0 || prescale_h > 0) {
         if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
+        check_frame_geometry(frame_h, frame_w, ld);
         set_dev(c->device);
         if (c->pre_src_w != frame_w || c->pre_src_h != frame_h) {
             const double box[4] = {0.0, 0.0, (double)frame_w, (double)frame_h};
