@@ -287,6 +287,34 @@ int hg_patcher_extract_filter(hg_patcher* p, int filter, const void* frame, int 
                               const double* boxes, const double* delta_angs, int64_t n, int out_w, int out_h, void* out,
                               int out_dtype, int64_t ldo);
 
+/* --- Colour frames: PIL's "L" conversion -----------------------------------------------------------------------------------
+ * A camera or a decoder delivers packed colour pixels; the reference converts them first (im.convert("L"),
+ * FaceDetectUpdated.py:541-543; its file branch loads with image_format="L", :533).  PIL's rule is integer and per pixel,
+ *     L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16
+ * and a fourth byte (RGBA, RGBX) is ignored.  Tested bit for bit against PIL, every 24-bit colour included.
+ * A colour frame is frame_h rows of frame_w packed pixels, rows ld_bytes BYTES apart: any ld_bytes >= frame_w * bytes per pixel
+ * and any base address, so a crop of a larger colour frame is a frame.  HG_FRAME_L is the grey frame every other entry reads. */
+#define HG_FRAME_L    0   /* one byte per pixel */
+#define HG_FRAME_RGB  1   /* packed, 3 bytes per pixel */
+#define HG_FRAME_BGR  2
+#define HG_FRAME_RGBA 3   /* packed, 4 bytes per pixel, 4th byte ignored (RGBX too) */
+#define HG_FRAME_BGRA 4
+/* The whole frame -> dst_dev (frame_h rows of frame_w bytes, dst_ld >= frame_w apart), enqueued on `stream`, no host wait.
+ * HG_FRAME_L: a pitched copy.  src and dst must NOT overlap (a thread reads four pixels and writes four bytes; nothing orders it
+ * against its neighbours).  HG_ERR_ARG, nothing launched: unknown format, null pointer, frame_h / frame_w <= 0,
+ * ld_bytes < frame_w * bytes per pixel, dst_ld < frame_w. */
+int hg_frame_to_gray_device(int device, const void* src_dev, int format, int frame_h, int frame_w, int64_t ld_bytes,
+                            uint8_t* dst_dev, int64_t dst_ld, void* stream);
+/* The same rule on the host, no device involved (runs on a machine without a GPU). */
+int hg_frame_to_gray_host(const void* src, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst, int64_t dst_ld);
+/* NEAREST, unrotated windows cut straight from a colour uint8 frame: every output pixel is the conversion of the source pixel
+ * hg_patcher_extract_device would pick on the converted frame (same index tables), 0 outside the frame.  Only the picked pixels
+ * are read.  Rotated and BILINEAR / BICUBIC windows are not cut from colour: convert first.  HG_FRAME_L: hg_patcher_extract_device
+ * on an HG_U8 frame. */
+int hg_patcher_extract_format_device(hg_patcher* p, int frame_format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes,
+                                     const double* boxes_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype,
+                                     int64_t ldo, void* stream);
+
 /* --- Cascade glue on the device (the reference's stage loop between two hot calls) -----------------
  * update_current_subimage_coordinates (face_analysis.py:803-840) + identify_patches_to_discard (:842-887) for n
  * candidates from their regression outputs, then the boolean-mask compaction of FaceDetectUpdated.py:739-759 as
@@ -345,6 +373,15 @@ void hg_cascade_free(hg_cascade* c);
  * reference.  The prescale stays NEAREST (:551-561).  Takes effect from the next detect / step call on this handle; setting it
  * while a call on this handle is in flight on another thread or stream is the caller's error. */
 int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n);
+/* The format of the frames handed to this cascade (HG_FRAME_*; HG_FRAME_L until set).  Afterwards frame_dev / ld of
+ * hg_cascade_detect_device, hg_cascade_detect_levels_device, hg_cascade_detect_frame_device, hg_cascade_detect_faces_frame_device
+ * and hg_tracker_step_frame_device (a tracker on this cascade) are read as that format, ld in BYTES (for HG_FRAME_L what it always
+ * meant), and refused with HG_ERR_ARG for ld < frame_w * bytes per pixel.  With a prescale the grey prescaled frame is cut from the
+ * colour frame in one launch that reads the sampled pixels only; without one the frame is converted once into a grey buffer that
+ * lives with the cascade and grows on demand.  Everything behind that — the grid, the stage loop, the eye step, the purge, the
+ * tracker — reads that grey frame.  May be called between frames, like hg_cascade_set_interpolation; HG_ERR_ARG (and nothing
+ * changed) for an unknown format. */
+int hg_cascade_set_frame_format(hg_cascade* c, int format);
 /* frame_dev: (frame_h, frame_w) uint8 on the device, row stride ld >= frame_w (a pitched buffer, a crop of a larger frame); this
  * and every entry below that reads a frame returns HG_ERR_ARG for ld < frame_w before it launches or writes anything; boxes_host (n0, 4) / level_host (n0, 3): the first-stage
  * windows and their level constants.  Outputs (host, room for out_cap detections): final coordinates, angles, index of the

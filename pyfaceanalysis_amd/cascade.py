@@ -26,7 +26,7 @@ import math
 
 import numpy as np
 
-from . import _capi, grid
+from . import _capi, frames, grid
 from .patches import Patcher
 
 CUT_OFFS_FACE = [0.99, 0.95, 0.85, 0.8, 0.7, 0.6, 0.5, 0.45, 0.10, 0.05]      # FaceDetectUpdated.py:98
@@ -93,12 +93,15 @@ def tracked_windows(box, pipeline, subimage_size):
 
 
 class DeviceCascade(object):
-    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0, interpolation_formats=None):
+    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0, interpolation_formats=None, frame_format="L"):
         """interpolation_formats: the filter of every stage's extraction, a sequence indexed by the stage's serial like
         ``CUT_OFFS_FACE`` (FaceDetectUpdated.py:125, :671; PIL's codes 0 / 2 / 3); None: NEAREST everywhere.  The prescale is
-        NEAREST whatever this says (:551-561)."""
+        NEAREST whatever this says (:551-561).  frame_format: the format of the frames ``detect``, ``detect_frame``, ``detect_faces``
+        and ``prescale`` are given ("L", "RGB", "BGR", "RGBA", "BGRA": frames.py); a colour frame is converted as PIL's
+        ``convert("L")`` does (:541-543) inside the library, and everything behind that reads the grey frame."""
         import torch
         self.torch = torch
+        self.frame_format = frames.format_code(frame_format)
         self.stages = list(stages)
         self.w, self.h = int(subimage_size[0]), int(subimage_size[1])
         self.k = int(n_features)              # feature columns kept per candidate (>= every classifier's input_dim)
@@ -153,38 +156,64 @@ class DeviceCascade(object):
         if self.interpolation_formats is not None:
             fmt = (C.c_int32 * len(self.interpolation_formats))(*self.interpolation_formats)
             _capi.check(L.hg_cascade_set_interpolation(h, fmt, len(self.interpolation_formats)))
+        if self.frame_format != _capi.HG_FRAME_L:
+            _capi.check(L.hg_cascade_set_frame_format(h, self.frame_format))
         return h
+
+    def set_frame_format(self, frame_format):
+        """Change the format of the frames given from now on (hg_cascade_set_frame_format): between two frames, never during one."""
+        code = frames.format_code(frame_format)
+        if self._h is not None:
+            _capi.check(_capi.lib().hg_cascade_set_frame_format(self._h, code))
+        self.frame_format = code
+
+    def _check_frame(self, frame):
+        frames.check_color_frame(self.torch, frame, self.frame_format, self.dev)
 
     def prescale(self, frame, prescale_size=grid.PRESCALE_SIZE):
         """FaceDetectUpdated.py:551-556: shrink so that the larger side is <= prescale_size, ``Image.resize(NEAREST)`` —
         PIL's nearest resize is the EXTENT rule over the whole frame, so the patcher does it (bit-exact vs PIL in the tests).
-        A frame that needs no shrinking is returned as it is.  Otherwise the returned tensor lives with the cascade, one per
+        A grey frame that needs no shrinking is returned as it is.  Otherwise the returned tensor lives with the cascade, one per
         (frame size, prescaled size): it is valid until the next ``prescale()`` with the same frame size and the same prescaled
-        size on this cascade, which writes into it again — a caller that keeps a prescaled frame longer clones it."""
-        from .eyes import check_frame
+        size on this cascade, which writes into it again — a caller that keeps a prescaled frame longer clones it.  A colour frame
+        (``frame_format``) always comes back as such a cascade-owned grey tensor, the grey frame the cascade reads: cut from the
+        colour frame by the same rule (only the sampled pixels are converted), or, where no shrinking is needed, converted whole."""
         t = self.torch
-        check_frame(t, frame, self.dev)
+        self._check_frame(frame)
         fh, fw = int(frame.shape[0]), int(frame.shape[1])
         pw, ph = grid.prescaled_size(fw, fh, prescale_size)
+        stream = t.cuda.current_stream(self.dev).cuda_stream
         if (pw, ph) == (fw, fh):
-            return frame
+            if self.frame_format == _capi.HG_FRAME_L:
+                return frame
+            key = (fw, fh, fw, fh)
+            if key not in self._prescale:
+                self._prescale[key] = (None, t.empty((fh, fw), dtype=t.uint8, device=self.dev))
+            return frames.to_gray(frame, self.frame_format, out=self._prescale[key][1])
         key = (fw, fh, pw, ph)
         if key not in self._prescale:      # the box of the whole frame and the output live with the cascade: no per-frame upload / allocation
             self._prescale[key] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
                                    t.empty((ph, pw), dtype=t.uint8, device=self.dev))
         whole, small = self._prescale[key]
-        self.patcher.extract_device(frame.data_ptr(), np.uint8, fh, fw, frame.stride(0), whole.data_ptr(), 1, (pw, ph), small.data_ptr(),
-                                    np.uint8, pw * ph, stream=t.cuda.current_stream(self.dev).cuda_stream)
+        if self.frame_format == _capi.HG_FRAME_L:
+            self.patcher.extract_device(frame.data_ptr(), np.uint8, fh, fw, frame.stride(0), whole.data_ptr(), 1, (pw, ph), small.data_ptr(),
+                                        np.uint8, pw * ph, stream=stream)
+        else:
+            _capi.check(_capi.lib().hg_patcher_extract_format_device(
+                self.patcher._handle(), self.frame_format, frame.data_ptr(), fh, fw, frame.stride(0), whole.data_ptr(), 1, pw, ph, small.data_ptr(),
+                _capi.HG_U8, pw * ph, stream))
         return small
 
     def detect(self, frame, smallest_face=0.2, windows=None):
-        """frame: (H, W) uint8 torch tensor on this device.  Returns a dict of host arrays: coords (n, 4), angles (n),
-        orig_index (n), confidence (n), counts (survivors after every stage, -1 where the count stayed on the device),
-        rows_executed."""
+        """frame: (H, W) uint8 torch tensor on this device ((H, W, C) for a colour ``frame_format``).  Returns a dict of host arrays:
+        coords (n, 4), angles (n), orig_index (n), confidence (n), counts (survivors after every stage, -1 where the count stayed on
+        the device), rows_executed."""
         t, L = self.torch, _capi.lib()
-        fh, fw = int(frame.shape[0]), int(frame.shape[1])
-        if frame.dtype != t.uint8 or frame.device != self.dev or frame.stride(1) != 1:
+        if self.frame_format != _capi.HG_FRAME_L:
+            self._check_frame(frame)
+        elif frame.dtype != t.uint8 or frame.device != self.dev or frame.stride(1) != 1:
             raise ValueError("frame must be a uint8 tensor on %s with contiguous rows" % (self.dev,))
+        fh, fw = int(frame.shape[0]), int(frame.shape[1])
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         counts = np.zeros(len(self.stages), dtype=np.int32)
         n_out, rows = C.c_int64(), C.c_int64()
@@ -219,9 +248,8 @@ class DeviceCascade(object):
         it and writing its detections (FaceDetectUpdated.py:551-561 prescale, :589-600 grid, :665-766 stage loop).  Everything that
         depends only on the frame size — prescaled size, level table, output buffers — is computed once and kept; the frame itself
         is checked on every call (the library is handed its raw pointer)."""
-        from .eyes import check_frame
         t, L = self.torch, _capi.lib()
-        check_frame(t, frame, self.dev)
+        self._check_frame(frame)
         fh, fw = int(frame.shape[0]), int(frame.shape[1])
         key = (fw, fh, float(smallest_face), int(prescale_size or 0))
         plan = self._frames.get(key)
@@ -245,9 +273,8 @@ class DeviceCascade(object):
         (hg_cascade_detect_faces_frame_device; FaceDetectUpdated.py:947-1041, :1180).  Returns faces (m, 10) = (x0, y0, x1, y1, angle,
         eyeL_x, eyeL_y, eyeR_x, eyeR_y, confidence), n_before_purge, counts, rows_executed, n_windows.  The frame is checked on every
         call; everything that depends only on the frame size is computed once and kept."""
-        from .eyes import check_frame
         t, L = self.torch, _capi.lib()
-        check_frame(t, frame, self.dev)
+        self._check_frame(frame)
         if eyes.device != self.device:
             raise ValueError("eye locator on device %d, cascade on device %d" % (eyes.device, self.device))
         fh, fw = int(frame.shape[0]), int(frame.shape[1])

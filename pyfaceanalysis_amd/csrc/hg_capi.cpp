@@ -43,6 +43,7 @@ int guarded(F&& fn) {
 
 namespace hg {
 void set_last_error(const std::string& s) { g_last_error = s; }
+const char* frame_to_gray_host(const void* src, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst, int64_t dst_ld);      // hg_hostpack.cpp
 }  // namespace hg
 
 namespace {
@@ -643,6 +644,14 @@ extern "C" {
 int hg_version(void) { return HG_VERSION; }
 
 const char* hg_last_error(void) { return g_last_error.c_str(); }
+
+// PIL's "L" conversion on the host: the rule itself is plain C++ in hg_hostpack.cpp
+int hg_frame_to_gray_host(const void* src, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst, int64_t dst_ld) {
+    const char* why = hg::frame_to_gray_host(src, format, frame_h, frame_w, ld_bytes, dst, dst_ld);
+    if (!why) return HG_OK;
+    hg::set_last_error(why);
+    return HG_ERR_ARG;
+}
 
 int hg_device_count(int* count) {
     return guarded([&] {

@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "hg_common.hpp"
+#include "hg_frame_format.hpp"
 #include "hg_gauss_dev.hpp"
 
 namespace hg {
@@ -617,6 +618,8 @@ struct hg_cascade {
     hg::DevBuf coords[2], angles[2], conf[2], oidx[2], sl[2], subs[2], neg, reg, discard, map, count, orig_coords, orig_level, orig_angles, chunk_count;
     hg::DevBuf pre_box, pre_frame;       // hg_cascade_detect_frame_device: the box of the whole frame and the prescaled frame
     int pre_src_w = 0, pre_src_h = 0;    // ... the frame size pre_box was written for
+    int frame_format = HG_FRAME_L;       // hg_cascade_set_frame_format: how frame_dev / ld of the detect entries are read
+    hg::DevBuf gray_frame;               // a colour frame that is not prescaled, converted (grows on demand, like pre_frame)
     int32_t* host_count = nullptr;       // pinned, device-visible: {count, sequence number} (publish_count)
     int32_t seq = 0;                     // sequence number of the last read-back asked for
     char* host_res = nullptr;            // pinned: the final survivors (HostResults), kResCap rows
@@ -689,6 +692,14 @@ int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n) {
     });
 }
 
+int hg_cascade_set_frame_format(hg_cascade* c, int format) {
+    return guarded([&] {
+        if (!c) hg::fail(HG_ERR_ARG, "null cascade handle");
+        if (!hg::frame_bpp(format)) hg::fail(HG_ERR_ARG, "unknown frame format %d (0 L, 1 RGB, 2 BGR, 3 RGBA, 4 BGRA)", format);
+        c->frame_format = format;
+    });
+}
+
 void hg_cascade_free(hg_cascade* c) {
     if (!c) return;
     if (hipSetDevice(c->device) == hipSuccess) {
@@ -744,9 +755,9 @@ struct Bounded {
 
 // Every frame-reading entry of this file refuses a bad frame as a bad ARGUMENT, before it launches or writes anything: a row stride
 // below the width (a broadcast view has 0) would have every row read its neighbours' pixels.
-void check_frame_geometry(int frame_h, int frame_w, int64_t ld) {
-    if (frame_h <= 0 || frame_w <= 0 || ld < frame_w)
-        hg::fail(HG_ERR_ARG, "bad frame geometry: %d rows of %d pixels, %lld apart", frame_h, frame_w, (long long)ld);
+void check_frame_geometry(int frame_h, int frame_w, int64_t ld, int bpp = 1) {
+    if (frame_h <= 0 || frame_w <= 0 || ld < (int64_t)frame_w * bpp)
+        hg::fail(HG_ERR_ARG, "bad frame geometry: %d rows of %d pixels of %d byte(s), %lld apart", frame_h, frame_w, bpp, (long long)ld);
 }
 
 void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
@@ -945,7 +956,19 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
 
 // FaceDetectUpdated.py:551-561: im.resize((w, h), NEAREST) before the grid is laid out — PIL's nearest resize is the EXTENT rule over
 // the whole frame (tested against PIL), so the patcher does it, into a buffer that lives with the cascade (prescale_w = 0: none).
-// fr / fh / fw / fld: the frame the grid and the stage loop read.
+// fr / fh / fw / fld: the frame the grid and the stage loop read — always grey.  A colour frame (hg_cascade_set_frame_format) is
+// prescaled by the same whole-frame box through the format gather, which converts the sampled pixels only; one that needs no
+// prescale is converted as a whole (gray_frame_of).
+void gray_frame_of(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, void* stream, const void*& fr, int64_t& fld) {
+    check_frame_geometry(frame_h, frame_w, ld, hg::frame_bpp(c->frame_format));
+    set_dev(c->device);
+    c->gray_frame.alloc((size_t)frame_h * frame_w);
+    if (hg_frame_to_gray_device(c->device, frame_dev, c->frame_format, frame_h, frame_w, ld, (uint8_t*)c->gray_frame.p, frame_w, stream) != HG_OK)
+        hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
+    fr = c->gray_frame.p;
+    fld = frame_w;
+}
+
 void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
                     const void*& fr, int& fh, int& fw, int64_t& fld) {
     fr = frame_dev;
@@ -954,7 +977,7 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
     fld = ld;
     if (prescale_w > 0 || prescale_h > 0) {
         if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
-        check_frame_geometry(frame_h, frame_w, ld);
+        check_frame_geometry(frame_h, frame_w, ld, hg::frame_bpp(c->frame_format));
         set_dev(c->device);
         if (c->pre_src_w != frame_w || c->pre_src_h != frame_h) {
             const double box[4] = {0.0, 0.0, (double)frame_w, (double)frame_h};
@@ -964,14 +987,16 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
         }
         c->pre_frame.alloc((size_t)prescale_w * prescale_h);
         const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
-        if (hg_patcher_extract_keyed_device(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), frame_dev, HG_U8, frame_h, frame_w, ld,
-                                            (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8,
-                                            (int64_t)prescale_w * prescale_h, stream) != HG_OK)
+        if (hg::patcher_extract_format(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), c->frame_format, frame_dev, frame_h, frame_w, ld,
+                                       (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8, (int64_t)prescale_w * prescale_h,
+                                       stream) != HG_OK)
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         fr = c->pre_frame.p;
         fh = prescale_h;
         fw = prescale_w;
         fld = prescale_w;
+    } else if (c->frame_format != HG_FRAME_L && frame_dev) {      // (a null frame: detect_impl's refusal)
+        gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, fr, fld);
     }
 }
 
@@ -984,6 +1009,7 @@ int hg_cascade_detect_device(hg_cascade* c, const void* frame_dev, int frame_h, 
                              double* out_confidence, int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed,
                              void* stream) {
     return guarded([&] {
+        if (c && c->frame_format != HG_FRAME_L && frame_dev && n0 > 0) gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, frame_dev, ld);
         detect_impl(c, frame_dev, frame_h, frame_w, ld, boxes_host, level_host, nullptr, n0, out_coords, out_angles, out_orig_index, out_confidence,
                     out_cap, n_out, stage_counts, rows_executed, stream);
     });
@@ -994,6 +1020,7 @@ int hg_cascade_detect_levels_device(hg_cascade* c, const void* frame_dev, int fr
                                     int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
     return guarded([&] {
         const LevelTable T = make_level_table(levels, n_levels);
+        if (c && c->frame_format != HG_FRAME_L && frame_dev && T.first[T.n_levels] > 0) gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, frame_dev, ld);
         detect_impl(c, frame_dev, frame_h, frame_w, ld, nullptr, nullptr, &T, T.first[T.n_levels], out_coords, out_angles, out_orig_index,
                     out_confidence, out_cap, n_out, stage_counts, rows_executed, stream);
     });

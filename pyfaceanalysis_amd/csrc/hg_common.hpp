@@ -174,5 +174,9 @@ struct DevBuf {
 int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w, int64_t ld,
                     const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo,
                     void* stream);
+// hg_extract.hip: NEAREST, unrotated windows from a frame of format HG_FRAME_* (ld_bytes: row stride in bytes), the tables kept under
+// `key` as above.  What hg_patcher_extract_format_device (key = 0) and the cascade's prescale of a colour frame call.
+int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,
+                           int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
 
 }  // namespace hg

@@ -25,9 +25,14 @@
 // The reference's other filters (interpolation_formats, FaceDetectUpdated.py:125: BILINEAR, BICUBIC) are the second half of this
 // file ("BILINEAR / BICUBIC windows"): PIL's generic affine transform in doubles, the same composition for rotated windows with
 // the stage's filter in both steps.
+//
+// Colour frames (include/higsfa.h, HG_FRAME_*): PIL's integer "L" rule (hg_frame_format.hpp) in k_frame_to_gray — a whole frame — and in
+// k_extent_gather instantiated on a packed-pixel source type — NEAREST, unrotated windows cut straight from the colour frame, which is
+// how the cascade prescales one.
 #include <hip/hip_runtime.h>
 
 #include "hg_common.hpp"
+#include "hg_frame_format.hpp"
 
 struct hg_patcher {
     int device = -1;
@@ -97,17 +102,39 @@ __global__ void k_extent_tables(const double* __restrict__ boxes, int64_t n, int
     if (angs && e == 0) rot_coef_store(boxes, angs, b, fw, fh, rot);
 }
 
+// A packed colour pixel as a source pixel type of k_extent_gather (include/higsfa.h, HG_FRAME_*): BPP bytes, alignment 1, read as
+// PIL's "L" value.  Only the BPP bytes of the pixel itself are read — a 4-byte read of a 3-byte pixel would leave the frame at the
+// last pixel of its last row.
+template <int BPP, bool BGR>
+struct ColorPx {
+    uint8_t c[BPP];
+};
+template <typename FT>
+__device__ __forceinline__ FT px_load(const FT* __restrict__ row, int x) { return row[x]; }
+template <int BPP, bool BGR>
+__device__ __forceinline__ uint8_t px_load(const ColorPx<BPP, BGR>* __restrict__ row, int x) {
+    const uint8_t* p = row[x].c;
+    if constexpr (BPP == 4) {      // the pixel's own four bytes as one load
+        uint32_t q;
+        __builtin_memcpy(&q, p, 4);
+        return hg::rgb_to_gray((q >> (BGR ? 16 : 0)) & 0xffu, (q >> 8) & 0xffu, (q >> (BGR ? 0 : 16)) & 0xffu);
+    } else {
+        return hg::rgb_to_gray(p[BGR ? 2 : 0], p[1], p[BGR ? 0 : 2]);
+    }
+}
+
 // One workgroup per (group of output rows, box): no index divisions, the row's source line and the column table are
-// read once; four output pixels per thread and one vector store when the output is uint8.
+// read once; four output pixels per thread and one vector store when the output is uint8.  ld_bytes: the frame's row stride in
+// bytes (a colour frame's rows need not be a whole number of pixels apart).
 template <typename FT, typename OT>
-__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame, int64_t ld, const int32_t* __restrict__ tabs, int64_t n,
+__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame, int64_t ld_bytes, const int32_t* __restrict__ tabs, int64_t n,
                                                         int w, int h, OT* __restrict__ out, int64_t ldo) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;     // blockDim.y output rows per workgroup
     if (y >= h) return;
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
         const int32_t* t = tabs + b * (w + h);
         const int ys = t[w + y];
-        const FT* src = frame + (int64_t)(ys >= 0 ? ys : 0) * ld;
+        const FT* src = (const FT*)((const char*)frame + (int64_t)(ys >= 0 ? ys : 0) * ld_bytes);
         OT* dst = out + b * ldo + (int64_t)y * w;
         if constexpr (sizeof(OT) == 1) {
             if ((w & 3) == 0 && (ldo & 3) == 0 && ((uintptr_t)out & 3) == 0) {
@@ -124,7 +151,7 @@ __global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ fr
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int xs = xs4[k];
-                        const uint32_t v = (xs >= 0 && ys >= 0) ? (uint32_t)(uint8_t)(OT)src[xs] : 0u;
+                        const uint32_t v = (xs >= 0 && ys >= 0) ? (uint32_t)(uint8_t)(OT)px_load(src, xs) : 0u;
                         pk |= v << (8 * k);
                     }
                     *(uint32_t*)(dst + x) = pk;
@@ -134,7 +161,48 @@ __global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ fr
         }
         for (int x = threadIdx.x; x < w; x += blockDim.x) {
             const int xs = t[x];
-            dst[x] = (xs >= 0 && ys >= 0) ? (OT)src[xs] : (OT)0;
+            dst[x] = (xs >= 0 && ys >= 0) ? (OT)px_load(src, xs) : (OT)0;
+        }
+    }
+}
+
+// A whole colour frame -> grey (hg_frame_to_gray_device; BPP = 1: a pitched copy).  A thread takes four neighbouring pixels of one
+// row: ONE unaligned load of their 4 * BPP bytes (rows start at any byte; gfx950 runs in unaligned-access mode, as for
+// k_extent_gather_u8x16 below) and one 4-byte store where dst rows are 4-aligned (`packed`), four byte stores otherwise.  The last
+// w % 4 pixels of a row are read pixel by pixel, so no load touches a byte outside [row start, row start + w * BPP).  Rows beyond the
+// grid's reach (more than 65535 rows of workgroups) are taken in further trips.
+template <int BPP, bool BGR>
+__global__ void __launch_bounds__(256) k_frame_to_gray(const uint8_t* __restrict__ src, int64_t ld_bytes, int h, int w, uint8_t* __restrict__ dst,
+                                                        int64_t dst_ld, int packed) {
+    const int64_t x = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (x >= w) return;
+    auto gray = [](const uint8_t* p) -> uint32_t {
+        if constexpr (BPP == 1) return p[0];
+        else return hg::rgb_to_gray(p[BGR ? 2 : 0], p[1], p[BGR ? 0 : 2]);
+    };
+    for (int64_t y = (int64_t)blockIdx.y * blockDim.y + threadIdx.y; y < h; y += (int64_t)gridDim.y * blockDim.y) {
+        const uint8_t* s = src + y * ld_bytes + x * BPP;
+        uint8_t* d = dst + y * dst_ld + x;
+        if (x + 4 <= w) {
+            uint32_t q[BPP];      // the four pixels' 4 * BPP bytes as BPP words (kept as words: a byte array is split into a load per channel)
+            __builtin_memcpy(q, s, 4 * BPP);
+            auto byte = [&](int i) -> uint32_t { return (q[i >> 2] >> (8 * (i & 3))) & 0xffu; };
+            uint32_t pk = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if constexpr (BPP == 1) pk = q[0];
+                else pk |= (uint32_t)hg::rgb_to_gray(byte(k * BPP + (BGR ? 2 : 0)), byte(k * BPP + 1), byte(k * BPP + (BGR ? 0 : 2))) << (8 * k);
+            }
+            if (packed) {
+                *(uint32_t*)d = pk;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d[k] = (uint8_t)(pk >> (8 * k));
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k)      // the row's last w % 4 pixels
+                if (x + k < w) d[k] = (uint8_t)gray(s + k * BPP);
         }
     }
 }
@@ -613,8 +681,9 @@ int guarded(F&& fn) {
     }
 }
 
+// ld_bytes: the frame's row stride in bytes (ld * sizeof(FT) for the scalar pixel types)
 template <typename FT>
-void launch_gather(const void* frame, int64_t ld, int fw, const int32_t* tabs, int64_t n, int w, int h, void* out, int out_dtype, int64_t ldo,
+void launch_gather(const void* frame, int64_t ld_bytes, int fw, const int32_t* tabs, int64_t n, int w, int h, void* out, int out_dtype, int64_t ldo,
                    hipStream_t st) {
     if constexpr (sizeof(FT) == 1) {
         const int tpr = w >> 4;
@@ -626,7 +695,7 @@ void launch_gather(const void* frame, int64_t ld, int fw, const int32_t* tabs, i
             while (passes > 1 && n * ((h + rows_per_pass * passes - 1) / (rows_per_pass * passes)) < 1024) passes = (passes + 1) / 2;
             const int rows_per_wg = rows_per_pass * passes;
             const dim3 grid((unsigned)((h + rows_per_wg - 1) / rows_per_wg), (unsigned)std::min<int64_t>(n, 65535));
-            hipLaunchKernelGGL(k_extent_gather_u8x16, grid, 256, 0, st, (const uint8_t*)frame, ld, fw, tabs, n, w, h, (uint8_t*)out, ldo, rows_per_wg);
+            hipLaunchKernelGGL(k_extent_gather_u8x16, grid, 256, 0, st, (const uint8_t*)frame, ld_bytes, fw, tabs, n, w, h, (uint8_t*)out, ldo, rows_per_wg);
             return;
         }
     }
@@ -634,9 +703,21 @@ void launch_gather(const void* frame, int64_t ld, int fw, const int32_t* tabs, i
     const dim3 thr(tx, 256 / tx);
     const dim3 grid((unsigned)((h + thr.y - 1) / thr.y), (unsigned)std::min<int64_t>(n, 65535));
     switch (out_dtype) {
-        case HG_U8: hipLaunchKernelGGL((k_extent_gather<FT, uint8_t>), grid, thr, 0, st, (const FT*)frame, ld, tabs, n, w, h, (uint8_t*)out, ldo); break;
-        case HG_F32: hipLaunchKernelGGL((k_extent_gather<FT, float>), grid, thr, 0, st, (const FT*)frame, ld, tabs, n, w, h, (float*)out, ldo); break;
-        default: hipLaunchKernelGGL((k_extent_gather<FT, double>), grid, thr, 0, st, (const FT*)frame, ld, tabs, n, w, h, (double*)out, ldo); break;
+        case HG_U8: hipLaunchKernelGGL((k_extent_gather<FT, uint8_t>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (uint8_t*)out, ldo); break;
+        case HG_F32: hipLaunchKernelGGL((k_extent_gather<FT, float>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (float*)out, ldo); break;
+        default: hipLaunchKernelGGL((k_extent_gather<FT, double>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (double*)out, ldo); break;
+    }
+}
+
+// the gather by frame format: HG_FRAME_L is the grey frame's own launch (the 16-pixel kernel where it applies)
+void launch_gather_format(int format, const void* frame, int64_t ld_bytes, int fw, const int32_t* tabs, int64_t n, int w, int h, void* out, int out_dtype,
+                          int64_t ldo, hipStream_t st) {
+    switch (format) {
+        case HG_FRAME_L: launch_gather<uint8_t>(frame, ld_bytes, fw, tabs, n, w, h, out, out_dtype, ldo, st); break;
+        case HG_FRAME_RGB: launch_gather<ColorPx<3, false>>(frame, ld_bytes, fw, tabs, n, w, h, out, out_dtype, ldo, st); break;
+        case HG_FRAME_BGR: launch_gather<ColorPx<3, true>>(frame, ld_bytes, fw, tabs, n, w, h, out, out_dtype, ldo, st); break;
+        case HG_FRAME_RGBA: launch_gather<ColorPx<4, false>>(frame, ld_bytes, fw, tabs, n, w, h, out, out_dtype, ldo, st); break;
+        default: launch_gather<ColorPx<4, true>>(frame, ld_bytes, fw, tabs, n, w, h, out, out_dtype, ldo, st); break;
     }
 }
 
@@ -698,9 +779,87 @@ void check_filter(int filter, int frame_dtype) {
     if (filter != HG_FILTER_NEAREST && frame_dtype != HG_U8) hg::fail(HG_ERR_ARG, "BILINEAR / BICUBIC windows need an HG_U8 frame");
 }
 
+// The NEAREST index tables of n unrotated boxes, built on `st`: key != 0 — kept in the patcher's ring under that key
+// (hg_patcher_extract_keyed_device's contract) and built on the first use only; key == 0 — the patcher's own table buffer, rebuilt.
+// The tables hold pixel indices: they do not depend on the frame's format.
+const int32_t* nearest_tables(hg_patcher* p, uint64_t key, int frame_h, int frame_w, const double* boxes_dev, int64_t n, int out_w, int out_h, hipStream_t st) {
+    const int64_t n_ent = n * (out_w + out_h);
+    if ((n_ent + 255) / 256 > 0x7fffffffll) hg::fail(HG_ERR_ARG, "too many boxes");
+    int32_t* tabs = nullptr;
+    if (key) {
+        hg_patcher::Keyed* K = nullptr;
+        for (auto& k : p->keyed)
+            if (k.key == key && !k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
+        if (K) return (const int32_t*)K->tabs.p;
+        // first use of this key (or its shape changed): build the tables, in stream order, into a buffer of their own
+        K = &p->keyed[p->keyed_next];
+        p->keyed_next = (p->keyed_next + 1) % 4;
+        if (K->tabs.p && (size_t)n_ent * 4 > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
+        K->tabs.alloc((size_t)n_ent * 4);
+        K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 0;
+        tabs = (int32_t*)K->tabs.p;
+    } else {
+        p->tabs.alloc((size_t)n_ent * 4);
+        tabs = (int32_t*)p->tabs.p;
+    }
+    hipLaunchKernelGGL(k_extent_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, tabs, (const double*)nullptr,
+                       (RotCoef*)nullptr);
+    return tabs;
+}
+
+void check_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        hg::fail(HG_ERR_DEVICE, "no HIP device available (this library has no CPU execution path)");
+    if (device < 0 || device >= count) hg::fail(HG_ERR_DEVICE, "device %d out of range", device);
+}
+
+// what every entry that reads a colour frame refuses before it launches anything
+void check_color_frame(int format, int frame_h, int frame_w, int64_t ld_bytes) {
+    const int bpp = hg::frame_bpp(format);
+    if (!bpp) hg::fail(HG_ERR_ARG, "unknown frame format %d (0 L, 1 RGB, 2 BGR, 3 RGBA, 4 BGRA)", format);
+    if (frame_h <= 0 || frame_w <= 0 || ld_bytes < (int64_t)frame_w * bpp)
+        hg::fail(HG_ERR_ARG, "bad frame geometry: %d rows of %d pixels of %d bytes, %lld bytes apart", frame_h, frame_w, bpp, (long long)ld_bytes);
+}
+
+template <int BPP, bool BGR>
+void launch_to_gray(const void* src, int64_t ld_bytes, int h, int w, uint8_t* dst, int64_t dst_ld, hipStream_t st) {
+    const int w4 = (w + 3) / 4;                                          // threads a row needs
+    const unsigned tx = w4 > 64 ? 256 : w4 > 32 ? 64 : 32;
+    const dim3 thr(tx, 256 / tx);
+    const dim3 grid((unsigned)((w4 + tx - 1) / tx), (unsigned)std::min<int64_t>(((int64_t)h + thr.y - 1) / thr.y, 65535));
+    const int packed = ((uintptr_t)dst & 3) == 0 && (dst_ld & 3) == 0 ? 1 : 0;
+    hipLaunchKernelGGL((k_frame_to_gray<BPP, BGR>), grid, thr, 0, st, (const uint8_t*)src, ld_bytes, h, w, dst, dst_ld, packed);
+}
+
 }  // namespace
 
 extern "C" {
+
+int hg_frame_to_gray_device(int device, const void* src_dev, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst_dev, int64_t dst_ld,
+                            void* stream) {
+    return guarded([&] {
+        check_color_frame(format, frame_h, frame_w, ld_bytes);
+        if (!src_dev || !dst_dev) hg::fail(HG_ERR_ARG, "null data pointer");
+        if (dst_ld < frame_w) hg::fail(HG_ERR_ARG, "bad output row stride %lld for %d pixels", (long long)dst_ld, frame_w);
+        check_device(device);
+        HG_HIP(hipSetDevice(device));
+        hipStream_t st = (hipStream_t)stream;
+        switch (format) {
+            case HG_FRAME_L: launch_to_gray<1, false>(src_dev, ld_bytes, frame_h, frame_w, dst_dev, dst_ld, st); break;
+            case HG_FRAME_RGB: launch_to_gray<3, false>(src_dev, ld_bytes, frame_h, frame_w, dst_dev, dst_ld, st); break;
+            case HG_FRAME_BGR: launch_to_gray<3, true>(src_dev, ld_bytes, frame_h, frame_w, dst_dev, dst_ld, st); break;
+            case HG_FRAME_RGBA: launch_to_gray<4, false>(src_dev, ld_bytes, frame_h, frame_w, dst_dev, dst_ld, st); break;
+            default: launch_to_gray<4, true>(src_dev, ld_bytes, frame_h, frame_w, dst_dev, dst_ld, st); break;
+        }
+        HG_HIP(hipGetLastError());
+    });
+}
+
+int hg_patcher_extract_format_device(hg_patcher* p, int frame_format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes,
+                                     const double* boxes_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    return hg::patcher_extract_format(p, 0, frame_format, frame_dev, frame_h, frame_w, ld_bytes, boxes_dev, n, out_w, out_h, out_dev, out_dtype, ldo, stream);
+}
 
 int hg_patcher_create(int device, hg_patcher** out) {
     return guarded([&] {
@@ -748,7 +907,7 @@ int hg_patcher_extract_rotate_device(hg_patcher* p, const void* frame_dev, int f
         } else if (frame_dtype == HG_U8) {
             launch_gather<uint8_t>(frame_dev, ld, frame_w, (const int32_t*)p->tabs.p, n, out_w, out_h, out_dev, out_dtype, ldo, st);
         } else {
-            launch_gather<float>(frame_dev, ld, frame_w, (const int32_t*)p->tabs.p, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+            launch_gather<float>(frame_dev, ld * 4, frame_w, (const int32_t*)p->tabs.p, n, out_w, out_h, out_dev, out_dtype, ldo, st);
         }
         HG_HIP(hipGetLastError());
     });
@@ -762,22 +921,9 @@ int hg_patcher_extract_keyed_device(hg_patcher* p, uint64_t key, const void* fra
         if (n == 0) return;
         HG_HIP(hipSetDevice(p->device));
         hipStream_t st = (hipStream_t)stream;
-        const int64_t n_ent = n * (out_w + out_h);
-        if ((n_ent + 255) / 256 > 0x7fffffffll) hg::fail(HG_ERR_ARG, "too many boxes");
-        hg_patcher::Keyed* K = nullptr;
-        for (auto& k : p->keyed)
-            if (k.key == key && !k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
-        if (!K) {      // first use of this key (or its shape changed): build the tables, in stream order, into a buffer of their own
-            K = &p->keyed[p->keyed_next];
-            p->keyed_next = (p->keyed_next + 1) % 4;
-            if (K->tabs.p && (size_t)n_ent * 4 > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
-            K->tabs.alloc((size_t)n_ent * 4);
-            K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 0;
-            hipLaunchKernelGGL(k_extent_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (int32_t*)K->tabs.p,
-                               (const double*)nullptr, (RotCoef*)nullptr);
-        }
-        if (frame_dtype == HG_U8) launch_gather<uint8_t>(frame_dev, ld, frame_w, (const int32_t*)K->tabs.p, n, out_w, out_h, out_dev, out_dtype, ldo, st);
-        else launch_gather<float>(frame_dev, ld, frame_w, (const int32_t*)K->tabs.p, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+        const int32_t* tabs = nearest_tables(p, key, frame_h, frame_w, boxes_dev, n, out_w, out_h, st);
+        if (frame_dtype == HG_U8) launch_gather<uint8_t>(frame_dev, ld, frame_w, tabs, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+        else launch_gather<float>(frame_dev, ld * 4, frame_w, tabs, n, out_w, out_h, out_dev, out_dtype, ldo, st);
         HG_HIP(hipGetLastError());
     });
 }
@@ -830,6 +976,22 @@ int hg_patcher_extract(hg_patcher* p, const void* frame, int frame_dtype, int fr
 }  // extern "C"
 
 namespace hg {
+// NEAREST, unrotated windows from a frame of any format (hg_patcher_extract_format_device; key as for patcher_extract: the cascade's
+// prescale passes the key of its whole-frame box, whose tables a grey and a colour frame of one size share)
+int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,
+                           int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    return guarded([&] {
+        check_color_frame(format, frame_h, frame_w, ld_bytes);
+        check_args(p, frame_dev, HG_U8, frame_h, frame_w, ld_bytes, boxes_dev, n, out_w, out_h, out_dev, out_dtype, ldo);
+        if (n == 0) return;
+        HG_HIP(hipSetDevice(p->device));
+        hipStream_t st = (hipStream_t)stream;
+        const int32_t* tabs = nearest_tables(p, key, frame_h, frame_w, boxes_dev, n, out_w, out_h, st);
+        launch_gather_format(format, frame_dev, ld_bytes, frame_w, tabs, n, out_w, out_h, out_dev, out_dtype, ldo, st);
+        HG_HIP(hipGetLastError());
+    });
+}
+
 // The single dispatch (hg_common.hpp): every C entry of this file that takes a filter, and the cascade's stage loop, come through here.
 // NEAREST goes to the entries it always went to; BILINEAR and BICUBIC share a coordinate table (it holds coordinates, not taps), kept
 // per key under the contract of hg_patcher_extract_keyed_device (key != 0: unrotated boxes the caller declares unchanged).

@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "hg_frame_format.hpp"
+
 namespace hg {
 
 namespace {
@@ -114,4 +116,27 @@ bool narrow_row_f32(const float* src, uint8_t* dst, int64_t n) {
     return kHaveAvx2 ? narrow_f32_avx2(src, dst, n) : narrow_scalar(src, dst, n);
 }
 
+}  // namespace hg
+
+// PIL's "L" conversion on the host (include/higsfa.h, hg_frame_to_gray_host: the C entry is in hg_capi.cpp, this file stays free of the
+// library's other parts): the rule of hg_frame_to_gray_device in plain C++, row by row.  Returns nullptr, or why the call is refused.
+namespace hg {
+const char* frame_to_gray_host(const void* src, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst, int64_t dst_ld) {
+    const int bpp = frame_bpp(format);
+    if (!bpp) return "unknown frame format";
+    if (!src || !dst) return "null data pointer";
+    if (frame_h <= 0 || frame_w <= 0 || ld_bytes < (int64_t)frame_w * bpp) return "bad frame geometry";
+    if (dst_ld < frame_w) return "bad output row stride";
+    const bool bgr = format == HG_FRAME_BGR || format == HG_FRAME_BGRA;
+    for (int y = 0; y < frame_h; ++y) {
+        const uint8_t* s = (const uint8_t*)src + (int64_t)y * ld_bytes;
+        uint8_t* d = dst + (int64_t)y * dst_ld;
+        if (bpp == 1) {
+            memcpy(d, s, (size_t)frame_w);
+            continue;
+        }
+        for (int x = 0; x < frame_w; ++x, s += bpp) d[x] = rgb_to_gray(s[bgr ? 2 : 0], s[1], s[bgr ? 0 : 2]);
+    }
+    return nullptr;
+}
 }  // namespace hg

@@ -55,6 +55,7 @@ class EyeLocator(object):
             if c.avg_labels is None:
                 raise ValueError("%s needs avg_labels" % name)
         self._h = None
+        self._gray = None        # locate(frame_format=...): the converted frame, reused while the frame size stays
 
     def consts(self):
         c = _capi.HgEyeConsts()
@@ -93,12 +94,17 @@ class EyeLocator(object):
                                                      t.cuda.current_stream(self.dev).cuda_stream))
         return out.cpu().numpy()
 
-    def locate(self, frame, boxes, angles, return_patches=False):
+    def locate(self, frame, boxes, angles, return_patches=False, frame_format="L"):
         """The eye step for n faces on ``frame`` ((H, W) uint8 tensor on this device, contiguous rows), BEFORE the discard.  Host
         arrays: eye_coords (n, 4) = (eyeL_x, eyeL_y, eyeR_x, eyeR_y), too_far (n) bool, reg (2, 2n) — EyeLX / EyeLY regressions, left
-        eyes then right eyes — and with return_patches the contrast-normalised patches (2n, w*h) float32."""
+        eyes then right eyes — and with return_patches the contrast-normalised patches (2n, w*h) float32.  frame_format: a colour
+        frame (frames.py) is first converted as PIL's ``convert("L")`` does, into a buffer that lives with the locator."""
+        from . import frames
         t = self.torch
-        check_frame(t, frame, self.dev)
+        if frames.check_color_frame(t, frame, frame_format, self.dev) != _capi.HG_FRAME_L:
+            if self._gray is None or tuple(self._gray.shape) != tuple(frame.shape[:2]):
+                self._gray = t.empty(tuple(frame.shape[:2]), dtype=t.uint8, device=self.dev)
+            frame = frames.to_gray(frame, frame_format, out=self._gray)
         b, a = self._faces(boxes, angles)
         n = b.shape[0]
         ec = t.empty((n, 4), dtype=t.float64, device=self.dev)

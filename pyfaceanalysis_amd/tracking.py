@@ -16,7 +16,6 @@ import numpy as np
 
 from . import _capi, grid
 from .cascade import frame_levels
-from .eyes import check_frame
 
 N_TRACKED = 9          # windows of a tracked frame: 3 posX values x 3 (equal) posY values
 
@@ -50,13 +49,14 @@ class FaceTracker(object):
         return None if self._box is None else self._box.copy()
 
     def step(self, frame):
-        """One frame of the stream ((H, W) uint8 tensor on the device, contiguous rows; checked on every call).  Returns faces (m, 10)
+        """One frame of the stream ((H, W) uint8 tensor on the device, contiguous rows — or a colour frame of the cascade's
+        ``frame_format``; checked on every call).  Returns faces (m, 10)
         as ``DeviceCascade.detect_faces``, tracked (this frame used the nine-window grid), n_windows (9 then, else the grid's count),
         n_before_purge, counts (-1 throughout on a tracked frame: no count left the device) and rows_executed."""
         if self._h is None:
             raise RuntimeError("tracker is closed")
         t, L, dc = self.torch, _capi.lib(), self.cascade
-        check_frame(t, frame, dc.dev)
+        dc._check_frame(frame)
         fh, fw = int(frame.shape[0]), int(frame.shape[1])
         plan = self._plans.get((fw, fh))
         if plan is None:
