@@ -1,32 +1,18 @@
-// Device-side definitions shared by the fused-plan translation units (hg_fused.hip: planner, executor,
-// mid/top layer kernels; hg_fused_front.hip: first-layer kernels; hg_fused_igsfa.hip: iGSFA kernels).
+// Device-side definitions shared by the fused-plan translation units (hg_fused.hip: executor, mid/top layer
+// kernels; hg_fused_front.hip: first-layer kernels; hg_fused_igsfa.hip: iGSFA kernels).  The planner is host
+// only: hg_fused_plan.cpp, and hg_fused_plan.hpp for what it shares with the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "hg_common.hpp"
+#include "hg_fused_plan.hpp"      // kMaxMT, kMaxFuncs, kMaxTail, DChunk, DRun: shared with the host-only planner
 
 namespace hg {
 namespace fused {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMaxMT = 4;            // up to 64 outputs per affine in the fused plan
-
-// Every stage is padded to a UNIFORM node structure (same K-block count, tile counts and
-// expansion list for all its nodes; missing pieces are zero weights), so all weight / bias
-// addresses are arithmetic on the node index and the only per-node table is the list of source
-// blocks of GEMM 1.
-constexpr int kMaxFuncs = 4;
-
-struct DChunk {   // stage 0: a group of consecutive nodes whose input columns share one LDS tile
-    int32_t node_begin, node_count, run_begin, run_count, n_cols, piece_begin, n_pieces, pad1;
-};
-struct DRun {
-    int32_t start, len, lds_off, pad;
-};
 
 // k_stage01p: two LDS tiles (one barrier per tile group) or one (two barriers, half the LDS).  With the packed
 // tile layout (128 + 4 words per row) both fit three workgroups per CU and measure the same (152-154 us).
@@ -426,7 +412,6 @@ struct TailStage {
     uint32_t nk2p[kMaxMT], funcp;
     float expo[kMaxFuncs];
 };
-constexpr int kMaxTail = 3;
 struct TailParams {
     TailStage st[kMaxTail];
     const f32x4* in;          // input of the first fused layer, fragment order (global memory)

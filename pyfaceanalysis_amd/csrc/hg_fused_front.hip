@@ -1,6 +1,6 @@
 // Fused plan, first-layer kernels: the caller's row-major sub-image matrix -> fragment-order activations
 // (layer 0 alone, its persistent variant, and layers 0+1 in one kernel).  See hg_fused.hip for the data
-// layout and the planner.
+// layout and hg_fused_plan.cpp for the planner.
 #include "hg_fused_dev.hpp"
 
 namespace hg {

@@ -178,7 +178,7 @@ __global__ void __launch_bounds__((KBM == 6 ? 768 : 512), (KBM <= 4 ? 4 : KBM <=
     }
 }
 
-// Folded iGSFA layer (hg_fused.hip, igsfa_affine): y = f(x - mean) W + c is a single GEMM from the expanded
+// Folded iGSFA layer (hg_fused_plan.cpp, igsfa_affine): y = f(x - mean) W + c is a single GEMM from the expanded
 // input fragments to the MO output tiles, and nothing needs the input fragments afterwards — so they are
 // streamed: one K-block of the node input in registers at a time (the next one, possibly the first block of
 // the next batch-tile group, already in flight), expanded under every function and multiplied into the

@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_tail(TailParams P) {
 // k_subtree: two or three layers BELOW the top as one launch for short batches.  Where the receptive fields tile the layer below
 // without overlap (every node of a layer is read by exactly one node of the next: all through the upper half of the preset
 // hierarchies), a run of layers falls into n_sub independent sub-trees (the planner lists each one's nodes: plan_subtree in
-// hg_fused.hip); a workgroup takes one sub-tree for one batch tile the way k_tail takes the whole top, and writes the sub-tree's
+// hg_fused_plan.cpp); a workgroup takes one sub-tree for one batch tile the way k_tail takes the whole top, and writes the sub-tree's
 // root tiles back in fragment order.  A short batch (one 1080p frame's later cascade stages: 18 .. 348 windows) leaves every
 // per-layer launch at its floor of 9-12 us; a run replaces three of them.  Consecutive workgroups are the sub-trees of one tile.
 // What it costs: a workgroup pulls its sub-tree's weights (up to 784 KiB for 4 + 2 + 1 nodes) through ONE compute unit's L1, so a

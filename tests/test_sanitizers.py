@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from pyfaceanalysis_amd import blob
-from tests import helpers
+from tests import helpers, plan_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -64,6 +64,20 @@ def test_blob_parser_under_asan_ubsan(tmp_path, nets):
     parsed = sum(int(l.split()[1]) for l in out.decode().splitlines() if l.startswith("parsed"))
     rejected = sum(int(l.split()[3]) for l in out.decode().splitlines() if l.startswith("parsed"))
     assert parsed + rejected == len(files) and parsed >= n_valid and rejected > 200
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_fused_planner_under_asan_ubsan(tmp_path):
+    """The fused planner (hg_fused_plan.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: the stand-alone driver of
+    tests/test_fused_plan_host.py, built with the sanitizers, plans every valid blob of that test (each under its switches)."""
+    exe = tmp_path / "plan_digest_driver_asan"
+    r = plan_cases.build_driver(exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    if r.returncode != 0:
+        pytest.skip("sanitizer build not possible here: " + r.stdout.decode(errors="replace")[-300:])
+    out = plan_cases.run_driver(exe, tmp_path, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=0", "UBSAN_OPTIONS": "print_stacktrace=1"})
+    assert len(out) == len(plan_cases.cases())
+    for name, lines in out.items():
+        assert lines and not any("runtime error" in ln or "AddressSanitizer" in ln for ln in lines), (name, lines[-5:])
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
