@@ -500,6 +500,11 @@ typedef struct hg_tracked_consts {
  * float64 on the device.  Enqueued on `stream`. */
 int hg_cascade_tracked_grid_device(int device, const hg_tracked_consts* consts, const double* face_dev, double* boxes_dev, double* level_dev,
                                    void* stream);
+/* The same for n_faces boxes in one launch (the grid kernel of a tracker that holds several faces): faces_dev (n_faces, 4) float64 ON THE
+ * DEVICE -> boxes_dev (9 * n_faces, 4) and level_dev (9 * n_faces, 3); window 9 s + i is window i of face s, the bits the single form
+ * writes for that face.  HG_ERR_ARG for a null pointer, n_faces < 1 and constants that are not positive and finite. */
+int hg_cascade_tracked_grid_multi_device(int device, const hg_tracked_consts* consts, const double* faces_dev, int n_faces, double* boxes_dev,
+                                         double* level_dev, void* stream);
 /* The tracker: created from a cascade and an eye handle on one device (both stay owned by the caller and must outlive it; consts'
  * sub-image size must be the cascade's).  It owns, on the device, the tracked box and its found flag, and remembers the size of the
  * prescaled frame the box belongs to.
@@ -525,6 +530,29 @@ int hg_tracker_reset(hg_tracker* t);
 int hg_tracker_step_frame_device(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h,
                                  const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out,
                                  int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid, void* stream);
+
+/* --- Several tracked faces ------------------------------------------------------------------------------------------------
+ * hg_tracker_create_multi: a tracker that holds up to max_faces faces (1..64) and, with rescan_every = R > 0, returns to the full grid
+ * after R consecutive tracked steps (0: never, as the reference).  hg_tracker_create is (max_faces, rescan_every) = (1, 0).  HG_ERR_ARG
+ * for max_faces outside 1..64 and for rescan_every < 0, before any handle is looked at.
+ * The path of a step is decided on the host.  A FULL-GRID step when nothing is held, when the prescaled size differs from the one the
+ * boxes belong to (all held boxes are dropped), or when R > 0 and R tracked steps have run since the last full-grid step: exactly
+ * hg_cascade_detect_faces_frame_device's work, then the hand-over.  Otherwise a TRACKED step with K = the held count: window 9 s + i is
+ * window i of held face s, the whole frame runs under the bound 9 K (the eye launches under 18 K) as described above with 9 K in the
+ * place of 9, the purge runs over the union of all faces' rows, *rows_executed counts 9 K rows per network-owning stage.
+ * The hand-over (both paths): candidates are the first min(kept, max_faces) purged rows; those whose four box numbers are all finite are
+ * carried, in purge order, as the held faces of the next step.  *n_held (nullable): that count.
+ * slots (nullable, out_cap entries): slots[j] is the index, in the previous step's carried order, of the held face whose nine windows
+ * produced kept row j; when the purge appends its first row a second time both copies carry the same slot; -1 for every row of a
+ * full-grid step.
+ * HG_ERR_ARG, writing no row and no slot, when out_cap is below the kept count (the hand-over has happened by then: *n_held is valid).
+ * hg_tracker_step_frame_device on such a handle is this call with slots = n_held = NULL.  One stream per handle, as above: a step must
+ * not run while another step of the same tracker, or any call on its cascade or eye handle, is in flight.  Synchronous. */
+int hg_tracker_create_multi(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int max_faces, int rescan_every, hg_tracker** out);
+int hg_tracker_step_frame_multi_device(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h,
+                                       const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out,
+                                       int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid,
+                                       int32_t* slots, int* n_held, void* stream);
 
 /* --- SFA training step for one layer of nodes (BASELINE.json configs[4]) -----
  * Not on the reference's path (it never trains, face_analysis.py:451-479); restates

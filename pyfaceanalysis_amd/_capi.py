@@ -21,6 +21,7 @@ _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extrac
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
 _ENTRIES_SINCE_COLOR = ("hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format")
+_ENTRIES_SINCE_MULTI_TRACKING = ("hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device")
 _lib = None
 
 
@@ -159,6 +160,10 @@ def lib():
         "hg_tracker_reset": (C.c_int, [vp]),
         "hg_tracker_step_frame_device": (C.c_int, [vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
                                                    C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(C.c_int), vp]),
+        "hg_cascade_tracked_grid_multi_device": (C.c_int, [i32, C.POINTER(HgTrackedConsts), vp, i32, vp, vp, vp]),
+        "hg_tracker_create_multi": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), i32, i32, C.POINTER(vp)]),
+        "hg_tracker_step_frame_multi_device": (C.c_int, [vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
+                                                         C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(C.c_int), vp, C.POINTER(C.c_int), vp]),
         "hg_sfa_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_pca_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_train_apply_device": (C.c_int, [vp, i32, i64, i64, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, i64, i32]),
@@ -169,7 +174,7 @@ def lib():
         except AttributeError:
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
-            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR and os.environ.get("HIGSFA_LIB"):
+            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -194,6 +199,7 @@ EXPORTED_SYMBOLS = (
     "hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join", "hg_flow_check_errors",
     "hg_lane_stream_id", "hg_event_synchronize",
     "hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format",
+    "hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

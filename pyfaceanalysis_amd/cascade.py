@@ -84,7 +84,13 @@ def tracked_windows(box, pipeline, subimage_size):
     """The nine windows of a frame that follows a found face (grid.tracked_boxes; the reference's ``track_single_face`` branch)
     with, per window, (max_Dx_diff, max_Dy_diff, base_side) — the layout ``frame_windows`` returns.  ``box``: (x0, y0, x1, y1) of the
     previous frame's first purged detection, in the coordinates of the prescaled frame.  What k_cascade_init_tracked writes on the
-    device, bit for bit (tests/test_tracking_gpu.py)."""
+    device, bit for bit (tests/test_tracking_gpu.py).  A (K, 4) array of boxes gives the concatenation of the per-box results, (9 K, 4)
+    and (9 K, 3): window 9 s + i is window i of box s, what k_cascade_init_tracked_multi writes (tests/test_multi_tracking_gpu.py)."""
+    if np.ndim(box) == 2:
+        parts = [tracked_windows(b, pipeline, subimage_size) for b in np.asarray(box, dtype=np.float64)]
+        if not parts:
+            return np.zeros((0, 4)), np.zeros((0, 3))
+        return np.concatenate([b for b, _ in parts]), np.concatenate([lv for _, lv in parts])
     p = dict(pipeline)
     sw, sh = subimage_size
     _, _, pw, ph, max_dx, max_dy = grid.tracked_positions(box, sw, sh, p["regression_width"], p["regression_height"], p["net_Dx"], p["net_Dy"])

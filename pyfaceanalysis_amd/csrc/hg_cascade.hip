@@ -24,7 +24,8 @@ void set_last_error(const std::string& s);
 void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
                      const double* conf, int64_t n, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st);
 void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts, hipStream_t st);
+                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts,
+                             const int32_t** row_src, const int32_t** kept_idx, hipStream_t st);
 void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts);
 int eyes_device(const hg_eyes* e);
 }
@@ -252,12 +253,10 @@ __global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coor
 // reference's operation order, no contraction (pragma above): equal to grid.tracked_boxes / cascade.tracked_windows and to the
 // reference's own outputs bit for bit (tests/golden/reference_tracking.npz).  One workgroup; writes what k_cascade_init_grid writes.
 constexpr int kTracked = 9;
-__global__ void k_cascade_init_tracked(hg_tracked_consts t, const double* __restrict__ face, double* __restrict__ orig_coords, double* __restrict__ orig_level,
-                                       double* __restrict__ coords, double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf,
-                                       int32_t* __restrict__ oidx, int32_t* __restrict__ count) {
-    const int i = threadIdx.x;
-    if (i == 0 && count) *count = kTracked;
-    if (i >= kTracked) return;
+// window i (0..8) of the face at face[0..3], written as row o of the outputs
+__device__ __forceinline__ void tracked_window(const hg_tracked_consts& t, const double* __restrict__ face, int i, int o, double* __restrict__ orig_coords,
+                                               double* __restrict__ orig_level, double* __restrict__ coords, double* __restrict__ angles,
+                                               double* __restrict__ neg, double* __restrict__ conf, int32_t* __restrict__ oidx) {
     const double fx0 = face[0], fy0 = face[1], fx1 = face[2], fy1 = face[3];
     const double face_size = d_add(d_mul(0.5, fabs(d_sub(fx1, fx0))), d_mul(0.5, fabs(d_sub(fy1, fy0))));      // :582
     const double s = d_div(d_mul(face_size, 1.0), t.subimage_width);                                                // :583
@@ -266,46 +265,92 @@ __global__ void k_cascade_init_tracked(hg_tracked_consts t, const double* __rest
     const int ix = i % 3;                                                                                                // y-major, three per row
     const double x0 = ix == 0 ? fx0 : (ix == 1 ? d_add(fx0, sepx) : d_sub(fx0, sepx)), y0 = fy0;                   // :622-623
     const double b[4] = {x0, y0, d_sub(d_add(x0, pw), 1.0), d_sub(d_add(y0, ph), 1.0)};                       // :668
-    for (int q = 0; q < 4; ++q) orig_coords[(size_t)i * 4 + q] = b[q];
-    orig_level[(size_t)i * 3] = d_div(d_mul(t.net_Dx, pw), t.regression_width);                                      // :650
-    orig_level[(size_t)i * 3 + 1] = d_div(d_mul(t.net_Dy, ph), t.regression_height);                                 // :651
-    orig_level[(size_t)i * 3 + 2] = __dsqrt_rn(d_add(d_mul(pw, pw), d_mul(ph, ph)));                            // FaceDetectUpdated.py:603-604
+    for (int q = 0; q < 4; ++q) orig_coords[(size_t)o * 4 + q] = b[q];
+    orig_level[(size_t)o * 3] = d_div(d_mul(t.net_Dx, pw), t.regression_width);                                      // :650
+    orig_level[(size_t)o * 3 + 1] = d_div(d_mul(t.net_Dy, ph), t.regression_height);                                 // :651
+    orig_level[(size_t)o * 3 + 2] = __dsqrt_rn(d_add(d_mul(pw, pw), d_mul(ph, ph)));                            // FaceDetectUpdated.py:603-604
     if (coords) {
-        for (int q = 0; q < 4; ++q) coords[(size_t)i * 4 + q] = b[q];
-        angles[i] = 0.0;
-        neg[i] = 0.0;
-        conf[i] = 0.0;
-        oidx[i] = i;
+        for (int q = 0; q < 4; ++q) coords[(size_t)o * 4 + q] = b[q];
+        angles[o] = 0.0;
+        neg[o] = 0.0;
+        conf[o] = 0.0;
+        oidx[o] = o;
     }
 }
 
-// The last kernel of a tracker's frame: row 0 of the purged rows becomes the tracked face (FaceDetectUpdated.py:1189-1195) — its box
-// goes into the tracker's device state, where the next frame's k_cascade_init_tracked reads it, with the found flag (a box that is
-// not finite is not carried) — and, for a tracked frame, everything the host needs goes to pinned memory: the kept rows, the two
-// counts, the flag, and last the sequence number the host waits for.  counts: {faces after the discard, faces after the purge}.
+__global__ void k_cascade_init_tracked(hg_tracked_consts t, const double* __restrict__ face, double* __restrict__ orig_coords, double* __restrict__ orig_level,
+                                       double* __restrict__ coords, double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf,
+                                       int32_t* __restrict__ oidx, int32_t* __restrict__ count) {
+    const int i = threadIdx.x;
+    if (i == 0 && count) *count = kTracked;
+    if (i >= kTracked) return;
+    tracked_window(t, face, i, i, orig_coords, orig_level, coords, angles, neg, conf, oidx);
+}
+
+// The same start for K held faces (what every tracker's frame launches; K = 1 under max_faces = 1): window 9 s + i is window i of face s, faces (K, 4) on the device in the
+// order the previous frame's hand-over carried them.  K is known on the host (the previous step's one wait fetched it), so the launch
+// holds 9 K windows exactly and the count word is 9 K: no filler row at the first stage.  Rows are independent, so the nine windows
+// of a face are the bits k_cascade_init_tracked writes for that face alone.
+__global__ void __launch_bounds__(64) k_cascade_init_tracked_multi(hg_tracked_consts t, const double* __restrict__ faces, int n_faces,
+                                                                   double* __restrict__ orig_coords, double* __restrict__ orig_level,
+                                                                   double* __restrict__ coords, double* __restrict__ angles, double* __restrict__ neg,
+                                                                   double* __restrict__ conf, int32_t* __restrict__ oidx, int32_t* __restrict__ count) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x, n = kTracked * n_faces;
+    if (o == 0 && count) *count = n;
+    if (o >= n) return;
+    const int s = o / kTracked;
+    tracked_window(t, faces + (size_t)s * 4, o - s * kTracked, o, orig_coords, orig_level, coords, angles, neg, conf, oidx);
+}
+
+// The last kernel of a tracker's frame: the purged rows become the tracked faces (FaceDetectUpdated.py:1189-1195, row 0 there).
+// Candidates are the first min(kept, max_faces) rows; those whose four box numbers are all finite are carried, in purge order, compacted
+// into the tracker's device state, where the next frame's k_cascade_init_tracked_multi reads them; the carried count goes beside them.
+// With max_faces = 1 that is row 0 or nothing.  For a tracked frame everything the host needs goes to pinned memory: the kept rows, the
+// two counts, the carried count, a slot per kept row and, last, the sequence number the host waits for.
+// counts: {faces after the discard, faces after the purge}.
+// slot[j]: the held face (index in the previous hand-over's carried order) whose nine windows kept row j came from — kept row -> the
+// assembled row it is (k_purge's kept[]) -> the cascade survivor that row was made from (k_eyes_glue) -> its original window / 9.  The
+// purge may append its first row a second time; both copies have the same kept[] entry, so the same slot.
 struct TrackerResults {
-    int32_t* words;      // pinned: {kept, before the purge, found, sequence number}; null: no read-back (the host has the rows already)
+    int32_t* words;      // pinned: {kept, before the purge, carried, sequence number}; null: no read-back (the host has the rows already)
     double* rows;        // pinned: [cap][10]
+    int32_t* slots;      // pinned: [cap]
     int32_t cap;
 };
-__global__ void __launch_bounds__(128) k_tracker_handover(const double* __restrict__ purged, const int32_t* __restrict__ counts, double* __restrict__ box,
-                                                          int32_t* __restrict__ found, TrackerResults R, int seq) {
+struct SlotChain {
+    const int32_t *kept_idx, *row_src, *oidx;
+};
+constexpr int kMaxFaces = 64;      // one wave's ballot compacts the candidates; 576 windows stay inside k_cascade_group's single-workgroup path
+__global__ void __launch_bounds__(128) k_tracker_handover(const double* __restrict__ purged, const int32_t* __restrict__ counts, double* __restrict__ boxes,
+                                                          int32_t* __restrict__ held, int max_faces, SlotChain S, TrackerResults R, int seq) {
+    __shared__ int carried_s;
     const int tid = threadIdx.x;
     const int kept = counts[1];
-    bool ok = kept > 0;
-    if (ok)
-        for (int q = 0; q < 4; ++q) ok = ok && isfinite(purged[q]);
-    if (ok && tid < 4) box[tid] = purged[tid];
-    if (tid == 0) *found = ok ? 1 : 0;
+    const int ncand = kept < max_faces ? kept : max_faces;
+    if (tid < 64) {      // the first wave: max_faces <= 64
+        bool ok = tid < ncand;
+        if (ok)
+            for (int q = 0; q < 4; ++q) ok = ok && isfinite(purged[(size_t)tid * 10 + q]);
+        const unsigned long long m = __ballot(ok ? 1 : 0);
+        if (ok) {
+            const int pos = __popcll(m & ((1ull << tid) - 1ull));
+            for (int q = 0; q < 4; ++q) boxes[(size_t)pos * 4 + q] = purged[(size_t)tid * 10 + q];
+        }
+        if (tid == 0) {
+            carried_s = __popcll(m);
+            *held = carried_s;
+        }
+    }
     if (!R.words) return;
     const int nrow = kept < R.cap ? kept : R.cap;
     for (int q = tid; q < nrow * 10; q += blockDim.x) R.rows[q] = purged[q];
+    for (int j = tid; j < nrow; j += blockDim.x) R.slots[j] = S.oidx[S.row_src[S.kept_idx[j]]] / kTracked;
     __threadfence_system();
     __syncthreads();
     if (tid == 0) {
         R.words[0] = kept;
         R.words[1] = counts[0];
-        R.words[2] = ok ? 1 : 0;
+        R.words[2] = carried_s;
         __threadfence_system();
         __hip_atomic_store(R.words + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -738,8 +783,9 @@ uint64_t key_of(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
     return h ? h : 1;
 }
 
-// A TRACKED frame (`B`): the windows are the nine of k_cascade_init_tracked, built from the box at B->face_dev, and the candidate
-// count never visits the host.  Nine bounds it from the start, so every launch of every group is sized by nine and the glue kernels
+// A TRACKED frame (`B`): the windows are the nine of k_cascade_init_tracked per held face (k_cascade_init_tracked_multi), built from the
+// B->n_faces boxes at B->face_dev, and the candidate count never visits the host.  n0 = 9 * n_faces bounds it from the start (nine in the
+// text below: one face), so every launch of every group is sized by that bound and the glue kernels
 // take the live count from the device word they already carry (A.count_in under A.n_max); no poll_count runs, stage_counts is -1
 // throughout, and nothing is copied out: the survivors stay in coords[*final_buf] ..., their count in *B->final_count, for the eye
 // step (eyes_frame_tail_bounded).  Rows between the live count and the bound: k_cascade_group gives them a defined window and
@@ -748,7 +794,8 @@ uint64_t key_of(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
 // any byte is a pixel, rows are independent, and the next glue launch skips them by the count.  A live count of 0 is a normal
 // case: every later launch runs on nine filler rows and compacts none.
 struct Bounded {
-    const double* face_dev;
+    const double* face_dev;      // (n_faces, 4)
+    int n_faces;
     hg_tracked_consts tc;
     const int32_t* final_count;      // out
 };
@@ -769,7 +816,8 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
     if (n0 > 0 && (!frame_dev || (!T && !B && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
     // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
     if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
-    if (B && (n0 != kTracked || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
+    // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
+    if (B && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
     set_dev(c->device);
     hipStream_t st = (hipStream_t)stream;
     const int ns = (int)c->stages.size();
@@ -781,8 +829,8 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
     }
     c->reserve(n0);
     if (B) {
-        hipLaunchKernelGGL(k_cascade_init_tracked, 1, 64, 0, st, B->tc, B->face_dev, (double*)c->orig_coords.p, (double*)c->orig_level.p,
-                           (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
+        hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)((n0 + 63) / 64), 64, 0, st, B->tc, B->face_dev, B->n_faces, (double*)c->orig_coords.p,
+                           (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
                            (int32_t*)c->count.p);
     } else if (T) {
         hipLaunchKernelGGL(k_cascade_init_grid, (unsigned)((n0 + 255) / 256), 256, 0, st, *T, (double*)c->orig_coords.p, (double*)c->orig_level.p,
@@ -899,7 +947,7 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         const bool want_count = !B && (any_disc || last);      // a tracked frame: the bound sizes the launches, nothing is read back
         const int32_t seq = want_count ? ++c->seq : 0;
         HostResults Hk{};
-        if (n_bound > 2 * kChunk) {      // many frames' windows: one workgroup per kChunk candidates, two launches
+        if (n_bound > 2 * kChunk) {      // many frames' windows (never a tracked frame: no pad_to here, and 9 * kMaxFaces is far below): one workgroup per kChunk candidates, two launches
             const unsigned chunks = (unsigned)((n_bound + kChunk - 1) / kChunk);
             c->chunk_count.alloc((size_t)chunks * kMaxGroup * 4);
             hipLaunchKernelGGL(k_cascade_group_mark, chunks, 1024, 0, st, G, c->base, A, c->cap, (int32_t*)c->chunk_count.p);
@@ -1081,19 +1129,21 @@ int hg_cascade_grid_device(int device, const hg_cascade_level* levels, int n_lev
 
 }  // extern "C"
 
-// ---- tracking one face across a frame stream (include/higsfa.h) ---------------------------------------------------------------
+// ---- tracking faces across a frame stream (include/higsfa.h) --------------------------------------------------------------------
 struct hg_tracker {
     hg_cascade* c = nullptr;
     hg_eyes* e = nullptr;
     hg_tracked_consts tc{};
-    hg::DevBuf state;                // device: tracked box (4 doubles), then the found flag (int32)
-    bool found = false;              // host mirror of the flag: decides which path the next step takes
-    int w = 0, h = 0;                // prescaled frame size the box belongs to
-    char* host_res = nullptr;        // pinned: words {kept, before the purge, found, sequence number} at 0, rows at 64
+    int max_faces = 1, rescan_every = 0;
+    hg::DevBuf state;                // device: the held boxes (max_faces x 4 doubles), then the carried count (int32)
+    int held = 0;                    // host mirror of the carried count: decides which path the next step takes and sizes it
+    int tracked_run = 0;             // consecutive tracked steps since the last full-grid step (rescan_every)
+    int w = 0, h = 0;                // prescaled frame size the boxes belong to
+    char* host_res = nullptr;        // pinned: words {kept, before the purge, carried, sequence number} at 0, rows at 64, slots behind the rows
     int32_t seq = 0;
-    static constexpr int kRows = kTracked + 1;      // the purge may keep n + 1 rows
+    int rows_cap() const { return kTracked * max_faces + 1; }      // the purge may keep n + 1 rows
     double* box_dev() const { return (double*)state.p; }
-    int32_t* found_dev() const { return (int32_t*)((char*)state.p + 32); }
+    int32_t* held_dev() const { return (int32_t*)((char*)state.p + (size_t)max_faces * 32); }
 };
 
 namespace {
@@ -1101,6 +1151,128 @@ void check_finite_consts(const hg_tracked_consts& t) {
     const double v[6] = {t.subimage_width, t.subimage_height, t.regression_width, t.regression_height, t.net_Dx, t.net_Dy};
     for (double x : v)
         if (!(x > 0.0) || !std::isfinite(x)) hg::fail(HG_ERR_ARG, "tracked-grid constants must be positive and finite");
+}
+
+void tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int max_faces, int rescan_every, hg_tracker** out) {
+    if (!out) hg::fail(HG_ERR_ARG, "null output handle pointer");
+    *out = nullptr;
+    // the two numbers first: refused before any handle is looked at
+    if (max_faces < 1 || max_faces > kMaxFaces) hg::fail(HG_ERR_ARG, "max_faces %d outside 1..%d", max_faces, kMaxFaces);
+    if (rescan_every < 0) hg::fail(HG_ERR_ARG, "negative rescan_every %d", rescan_every);
+    if (!c || !e || !consts) hg::fail(HG_ERR_ARG, "null argument");
+    check_finite_consts(*consts);
+    if (consts->subimage_width != (double)c->w || consts->subimage_height != (double)c->h)
+        hg::fail(HG_ERR_ARG, "tracked-grid sub-image %g x %g, the cascade's is %d x %d", consts->subimage_width, consts->subimage_height, c->w, c->h);
+    if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+    set_dev(c->device);
+    auto t = std::make_unique<hg_tracker>();
+    t->c = c;
+    t->e = e;
+    t->tc = *consts;
+    t->max_faces = max_faces;
+    t->rescan_every = rescan_every;
+    const size_t state_bytes = (size_t)max_faces * 32 + 16;
+    t->state.alloc(state_bytes);
+    HG_HIP(hipMemset(t->state.p, 0, state_bytes));
+    HG_HIP(hipHostMalloc((void**)&t->host_res, 64 + (size_t)t->rows_cap() * 84, hipHostMallocDefault));
+    memset(t->host_res, 0, 64);
+    *out = t.release();
+}
+
+void tracker_step(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels,
+                  int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed,
+                  int* used_tracked_grid, int32_t* slots, int* n_held, void* stream) {
+    if (!t || !n_out) hg::fail(HG_ERR_ARG, "null argument");
+    if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+    hg_cascade* c = t->c;
+    hg_eyes* e = t->e;
+    hipStream_t st = (hipStream_t)stream;
+    *n_out = 0;
+    if (n_before_purge) *n_before_purge = 0;
+    if (used_tracked_grid) *used_tracked_grid = 0;
+    const void* fr;
+    int fh, fw;
+    int64_t fld;
+    prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
+    if (t->held && (fw != t->w || fh != t->h)) t->held = 0;      // the boxes mean nothing on another frame size
+    if (n_held) *n_held = t->held;
+    int64_t n = 0;
+    int cur = 0;
+    const double* purged = nullptr;
+    const int32_t* counts = nullptr;
+    // the path rule, on the host: nothing held (a size change drops every box), or rescan_every tracked steps in a row behind us
+    if (!t->held || (t->rescan_every > 0 && t->tracked_run >= t->rescan_every)) {
+        // what hg_cascade_detect_faces_frame_device runs, then the first rows (if any) become the tracked faces
+        const LevelTable T = make_level_table(levels, n_levels);
+        const int64_t n0 = T.first[T.n_levels];
+        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
+        hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
+                            out_rows, out_cap, n_out, n_before_purge, st);
+        int carried = 0;      // the hand-over's rule, on the rows the host has already
+        for (int64_t j = 0; j < *n_out && j < t->max_faces; ++j) {
+            bool ok = true;
+            for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(out_rows[j * 10 + q]);
+            carried += ok ? 1 : 0;
+        }
+        if (carried) {      // the boxes go from the purge's device rows into the tracker's state, in stream order before the next frame
+            hg::eyes_tail_buffers(e, &purged, &counts);
+            hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->held_dev(), t->max_faces, SlotChain{}, TrackerResults{}, 0);
+            HG_HIP(hipGetLastError());
+        } else {
+            HG_HIP(hipMemsetAsync(t->held_dev(), 0, 4, st));
+        }
+        t->held = carried;
+        t->tracked_run = 0;
+        t->w = fw;
+        t->h = fh;
+        for (int64_t j = 0; slots && j < *n_out; ++j) slots[j] = -1;      // no held face stands behind a row of the full grid
+        if (n_held) *n_held = carried;
+        return;
+    }
+    // the tracked frame: everything enqueued back to back, one wait at the end
+    if (used_tracked_grid) *used_tracked_grid = 1;
+    const int64_t n0 = (int64_t)kTracked * t->held;
+    Bounded B{};
+    B.face_dev = t->box_dev();
+    B.n_faces = t->held;
+    B.tc = t->tc;
+    detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, nullptr, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur, &B);
+    SlotChain S{};
+    hg::eyes_frame_tail_bounded(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n0,
+                                B.final_count, &purged, &counts, &S.row_src, &S.kept_idx, st);
+    S.oidx = (const int32_t*)c->oidx[cur].p;
+    TrackerResults R{};
+    R.words = (int32_t*)t->host_res;
+    R.rows = (double*)(t->host_res + 64);
+    R.cap = t->rows_cap();
+    R.slots = (int32_t*)(t->host_res + 64 + (size_t)R.cap * 80);
+    const int32_t seq = ++t->seq;
+    hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->held_dev(), t->max_faces, S, R, seq);
+    HG_HIP(hipGetLastError());
+    // the one wait: the sequence word is polled (a stream synchronisation costs 20-40 us more, see publish_count); a deadline guards
+    // against a device that never answers
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; __atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) != seq; ++spins) {
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+            HG_HIP(hipStreamSynchronize(st));
+            if (__atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) == seq) break;
+            t->held = 0;
+            hg::fail(HG_ERR_DEVICE, "tracked frame did not report its result");
+        }
+        __builtin_ia32_pause();
+    }
+    const int64_t kept = R.words[0];
+    if (n_before_purge) *n_before_purge = R.words[1];
+    t->held = R.words[2];
+    ++t->tracked_run;
+    if (n_held) *n_held = t->held;      // the hand-over has happened whatever follows
+    if (kept > out_cap || kept > R.cap) hg::fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)std::min<int64_t>(out_cap, R.cap));
+    if (kept > 0) {
+        if (!out_rows) hg::fail(HG_ERR_ARG, "null output rows");
+        memcpy(out_rows, R.rows, (size_t)kept * 80);
+        if (slots) memcpy(slots, R.slots, (size_t)kept * 4);
+    }
+    *n_out = kept;
 }
 }  // namespace
 
@@ -1117,26 +1289,26 @@ int hg_cascade_tracked_grid_device(int device, const hg_tracked_consts* consts, 
     });
 }
 
-int hg_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, hg_tracker** out) {
+int hg_cascade_tracked_grid_multi_device(int device, const hg_tracked_consts* consts, const double* faces_dev, int n_faces, double* boxes_dev,
+                                         double* level_dev, void* stream) {
     return guarded([&] {
-        if (!out) hg::fail(HG_ERR_ARG, "null output handle pointer");
-        *out = nullptr;
-        if (!c || !e || !consts) hg::fail(HG_ERR_ARG, "null argument");
+        if (!consts || !faces_dev || !boxes_dev || !level_dev) hg::fail(HG_ERR_ARG, "null argument");
+        if (n_faces < 1 || n_faces > 0x7fffffff / kTracked / 4) hg::fail(HG_ERR_ARG, "bad face count %d", n_faces);
         check_finite_consts(*consts);
-        if (consts->subimage_width != (double)c->w || consts->subimage_height != (double)c->h)
-            hg::fail(HG_ERR_ARG, "tracked-grid sub-image %g x %g, the cascade's is %d x %d", consts->subimage_width, consts->subimage_height, c->w, c->h);
-        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
-        set_dev(c->device);
-        auto t = std::make_unique<hg_tracker>();
-        t->c = c;
-        t->e = e;
-        t->tc = *consts;
-        t->state.alloc(48);
-        HG_HIP(hipMemset(t->state.p, 0, 48));
-        HG_HIP(hipHostMalloc((void**)&t->host_res, 64 + (size_t)hg_tracker::kRows * 80, hipHostMallocDefault));
-        memset(t->host_res, 0, 64);
-        *out = t.release();
+        set_dev(device);
+        hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)(((int64_t)kTracked * n_faces + 63) / 64), 64, 0, (hipStream_t)stream, *consts, faces_dev,
+                           n_faces, boxes_dev, level_dev, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (int32_t*)nullptr,
+                           (int32_t*)nullptr);
+        HG_HIP(hipGetLastError());
     });
+}
+
+int hg_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, hg_tracker** out) {
+    return guarded([&] { tracker_create(c, e, consts, 1, 0, out); });
+}
+
+int hg_tracker_create_multi(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int max_faces, int rescan_every, hg_tracker** out) {
+    return guarded([&] { tracker_create(c, e, consts, max_faces, rescan_every, out); });
 }
 
 void hg_tracker_free(hg_tracker* t) {
@@ -1149,8 +1321,9 @@ int hg_tracker_reset(hg_tracker* t) {
     return guarded([&] {
         if (!t) hg::fail(HG_ERR_ARG, "null tracker handle");
         set_dev(t->c->device);
-        HG_HIP(hipMemset(t->found_dev(), 0, 4));      // steps are synchronous: nothing of this tracker is in flight
-        t->found = false;
+        HG_HIP(hipMemset(t->held_dev(), 0, 4));      // steps are synchronous: nothing of this tracker is in flight
+        t->held = 0;
+        t->tracked_run = 0;
         t->w = t->h = 0;
     });
 }
@@ -1159,81 +1332,18 @@ int hg_tracker_step_frame_device(hg_tracker* t, const void* frame_dev, int frame
                                  const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge,
                                  int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid, void* stream) {
     return guarded([&] {
-        if (!t || !n_out) hg::fail(HG_ERR_ARG, "null argument");
-        if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
-        hg_cascade* c = t->c;
-        hg_eyes* e = t->e;
-        hipStream_t st = (hipStream_t)stream;
-        *n_out = 0;
-        if (n_before_purge) *n_before_purge = 0;
-        if (used_tracked_grid) *used_tracked_grid = 0;
-        const void* fr;
-        int fh, fw;
-        int64_t fld;
-        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
-        if (t->found && (fw != t->w || fh != t->h)) t->found = false;      // the box means nothing on another frame size
-        int64_t n = 0;
-        int cur = 0;
-        const double* purged = nullptr;
-        const int32_t* counts = nullptr;
-        if (!t->found) {
-            // what hg_cascade_detect_faces_frame_device runs, then row 0 (if any) becomes the tracked face
-            const LevelTable T = make_level_table(levels, n_levels);
-            const int64_t n0 = T.first[T.n_levels];
-            detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
-            hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
-                                out_rows, out_cap, n_out, n_before_purge, st);
-            bool ok = *n_out > 0;
-            for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(out_rows[q]);
-            if (ok) {      // the box goes from the purge's device rows into the tracker's state, in stream order before the next frame
-                hg::eyes_tail_buffers(e, &purged, &counts);
-                hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->found_dev(), TrackerResults{}, 0);
-                HG_HIP(hipGetLastError());
-            } else {
-                HG_HIP(hipMemsetAsync(t->found_dev(), 0, 4, st));
-            }
-            t->found = ok;
-            t->w = fw;
-            t->h = fh;
-            return;
-        }
-        // the tracked frame: everything enqueued back to back, one wait at the end
-        if (used_tracked_grid) *used_tracked_grid = 1;
-        Bounded B{};
-        B.face_dev = t->box_dev();
-        B.tc = t->tc;
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, nullptr, kTracked, nullptr, nullptr, nullptr, nullptr, kTracked, &n, stage_counts, rows_executed,
-                    stream, &cur, &B);
-        hg::eyes_frame_tail_bounded(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p,
-                                    kTracked, B.final_count, &purged, &counts, st);
-        TrackerResults R{};
-        R.words = (int32_t*)t->host_res;
-        R.rows = (double*)(t->host_res + 64);
-        R.cap = hg_tracker::kRows;
-        const int32_t seq = ++t->seq;
-        hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->found_dev(), R, seq);
-        HG_HIP(hipGetLastError());
-        // the one wait: the sequence word is polled (a stream synchronisation costs 20-40 us more, see publish_count); a deadline guards
-        // against a device that never answers
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; __atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) != seq; ++spins) {
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                HG_HIP(hipStreamSynchronize(st));
-                if (__atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) == seq) break;
-                t->found = false;
-                hg::fail(HG_ERR_DEVICE, "tracked frame did not report its result");
-            }
-            __builtin_ia32_pause();
-        }
-        const int64_t kept = R.words[0];
-        if (n_before_purge) *n_before_purge = R.words[1];
-        t->found = R.words[2] != 0;
-        if (kept > out_cap || kept > R.cap) hg::fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)std::min<int64_t>(out_cap, R.cap));
-        if (kept > 0) {
-            if (!out_rows) hg::fail(HG_ERR_ARG, "null output rows");
-            memcpy(out_rows, R.rows, (size_t)kept * 80);
-        }
-        *n_out = kept;
+        tracker_step(t, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_rows, out_cap, n_out, n_before_purge, stage_counts,
+                     rows_executed, used_tracked_grid, nullptr, nullptr, stream);
+    });
+}
+
+int hg_tracker_step_frame_multi_device(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h,
+                                       const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int64_t* n_out,
+                                       int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid, int32_t* slots,
+                                       int* n_held, void* stream) {
+    return guarded([&] {
+        tracker_step(t, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_rows, out_cap, n_out, n_before_purge, stage_counts,
+                     rows_executed, used_tracked_grid, slots, n_held, stream);
     });
 }
 

@@ -38,6 +38,7 @@ struct hg_eyes {
     int filter = HG_FILTER_NEAREST;      // of the eye patches (hg_eyes_set_interpolation)
     int64_t cap = 0;       // faces the buffers hold
     hg::DevBuf eboxes, dang, pu8, pf32, sl, sl2, reg, ecoords, toofar, rows, purged, scratch, count;
+    hg::DevBuf row_src, kept_idx;        // a tracker's slots: the face of every assembled row, the assembled row of every kept row
     int32_t* host_words = nullptr;       // pinned: {faces after the discard, faces after the purge}
 
     void reserve(int64_t n) {
@@ -55,6 +56,8 @@ struct hg_eyes {
         rows.alloc((size_t)n * 80);
         purged.alloc((size_t)(n + 1) * 80);
         scratch.alloc((size_t)(n + 1) * 16);
+        row_src.alloc((size_t)n * 4);
+        kept_idx.alloc((size_t)(n + 1) * 4);
         count.alloc(16);
         if (hg_flow_reserve(fx, 2 * n) != HG_OK || (fy != fx && hg_flow_reserve(fy, 2 * n) != HG_OK)) hg::fail(HG_ERR_NOMEM, "%s", hg_last_error());
         cap = n;
@@ -179,10 +182,11 @@ __device__ __forceinline__ void shift_eye(const double* b, double rx, double ry,
 // (FaceDetectUpdated.py:1010-1017; k_cascade_compact's ballot scan, one workgroup over chunks of its size) and the 10-column rows
 // (:1036-1041).  reg: [0, 2n) EyeLX, [reg_stride, reg_stride + 2n) EyeLY; row i left eye, n + i right eye.  Every output may be null.
 // n_dev (nullable): only the first min(*n_dev, n) faces exist (k_eye_boxes); the layout stays that of n faces.
+// row_src (nullable): row_src[j] = the face i that assembled row j was made from (what a tracker's slots are composed of).
 __global__ void __launch_bounds__(1024) k_eyes_glue(int64_t n, const int32_t* __restrict__ n_dev, hg_eye_consts c, const double* __restrict__ boxes, const double* __restrict__ angles,
                                                     const double* __restrict__ conf, const double* __restrict__ eboxes, const double* __restrict__ reg,
                                                     int64_t reg_stride, double* __restrict__ ecoords, uint8_t* __restrict__ toofar,
-                                                    double* __restrict__ rows, int32_t* __restrict__ count) {
+                                                    double* __restrict__ rows, int32_t* __restrict__ count, int32_t* __restrict__ row_src) {
     __shared__ int wsum[16];
     __shared__ int base;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -217,6 +221,7 @@ __global__ void __launch_bounds__(1024) k_eyes_glue(int64_t n, const int32_t* __
             for (int q = 0; q < 4; ++q) r[5 + q] = e[q];
             r[9] = conf[i];
         }
+        if (keep && row_src) row_src[off + before] = (int32_t)i;
         __syncthreads();
         if (tid == 0) {
             int t = 0;
@@ -251,9 +256,10 @@ __device__ __forceinline__ double rel_error(const double* a, const double* e) {
 }
 
 // rows (n_max, 10); n = min(*n_dev, n_max) when n_dev is given.  scratch: w (n doubles), then perm (n int32) and kept (n + 1 int32).
-// out: room for n + 1 rows; *count = rows written.
+// out: room for n + 1 rows; *count = rows written.  kept_out (nullable, n_max + 1 entries): the index in `rows` of every row written.
 __global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows, int64_t n_max, const int32_t* __restrict__ n_dev,
-                                                double* __restrict__ out, int32_t* __restrict__ count, char* __restrict__ scratch) {
+                                                double* __restrict__ out, int32_t* __restrict__ count, char* __restrict__ scratch,
+                                                int32_t* __restrict__ kept_out) {
     __shared__ double tile[1024];
     __shared__ double redv[16];
     __shared__ int redf[16];
@@ -262,6 +268,7 @@ __global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows,
     const int64_t n = (n_dev && *n_dev < n_max) ? (int64_t)*n_dev : n_max;
     if (n <= 1) {                       // :219-220: a copy
         for (int64_t q = tid; q < n * 10; q += blockDim.x) out[q] = rows[q];
+        if (tid == 0 && n == 1 && kept_out) kept_out[0] = 0;
         if (tid == 0) *count = (int32_t)n;
         return;
     }
@@ -339,11 +346,14 @@ __global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows,
     }
     const int nk = nk_s;
     for (int64_t q = tid; q < (int64_t)nk * 10; q += blockDim.x) out[q] = rows[(int64_t)kept[q / 10] * 10 + q % 10];
+    if (kept_out)
+        for (int q = tid; q < nk; q += blockDim.x) kept_out[q] = kept[q];
     if (tid == 0) *count = nk;
 }
 
-void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, double* out, int32_t* count, void* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(k_purge, 1, 1024, 0, st, rows, n_max, n_dev, out, count, (char*)scratch);
+void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, double* out, int32_t* count, void* scratch, hipStream_t st,
+                  int32_t* kept_out = nullptr) {
+    hipLaunchKernelGGL(k_purge, 1, 1024, 0, st, rows, n_max, n_dev, out, count, (char*)scratch, kept_out);
     HG_HIP(hipGetLastError());
 }
 
@@ -353,7 +363,7 @@ void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, doubl
 // step and the networks read defined data in all 2n rows, and k_eyes_glue assembles the live faces only.
 void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles, const double* conf,
               int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st,
-              const int32_t* n_dev = nullptr) {
+              const int32_t* n_dev = nullptr, int32_t* row_src = nullptr) {
     if (n == 0) {
         if (count) HG_HIP(hipMemsetAsync(count, 0, 4, st));
         return;
@@ -383,7 +393,7 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
     }
     hipLaunchKernelGGL(k_eyes_glue, 1, 1024, 0, st, n, n_dev, c, boxes, angles, conf, (const double*)e->eboxes.p, (const double*)rg, n2, ecoords, toofar,
-                       rows, count);
+                       rows, count, row_src);
     HG_HIP(hipGetLastError());
 }
 
@@ -420,15 +430,21 @@ void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w
 // eye step, the discard, the rows and the purge are enqueued and NOTHING is read back — the caller's last kernel fetches what the host
 // needs.  *purged: the kept rows (room for n_bound + 1); *counts: {faces after the discard, faces after the purge}, both on the device.
 // A live count of 0 runs through every launch: k_eyes_glue and k_purge then write counts of 0.
+// *row_src / *kept_idx: for every assembled row the survivor it was made from, for every kept row the assembled row it is (a tracker's
+// slots, k_tracker_handover).
 void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts, hipStream_t st) {
+                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts,
+                             const int32_t** row_src, const int32_t** kept_idx, hipStream_t st) {
     if (!e || !n_dev || n_bound < 1) fail(HG_ERR_ARG, "bad bounded eye step");
     e->reserve(n_bound);      // before any workspace pointer is taken (see eyes_frame_tail)
     eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n_bound, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st,
-             n_dev);
-    launch_purge((const double*)e->rows.p, n_bound, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st);
+             n_dev, (int32_t*)e->row_src.p);
+    launch_purge((const double*)e->rows.p, n_bound, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st,
+                 (int32_t*)e->kept_idx.p);
     *purged = (const double*)e->purged.p;
     *counts = (const int32_t*)e->count.p;
+    *row_src = (const int32_t*)e->row_src.p;
+    *kept_idx = (const int32_t*)e->kept_idx.p;
 }
 
 // What the tracker's hand-over kernel reads after an ordinary frame's tail (eyes_frame_tail with n > 0): the same two buffers.

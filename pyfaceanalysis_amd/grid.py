@@ -101,7 +101,11 @@ def tracked_positions(box, subimage_width, subimage_height, regression_width, re
 def tracked_boxes(box, subimage_width=None, subimage_height=None, regression_width=None, regression_height=None, net_Dx=None, net_Dy=None):
     """(9, 4) windows of a tracked frame: the product of posX and posY (face_analysis.py:661-669), y-major — the three distinct
     boxes (x, y0, x + pw - 1, y0 + ph - 1), three times over, because posY holds the same value three times.  The duplicates reach
-    the purge as they do in the reference.  Constants default to ``FACE_PIPELINE``'s."""
+    the purge as they do in the reference.  Constants default to ``FACE_PIPELINE``'s.  A (K, 4) array of boxes gives (9 K, 4): the nine
+    windows of box 0, then those of box 1, ... (the grid of a tracker that holds several faces)."""
+    if np.ndim(box) == 2:
+        return np.concatenate([tracked_boxes(b, subimage_width, subimage_height, regression_width, regression_height, net_Dx, net_Dy)
+                               for b in np.asarray(box, dtype=np.float64)] or [np.zeros((0, 4))])
     p = FACE_PIPELINE
     sw = p["subimage_width"] if subimage_width is None else subimage_width
     sh = p["subimage_height"] if subimage_height is None else subimage_height

@@ -1,4 +1,4 @@
-"""Tracking one face across a stream of frames: the reference's ``track_single_face`` mode on the device.
+"""Tracking faces across a stream of frames: the reference's ``track_single_face`` mode on the device, and the same for several faces.
 
 Once a frame has produced a face, its first purged detection is carried over (FaceDetectUpdated.py:1189-1195); the next frame then
 searches nine windows around that box instead of the whole pyramid — one sampling value from the box's size (face_analysis.py:576-585),
@@ -7,6 +7,11 @@ grid.  ``FaceTracker`` holds that state in the library (include/higsfa.h ``hg_tr
 purge writes it, the next frame's grid kernel reads it — and a tracked frame is enqueued as a whole, every launch sized by the bound 9,
 with one host wait at the end.  ``grid.tracked_boxes`` / ``cascade.tracked_windows`` are the host restatement of the
 nine windows.
+
+Several faces (``max_faces`` > 1): the first ``max_faces`` purged detections with a finite box are carried, in purge order, and a
+tracked frame searches the nine windows of EVERY held face in one pooled pass — 9 K windows under the bound 9 K, one purge over the
+union of their rows, one host wait.  Every returned row names the held face it came from (``slots``).  ``rescan_every`` = R sends
+every R-th + 1 step back to the full grid, where new faces can enter (include/higsfa.h ``hg_tracker_create_multi``).
 """
 from __future__ import annotations
 
@@ -17,42 +22,62 @@ import numpy as np
 from . import _capi, grid
 from .cascade import frame_levels
 
-N_TRACKED = 9          # windows of a tracked frame: 3 posX values x 3 (equal) posY values
+N_TRACKED = 9          # windows of a tracked frame per held face: 3 posX values x 3 (equal) posY values
+MAX_FACES = 64         # the library's cap (hg_tracker_create_multi)
+
+
+def tracked_consts(cascade):
+    """``hg_tracked_consts`` of a ``DeviceCascade``: its sub-image size and its pipeline's regression size and separations."""
+    p = cascade.pipeline
+    tc = _capi.HgTrackedConsts()
+    tc.subimage_width, tc.subimage_height = cascade.w, cascade.h
+    tc.regression_width, tc.regression_height = p["regression_width"], p["regression_height"]
+    tc.net_Dx, tc.net_Dy = p["net_Dx"], p["net_Dy"]
+    return tc
 
 
 class FaceTracker(object):
-    """One face followed through a stream of frames, on ``cascade`` (a ``DeviceCascade``) and ``eyes`` (an ``EyeLocator``) of one device.
-    Both stay owned by the caller and must outlive the tracker; while the tracker is in use they serve one stream at a time (a
-    ``detect_faces`` between two steps is fine, one in flight during a step is not)."""
+    """Up to ``max_faces`` faces (1..64) followed through a stream of frames, on ``cascade`` (a ``DeviceCascade``) and ``eyes`` (an
+    ``EyeLocator``) of one device.  Both stay owned by the caller and must outlive the tracker; while the tracker is in use they serve
+    one stream at a time (a ``detect_faces`` between two steps is fine, one in flight during a step is not).  ``rescan_every`` = R > 0:
+    after R consecutive tracked steps the next step searches the full grid again (0: only when every face is lost, as the reference)."""
 
-    def __init__(self, cascade, eyes, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+    def __init__(self, cascade, eyes, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE, max_faces=1, rescan_every=0):
+        self.max_faces, self.rescan_every = int(max_faces), int(rescan_every)
+        self._multi = self.max_faces != 1 or self.rescan_every != 0      # the defaults: hg_tracker_create and today's dict
         if eyes.device != cascade.device:
             raise ValueError("eye locator on device %d, cascade on device %d" % (eyes.device, cascade.device))
         self.cascade, self.eyes = cascade, eyes
         self.smallest_face, self.prescale_size = float(smallest_face), int(prescale_size or 0)
         self.torch = cascade.torch
         self._plans = {}       # frame size -> everything a step needs that depends on the size alone
-        self._box = None
+        self._boxes = np.zeros((0, 4))
         self._h = None
-        p = cascade.pipeline
-        tc = _capi.HgTrackedConsts()
-        tc.subimage_width, tc.subimage_height = cascade.w, cascade.h
-        tc.regression_width, tc.regression_height = p["regression_width"], p["regression_height"]
-        tc.net_Dx, tc.net_Dy = p["net_Dx"], p["net_Dy"]
+        tc = tracked_consts(cascade)
         h = C.c_void_p()
-        _capi.check(_capi.lib().hg_tracker_create(cascade._handle(), eyes._handle(), C.byref(tc), C.byref(h)))
+        if self._multi:
+            _capi.check(_capi.lib().hg_tracker_create_multi(cascade._handle(), eyes._handle(), C.byref(tc), self.max_faces, self.rescan_every, C.byref(h)))
+        else:
+            _capi.check(_capi.lib().hg_tracker_create(cascade._handle(), eyes._handle(), C.byref(tc), C.byref(h)))
         self._h = h
 
     @property
     def tracked_face(self):
-        """Host copy of the tracked box (x0, y0, x1, y1), in the coordinates of the prescaled frame it was found on, or None."""
-        return None if self._box is None else self._box.copy()
+        """Host copy of the first tracked box (x0, y0, x1, y1), in the coordinates of the prescaled frame it was found on, or None."""
+        return self._boxes[0].copy() if len(self._boxes) else None
+
+    @property
+    def tracked_faces(self):
+        """Host copy of the held boxes, (n_held, 4) in carried order — the order ``slots`` of the next step refers to — or (0, 4)."""
+        return self._boxes.copy()
 
     def step(self, frame):
         """One frame of the stream ((H, W) uint8 tensor on the device, contiguous rows — or a colour frame of the cascade's
         ``frame_format``; checked on every call).  Returns faces (m, 10)
-        as ``DeviceCascade.detect_faces``, tracked (this frame used the nine-window grid), n_windows (9 then, else the grid's count),
-        n_before_purge, counts (-1 throughout on a tracked frame: no count left the device) and rows_executed."""
+        as ``DeviceCascade.detect_faces``, tracked (this frame used the nine-window grid), n_windows (9 per held face then, else the
+        grid's count), n_before_purge, counts (-1 throughout on a tracked frame: no count left the device) and rows_executed.  With
+        ``max_faces`` > 1 or ``rescan_every`` > 0 also slots (int32, one per face row: the held face — index into ``tracked_faces``
+        as it was BEFORE this step — whose windows produced the row; -1 on a full-grid step) and n_held (faces carried to the next step)."""
         if self._h is None:
             raise RuntimeError("tracker is closed")
         t, L, dc = self.torch, _capi.lib(), self.cascade
@@ -63,33 +88,44 @@ class FaceTracker(object):
             pw, ph = grid.prescaled_size(fw, fh, self.prescale_size) if self.prescale_size else (fw, fh)
             pre = (pw, ph) if (pw, ph) != (fw, fh) else (0, 0)
             levels, n_levels, n0 = frame_levels(pw, ph, self.smallest_face, dc.pipeline, (dc.w, dc.h))
-            rows, counts = np.empty((max(n0, N_TRACKED) + 1, 10)), np.zeros(len(dc.stages), dtype=np.int32)      # the purge may keep n + 1 rows
-            plan = self._plans[(fw, fh)] = (pre, levels, n_levels, n0, rows, counts)
-        pre, levels, n_levels, n0, rows, counts = plan
-        n_out, n_before, n_rows, used = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+            n_rows_max = max(n0, N_TRACKED * self.max_faces) + 1      # the purge may keep n + 1 rows
+            rows, counts = np.empty((n_rows_max, 10)), np.zeros(len(dc.stages), dtype=np.int32)
+            plan = self._plans[(fw, fh)] = (pre, levels, n_levels, n0, rows, counts, np.empty(n_rows_max, dtype=np.int32))
+        pre, levels, n_levels, n0, rows, counts, slots = plan
+        n_out, n_before, n_rows, used, n_held = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+        held_before = len(self._boxes)
+        head = (self._h, frame.data_ptr(), fh, fw, frame.stride(0), pre[0], pre[1], levels, n_levels, rows.ctypes.data_as(C.c_void_p), len(rows),
+                C.byref(n_out), C.byref(n_before), counts.ctypes.data_as(C.c_void_p), C.byref(n_rows), C.byref(used))
+        stream = t.cuda.current_stream(dc.dev).cuda_stream
         try:
-            _capi.check(L.hg_tracker_step_frame_device(
-                self._h, frame.data_ptr(), fh, fw, frame.stride(0), pre[0], pre[1], levels, n_levels, rows.ctypes.data_as(C.c_void_p), len(rows),
-                C.byref(n_out), C.byref(n_before), counts.ctypes.data_as(C.c_void_p), C.byref(n_rows), C.byref(used),
-                t.cuda.current_stream(dc.dev).cuda_stream))
+            if self._multi:
+                _capi.check(L.hg_tracker_step_frame_multi_device(*(head + (slots.ctypes.data_as(C.c_void_p), C.byref(n_held), stream))))
+            else:
+                _capi.check(L.hg_tracker_step_frame_device(*(head + (stream,))))
         except Exception:
             self.reset()
             raise
         faces = rows[:n_out.value].copy()
-        # the library's rule (hg_tracker_step_frame_device): row 0's box is carried if there is a row and the box is finite
-        self._box = faces[0, :4].copy() if len(faces) and np.isfinite(faces[0, :4]).all() else None
+        # the library's rule (k_tracker_handover): of the first max_faces rows those with a finite box are carried, in order
+        cand = faces[:self.max_faces, :4]
+        self._boxes = cand[np.isfinite(cand).all(axis=1)].copy()
         tracked = bool(used.value)
-        return dict(faces=faces, tracked=tracked, n_windows=N_TRACKED if tracked else n0, n_before_purge=n_before.value,
-                    counts=counts.tolist(), rows_executed=n_rows.value)
+        res = dict(faces=faces, tracked=tracked, n_windows=N_TRACKED * held_before if tracked else n0, n_before_purge=n_before.value,
+                   counts=counts.tolist(), rows_executed=n_rows.value)
+        if self._multi:
+            if n_held.value != len(self._boxes):
+                raise RuntimeError("tracker holds %d faces, the rows say %d" % (n_held.value, len(self._boxes)))
+            res["slots"], res["n_held"] = slots[:n_out.value].copy(), n_held.value
+        return res
 
     def reset(self):
         """Forget the tracked face: the next step searches the full grid."""
         if self._h is not None:
             _capi.check(_capi.lib().hg_tracker_reset(self._h))
-        self._box = None
+        self._boxes = np.zeros((0, 4))
 
     def close(self):
         if self._h is not None:
             _capi.lib().hg_tracker_free(self._h)
             self._h = None
-        self._box = None
+        self._boxes = np.zeros((0, 4))
