@@ -315,6 +315,57 @@ int hg_patcher_extract_format_device(hg_patcher* p, int frame_format, const void
                                      const double* boxes_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype,
                                      int64_t ldo, void* stream);
 
+/* --- Antialiased resize: PIL's Image.resize((w, h), filter) ------------------------------------------------------------------
+ * The prescale of every frame path is im.resize((w, h), Image.NEAREST) (FaceDetectUpdated.py:551-556): point sampling, which aliases; the
+ * reference's author left the alternatives in a comment on that line and makes the display copy with BILINEAR (:559).  These entries
+ * are Pillow's resize for 8-bit images (ImagingResample, Resample.c), bit for bit (tested against PIL).
+ * enum hg_resample and enum hg_filter are DIFFERENT OPERATIONS that share PIL's codes: hg_filter is transform(EXTENT, filter), which
+ * samples a fixed 2 x 2 / 4 x 4 neighbourhood of each source point (right for windows); hg_resample is a separable convolution whose
+ * support grows with the shrink factor — that growth is the antialiasing.  On a 192 x 108 -> 100 x 56 noise image the two differ in
+ * 5534 of 5600 pixels.  The rule, per axis that changes size (in -> out pixels; doubles, every operation rounded on its own):
+ *   filters   BOX (support S = 0.5) 1 for -0.5 < x <= 0.5; BILINEAR (1) 1 - |x|; HAMMING (1) sinc(x) (0.54f + 0.46f cos(pi x)), the two
+ *             constants being floats as Pillow writes them; BICUBIC (2) a = -0.5; LANCZOS (3) sinc(x) sinc(x / 3) for -3 <= x < 3
+ *   tables    scale = in / out, fs = max(scale, 1), support = S fs, ksize = (int)ceil(support) * 2 + 1; for output pixel xx:
+ *             center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), xmax = min((int)(center + support + 0.5), in) - xmin,
+ *             w[x] = f((x + xmin - center + 0.5) / fs) for x < xmax, normalised by their running sum when that is not 0,
+ *             k[x] = (int)(w[x] 2^22 -+ 0.5) (sin / cos: the host's libm, the one PIL calls on that machine)
+ *   one pass  out[xx] = clip8((2^21 + sum_{x < xmax} in[xmin + x] k[x]) >> 22), int32, arithmetic shift, clamped to 0..255
+ * The horizontal pass runs first (if the width changes) into a uint8 image, the vertical pass reads that (if the height changes); an
+ * axis that keeps its size gets no pass.  Image.resize's own exception is kept: a very tall image (h > 100 w) whose height shrinks has
+ * its height resized first, at full width, and its width afterwards.  out_format is HG_FRAME_L or the source's own format:
+ *   grey output from a colour source   convert("L") of every source pixel read, then the passes (im.convert("L").resize(...), the
+ *                                      reference's order, :543 then :556; the other order gives other bytes)
+ *   colour output                      band by band with the same tables; the four-byte formats as RGBX, all four bytes (Pillow
+ *                                      premultiplies mode "RGBA" proper before a filtered resize: not offered)
+ * HG_RESAMPLE_NEAREST with grey output is the whole-frame gather the prescale has always used (hg_patcher_extract_format_device over
+ * the box (0, 0, w, h)): the same bytes as before; with colour output it is refused.  Not offered: Pillow's box= and reducing_gap=.
+ * HG_ERR_ARG with a message, before anything is launched or written: an unknown filter or format, an out_format that is neither
+ * HG_FRAME_L nor the source's, null pointers, sizes <= 0, ld_bytes < w * bytes per pixel, dst_ld_bytes < out_w * bytes per output pixel,
+ * NEAREST with colour output, source and destination whose byte ranges overlap, and an axis whose tables (out * (ksize + 2) int32)
+ * exceed HG_RESAMPLE_MAX_TABLE_BYTES. */
+enum hg_resample {
+    HG_RESAMPLE_NEAREST = 0, HG_RESAMPLE_LANCZOS = 1, HG_RESAMPLE_BILINEAR = 2, HG_RESAMPLE_BICUBIC = 3, HG_RESAMPLE_BOX = 4, HG_RESAMPLE_HAMMING = 5
+};
+#define HG_RESAMPLE_MAX_TABLE_BYTES (64 << 20)
+/* The rule on the host, plain C++, no device involved: src is h rows of w pixels of `format`, ld_bytes apart; dst out_h rows of out_w
+ * pixels of out_format, dst_ld_bytes apart. */
+int hg_frame_resize_host(int filter, const void* src, int format, int h, int w, int64_t ld_bytes, int out_format, void* dst, int out_h,
+                         int out_w, int64_t dst_ld_bytes);
+/* The same on the patcher's device, enqueued on `stream`, no host wait.  Rows may start at any byte; no load touches a byte outside
+ * [row start, row start + w * bytes per pixel).  The patcher keeps the uploaded tables of the eight most recently used (in, out, filter) axes and the
+ * intermediate image; both grow on demand, so from the second frame of a size a call uploads and allocates nothing.  ONE STREAM PER
+ * PATCHER, as for the keyed tables above.  A MISS IS A HOST WAIT: the tables of an axis the patcher does not hold are computed on the
+ * host, and when they replace another axis' (the least recently used of eight) the call first waits for the calling stream; so is an
+ * intermediate that has to grow.  A caller that alternates more than four (size, filter) pairs through one patcher pays that on every
+ * call — inside hg_cascade_detect_frame_device and the tracker steps too, when a filter is set and frame sizes rotate.
+ * Two launches (horizontal, then vertical; the horizontal pass writes only the source rows the vertical pass reads), or ONE where both
+ * axes change and a 64 x 16 output tile's intermediate rows fit the kernel's 16 KB of LDS: the same bytes.  Which sources and filters take the
+ * one launch by default follows the measurement (hg_resample.hip, kFusedDefault).  flags: bit 0 forces the two launches, bit 1 the one
+ * launch where it is eligible (both for tests and A/B runs; not both at once); other bits must be 0.  Rows of at most 2^28 pixels;
+ * NEAREST writes at most 4096 x 4096 pixels (the window gather's limit). */
+int hg_patcher_resize_device(hg_patcher* p, int filter, int flags, const void* src_dev, int format, int h, int w, int64_t ld_bytes,
+                             int out_format, void* dst_dev, int out_h, int out_w, int64_t dst_ld_bytes, void* stream);
+
 /* --- Cascade glue on the device (the reference's stage loop between two hot calls) -----------------
  * update_current_subimage_coordinates (face_analysis.py:803-840) + identify_patches_to_discard (:842-887) for n
  * candidates from their regression outputs, then the boolean-mask compaction of FaceDetectUpdated.py:739-759 as
@@ -370,7 +421,7 @@ void hg_cascade_free(hg_cascade* c);
  * interpolation_formats[network_serial], FaceDetectUpdated.py:125, :671, :686.  HG_ERR_ARG (and nothing changed) if a stage's
  * serial is >= n or a code is unknown.  Before the first call every stage is NEAREST.  A stage that skips its extraction (the stage
  * before it is a Disc stage, or it has no network, :674-684) reuses the previous patches: its entry has no effect, as in the
- * reference.  The prescale stays NEAREST (:551-561).  Takes effect from the next detect / step call on this handle; setting it
+ * reference.  The prescale is not a stage: it keeps its own filter (hg_cascade_set_prescale_filter; NEAREST until set, :551-561).  Takes effect from the next detect / step call on this handle; setting it
  * while a call on this handle is in flight on another thread or stream is the caller's error. */
 int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n);
 /* The format of the frames handed to this cascade (HG_FRAME_*; HG_FRAME_L until set).  Afterwards frame_dev / ld of
@@ -382,6 +433,12 @@ int hg_cascade_set_interpolation(hg_cascade* c, const int32_t* filters, int n);
  * tracker — reads that grey frame.  May be called between frames, like hg_cascade_set_interpolation; HG_ERR_ARG (and nothing
  * changed) for an unknown format. */
 int hg_cascade_set_frame_format(hg_cascade* c, int format);
+/* The filter of the prescale (enum hg_resample — NOT enum hg_filter; HG_RESAMPLE_NEAREST until set): with any other filter the prescale of
+ * hg_cascade_detect_frame_device, hg_cascade_detect_faces_frame_device and both tracker steps is hg_patcher_resize_device on the cascade's
+ * patcher — im.convert("L").resize((w, h), filter) — into the same cascade-owned grey buffer; the grid, the stage loop, the eye step and the
+ * tracker read that frame as before.  A handle never given a filter, or set back to NEAREST, runs exactly the launches it always ran.
+ * May be called between frames, like hg_cascade_set_interpolation; HG_ERR_ARG (and nothing changed) for an unknown code. */
+int hg_cascade_set_prescale_filter(hg_cascade* c, int filter);
 /* frame_dev: (frame_h, frame_w) uint8 on the device, row stride ld >= frame_w (a pitched buffer, a crop of a larger frame); this
  * and every entry below that reads a frame returns HG_ERR_ARG for ld < frame_w before it launches or writes anything; boxes_host (n0, 4) / level_host (n0, 3): the first-stage
  * windows and their level constants.  Outputs (host, room for out_cap detections): final coordinates, angles, index of the

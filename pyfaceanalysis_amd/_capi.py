@@ -12,16 +12,19 @@ HG_OK = 0
 HG_ERR_ARG, HG_ERR_FORMAT, HG_ERR_DIM, HG_ERR_DEVICE, HG_ERR_NOMEM, HG_ERR_STATE = -1, -2, -3, -4, -5, -6
 HG_PLAN_GENERIC, HG_PLAN_FUSED = 0, 1
 HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC = 0, 2, 3      # enum hg_filter: PIL's own codes (Image.NEAREST / BILINEAR / BICUBIC)
+# enum hg_resample: PIL's codes again, but a DIFFERENT operation (Image.resize, not Image.transform): frames.resize, the cascade's prescale
+HG_RESAMPLE_NEAREST, HG_RESAMPLE_LANCZOS, HG_RESAMPLE_BILINEAR, HG_RESAMPLE_BICUBIC, HG_RESAMPLE_BOX, HG_RESAMPLE_HAMMING = 0, 1, 2, 3, 4, 5
 HG_FRAME_L, HG_FRAME_RGB, HG_FRAME_BGR, HG_FRAME_RGBA, HG_FRAME_BGRA = 0, 1, 2, 3, 4      # frame formats (pyfaceanalysis_amd/frames.py)
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
 _ENTRIES_SINCE_COLOR = ("hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format")
 _ENTRIES_SINCE_MULTI_TRACKING = ("hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device")
+_ENTRIES_SINCE_RESIZE = ("hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter")
 _lib = None
 
 
@@ -137,6 +140,9 @@ def lib():
         "hg_frame_to_gray_host": (C.c_int, [vp, i32, i32, i32, i64, vp, i64]),
         "hg_patcher_extract_format_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, i32, i32, vp, i32, i64, vp]),
         "hg_cascade_set_frame_format": (C.c_int, [vp, i32]),
+        "hg_frame_resize_host": (C.c_int, [i32, vp, i32, i32, i32, i64, i32, vp, i32, i32, i64]),
+        "hg_patcher_resize_device": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i64, i32, vp, i32, i32, i64, vp]),
+        "hg_cascade_set_prescale_filter": (C.c_int, [vp, i32]),
         "hg_eyes_set_interpolation": (C.c_int, [vp, i32]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
@@ -174,7 +180,7 @@ def lib():
         except AttributeError:
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
-            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING and os.environ.get("HIGSFA_LIB"):
+            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -200,6 +206,7 @@ EXPORTED_SYMBOLS = (
     "hg_lane_stream_id", "hg_event_synchronize",
     "hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format",
     "hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device",
+    "hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

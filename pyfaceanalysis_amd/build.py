@@ -12,10 +12,12 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhigsfa.so")
-SOURCES = ["hg_tree.cpp", "hg_capi.cpp", "hg_hostpack.cpp", "hg_generic.hip", "hg_fused_plan.cpp", "hg_fused.hip", "hg_fused_front.hip", "hg_fused_igsfa.hip", "hg_fused_prod.hip", "hg_fused_tail.hip",
-           "hg_gauss.hip", "hg_extract.hip", "hg_cascade.hip", "hg_eyes.hip", "hg_train.hip"]
+SOURCES = ["hg_tree.cpp", "hg_capi.cpp", "hg_hostpack.cpp", "hg_resample.cpp", "hg_generic.hip", "hg_fused_plan.cpp", "hg_fused.hip", "hg_fused_front.hip", "hg_fused_igsfa.hip", "hg_fused_prod.hip", "hg_fused_tail.hip",
+           "hg_gauss.hip", "hg_extract.hip", "hg_resample.hip", "hg_cascade.hip", "hg_eyes.hip", "hg_train.hip"]
 HEADERS = ["hg_common.hpp", os.path.join("..", "..", "include", "higsfa.h")]
-HOST_ONLY = {"hg_hostpack.cpp"}      # no HIP in them: built with g++ (function multiversioning, which the device pass rejects)
+# no HIP in them: built with g++ (function multiversioning, which the device pass rejects), with these extra flags.  hg_resample.cpp
+# restates Pillow's coefficient arithmetic in doubles: no contraction (and it uses no multiversioning: one body per function)
+HOST_ONLY = {"hg_hostpack.cpp": [], "hg_resample.cpp": ["-ffp-contract=off"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-result"]
@@ -67,7 +69,7 @@ def build(force=False, verbose=False):
         objs.append(op)
         if force or _newer(sp, op) or any(_newer(h, op) for h in hdr_paths):
             if src in HOST_ONLY:
-                cmd = [CXX, "-O3", "-std=c++17", "-fPIC", "-Wall", "-c", sp, "-o", op]
+                cmd = [CXX, "-O3", "-std=c++17", "-fPIC", "-Wall"] + HOST_ONLY[src] + ["-c", sp, "-o", op]
             else:
                 cmd = [HIPCC] + FLAGS + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", sp, "-o", op]
             if verbose:

@@ -99,15 +99,19 @@ def tracked_windows(box, pipeline, subimage_size):
 
 
 class DeviceCascade(object):
-    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0, interpolation_formats=None, frame_format="L"):
+    def __init__(self, stages, subimage_size, n_features, pipeline=None, device=0, interpolation_formats=None, frame_format="L",
+                 prescale_filter="NEAREST"):
         """interpolation_formats: the filter of every stage's extraction, a sequence indexed by the stage's serial like
         ``CUT_OFFS_FACE`` (FaceDetectUpdated.py:125, :671; PIL's codes 0 / 2 / 3); None: NEAREST everywhere.  The prescale is
-        NEAREST whatever this says (:551-561).  frame_format: the format of the frames ``detect``, ``detect_frame``, ``detect_faces``
+        not a stage: prescale_filter (``frames.RESAMPLE``: a name or PIL's code) is the filter of ``Image.resize`` in front of every
+        frame path — ``detect_frame``, ``detect_faces``, ``prescale`` and a ``FaceTracker`` on this cascade; "NEAREST" is the
+        reference's (:551-561), the others are PIL's antialiased resize of the grey frame, bit for bit.  frame_format: the format of the frames ``detect``, ``detect_frame``, ``detect_faces``
         and ``prescale`` are given ("L", "RGB", "BGR", "RGBA", "BGRA": frames.py); a colour frame is converted as PIL's
         ``convert("L")`` does (:541-543) inside the library, and everything behind that reads the grey frame."""
         import torch
         self.torch = torch
         self.frame_format = frames.format_code(frame_format)
+        self.prescale_filter = frames.resample_code(prescale_filter)
         self.stages = list(stages)
         self.w, self.h = int(subimage_size[0]), int(subimage_size[1])
         self.k = int(n_features)              # feature columns kept per candidate (>= every classifier's input_dim)
@@ -164,7 +168,16 @@ class DeviceCascade(object):
             _capi.check(L.hg_cascade_set_interpolation(h, fmt, len(self.interpolation_formats)))
         if self.frame_format != _capi.HG_FRAME_L:
             _capi.check(L.hg_cascade_set_frame_format(h, self.frame_format))
+        if self.prescale_filter != _capi.HG_RESAMPLE_NEAREST:
+            _capi.check(L.hg_cascade_set_prescale_filter(h, self.prescale_filter))
         return h
+
+    def set_prescale_filter(self, prescale_filter):
+        """Change the prescale's filter from the next frame on (hg_cascade_set_prescale_filter): between two frames, never during one."""
+        code = frames.resample_code(prescale_filter)
+        if self._h is not None:
+            _capi.check(_capi.lib().hg_cascade_set_prescale_filter(self._h, code))
+        self.prescale_filter = code
 
     def set_frame_format(self, frame_format):
         """Change the format of the frames given from now on (hg_cascade_set_frame_format): between two frames, never during one."""
@@ -177,7 +190,7 @@ class DeviceCascade(object):
         frames.check_color_frame(self.torch, frame, self.frame_format, self.dev)
 
     def prescale(self, frame, prescale_size=grid.PRESCALE_SIZE):
-        """FaceDetectUpdated.py:551-556: shrink so that the larger side is <= prescale_size, ``Image.resize(NEAREST)`` —
+        """FaceDetectUpdated.py:551-556: shrink so that the larger side is <= prescale_size, ``Image.resize(prescale_filter)``; NEAREST —
         PIL's nearest resize is the EXTENT rule over the whole frame, so the patcher does it (bit-exact vs PIL in the tests).
         A grey frame that needs no shrinking is returned as it is.  Otherwise the returned tensor lives with the cascade, one per
         (frame size, prescaled size): it is valid until the next ``prescale()`` with the same frame size and the same prescaled
@@ -201,6 +214,8 @@ class DeviceCascade(object):
             self._prescale[key] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
                                    t.empty((ph, pw), dtype=t.uint8, device=self.dev))
         whole, small = self._prescale[key]
+        if self.prescale_filter != _capi.HG_RESAMPLE_NEAREST:      # PIL's antialiased resize of the grey frame (frames.resize)
+            return frames.resize(frame, (pw, ph), self.prescale_filter, self.frame_format, out=small, patcher=self.patcher)
         if self.frame_format == _capi.HG_FRAME_L:
             self.patcher.extract_device(frame.data_ptr(), np.uint8, fh, fw, frame.stride(0), whole.data_ptr(), 1, (pw, ph), small.data_ptr(),
                                         np.uint8, pw * ph, stream=stream)

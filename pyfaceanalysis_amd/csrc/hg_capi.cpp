@@ -17,6 +17,7 @@
 
 #include "hg_common.hpp"
 #include "hg_hostpipe.hpp"
+#include "hg_resample.hpp"
 
 namespace {
 
@@ -644,6 +645,21 @@ extern "C" {
 int hg_version(void) { return HG_VERSION; }
 
 const char* hg_last_error(void) { return g_last_error.c_str(); }
+
+// PIL's filtered resize on the host: the rule itself is plain C++ in hg_resample.cpp
+int hg_frame_resize_host(int filter, const void* src, int format, int h, int w, int64_t ld_bytes, int out_format, void* dst, int out_h, int out_w,
+                         int64_t dst_ld_bytes) {
+    const char* why = nullptr;
+    try {
+        why = hg::frame_resize_host(filter, src, format, h, w, ld_bytes, out_format, dst, out_h, out_w, dst_ld_bytes);
+    } catch (const std::bad_alloc&) {
+        hg::set_last_error("resize: out of host memory");
+        return HG_ERR_NOMEM;
+    }
+    if (!why) return HG_OK;
+    hg::set_last_error(why);
+    return HG_ERR_ARG;
+}
 
 // PIL's "L" conversion on the host: the rule itself is plain C++ in hg_hostpack.cpp
 int hg_frame_to_gray_host(const void* src, int format, int frame_h, int frame_w, int64_t ld_bytes, uint8_t* dst, int64_t dst_ld) {

@@ -665,6 +665,7 @@ struct hg_cascade {
     int pre_src_w = 0, pre_src_h = 0;    // ... the frame size pre_box was written for
     int frame_format = HG_FRAME_L;       // hg_cascade_set_frame_format: how frame_dev / ld of the detect entries are read
     hg::DevBuf gray_frame;               // a colour frame that is not prescaled, converted (grows on demand, like pre_frame)
+    int prescale_filter = HG_RESAMPLE_NEAREST;      // hg_cascade_set_prescale_filter (enum hg_resample)
     int32_t* host_count = nullptr;       // pinned, device-visible: {count, sequence number} (publish_count)
     int32_t seq = 0;                     // sequence number of the last read-back asked for
     char* host_res = nullptr;            // pinned: the final survivors (HostResults), kResCap rows
@@ -742,6 +743,15 @@ int hg_cascade_set_frame_format(hg_cascade* c, int format) {
         if (!c) hg::fail(HG_ERR_ARG, "null cascade handle");
         if (!hg::frame_bpp(format)) hg::fail(HG_ERR_ARG, "unknown frame format %d (0 L, 1 RGB, 2 BGR, 3 RGBA, 4 BGRA)", format);
         c->frame_format = format;
+    });
+}
+
+int hg_cascade_set_prescale_filter(hg_cascade* c, int filter) {
+    return guarded([&] {
+        if (!c) hg::fail(HG_ERR_ARG, "null cascade handle");
+        if (filter < HG_RESAMPLE_NEAREST || filter > HG_RESAMPLE_HAMMING)
+            hg::fail(HG_ERR_ARG, "unknown resize filter %d (0 NEAREST, 1 LANCZOS, 2 BILINEAR, 3 BICUBIC, 4 BOX, 5 HAMMING)", filter);
+        c->prescale_filter = filter;
     });
 }
 
@@ -1034,6 +1044,16 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
             c->pre_src_h = frame_h;
         }
         c->pre_frame.alloc((size_t)prescale_w * prescale_h);
+        if (c->prescale_filter != HG_RESAMPLE_NEAREST) {      // im.convert("L").resize((w, h), filter): PIL's antialiased resize (hg_resample.hip)
+            const int rc = hg_patcher_resize_device(c->patcher, c->prescale_filter, 0, frame_dev, c->frame_format, frame_h, frame_w, ld, HG_FRAME_L,
+                                                    c->pre_frame.p, prescale_h, prescale_w, prescale_w, stream);
+            if (rc != HG_OK) hg::fail(rc, "%s", hg_last_error());
+            fr = c->pre_frame.p;
+            fh = prescale_h;
+            fw = prescale_w;
+            fld = prescale_w;
+            return;
+        }
         const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
         if (hg::patcher_extract_format(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), c->frame_format, frame_dev, frame_h, frame_w, ld,
                                        (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8, (int64_t)prescale_w * prescale_h,

@@ -179,4 +179,10 @@ int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_d
 int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,
                            int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
 
+// hg_resample.hip: PIL's filtered resize (hg_patcher_resize_device).  Its state hangs off the patcher (hg_extract.hip keeps the pointer and
+// frees it with the handle through resample_state_free).
+void resample_state_free(void* state);
+void*& patcher_resample_state(hg_patcher* p);
+int patcher_device(const hg_patcher* p);
+
 }  // namespace hg

@@ -49,6 +49,8 @@ struct hg_patcher {
     hg::DevBuf ftabs, frot;     // BILINEAR / BICUBIC: coordinate tables and rotation matrices of unkeyed calls
     Keyed keyed[4];
     int keyed_next = 0;
+    void* resample = nullptr;   // hg_patcher_resize_device: the tables and the intermediate image (hg_resample.hip owns and frees it)
+    ~hg_patcher() { hg::resample_state_free(resample); }
 };
 
 namespace hg { void set_last_error(const std::string& s); }
@@ -976,6 +978,9 @@ int hg_patcher_extract(hg_patcher* p, const void* frame, int frame_dtype, int fr
 }  // extern "C"
 
 namespace hg {
+void*& patcher_resample_state(hg_patcher* p) { return p->resample; }
+int patcher_device(const hg_patcher* p) { return p->device; }
+
 // NEAREST, unrotated windows from a frame of any format (hg_patcher_extract_format_device; key as for patcher_extract: the cascade's
 // prescale passes the key of its whole-frame box, whose tables a grey and a colour frame of one size share)
 int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,
