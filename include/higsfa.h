@@ -64,7 +64,7 @@ typedef struct hg_info {
     int32_t device;           /* HIP device ordinal, -1 while host-only                        */
     int64_t weight_bytes;     /* device bytes held by weights/descriptors                      */
     int64_t flops_per_row;    /* algorithmic FLOPs per sub-image: sum 2*in*out over affines    */
-    int64_t padded_flops_per_row; /* FLOPs the fused MFMA tiling actually issues per row       */
+    int64_t padded_flops_per_row; /* FLOPs the fused MFMA tiling issues per row, every layer with its own first affine (hoisted links issue fewer: hg_flow_describe) */
     int64_t workspace_bytes;  /* device bytes currently reserved for activations              */
 } hg_info;
 

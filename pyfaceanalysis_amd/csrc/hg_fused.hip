@@ -368,7 +368,7 @@ __global__ void __launch_bounds__(256) k_stage_splitm(StageParams P, int mt1n, i
     if (P.has_exp && w < mt2n) {
 #pragma unroll
         for (int k = 0; k < KB; ++k)
-            if (k < k2n) a2[k] = wnode[((size_t)P.kb1 * mt1n + (size_t)k * mt2n + w) * 64];
+            if (k < k2n) a2[k] = wnode[((size_t)(P.sum_in ? 0 : P.kb1 * mt1n) + (size_t)k * mt2n + w) * 64];
     }
     // Remainder tiles (P.a4x4: the stage's last tile of both affines is stored in 4x4 form, hg_fused_dev.hpp): the wave that owns
     // that tile multiplies with v_mfma_f32_4x4x1 into d4 and folds the four partial sums afterwards — the same products in the
@@ -381,6 +381,25 @@ __global__ void __launch_bounds__(256) k_stage_splitm(StageParams P, int mt1n, i
         const f32x4 bb = *(const f32x4*)(bnode + w * 16);
 #pragma unroll
         for (int t = 0; t < T; ++t) z[t] = bb;
+        if (P.sum_in) {
+            // hoisted first affine (StageParams::sum_in): z tile w = ((bias + child 0's tile w) + child 1's) + ...; all blocks requested first
+            int on[KB];
+            f32x4 bf[KB][T];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                const bool real = k < P.n_kids;
+                const int2 e = kt[(real ? k : 0) * mt1n + w];
+                on[k] = real ? e.y : 0;
+#pragma unroll
+                for (int t = 0; t < T; ++t) bf[k][t] = P.in[(size_t)(trow[t] + (uint32_t)e.x) * 64 + lane];
+            }
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (on[k]) {
+#pragma unroll
+                    for (int t = 0; t < T; ++t) z[t] += bf[k][t];
+                }
+        } else
         for (int k0 = 0; k0 < P.kb1; k0 += KB) {
             // the whole batch of K-block entries first (scalar loads that do not wait for one another; the table has 8 spare
             // entries behind the last node), then every weight / input block of the batch, then the MFMAs
@@ -623,7 +642,7 @@ public:
         for (auto& s : plan_->stages) t += (int64_t)(s.afrag.size() + s.bias.size()) * 4;
         return t;
     }
-    int64_t padded_flops_per_row() const override { return plan_->padded_flops; }
+    int64_t padded_flops_per_row() const override { return plan_->padded_flops_given; }      // (the hoisted plan's own count: describe())
     int64_t workspace_bytes() const override {      // every lane's
         int64_t t = 0;
         for (int l = 0; l < n_lanes_; ++l) t += (int64_t)(lanes_[l].bufA.bytes + lanes_[l].bufB.bytes);
@@ -864,6 +883,8 @@ private:
         R.pack_in = hs.pack_in;
         R.pack_slot = (const int32_t*)d.pack_slot.p;
         R.a4x4 = hs.rem4 ? 1 : 0;
+        R.sum_in = hs.sum_in ? 1 : 0;
+        R.n_kids = hs.n_kids;
         for (int fi = 0; fi < hs.nf; ++fi) {
             R.funcp |= (uint32_t)hs.funcs[fi].kind << (4 * fi);
             R.expo[fi] = (float)hs.funcs[fi].expo;
@@ -1110,7 +1131,7 @@ private:
     // an ordinary layer on k_stage: node groups whose weights sit in LDS, swept over the batch's tile groups
     void launch_stage(const HostStage& s, StageParams& P, int n_tiles, int si, hipStream_t st) {
         // node groups sized so a group's weights are ~64 KiB of LDS (always >= 1 node)
-        const int npg = std::max(1, std::min(s.n_nodes, kWeightLdsKiB / std::max(1, s.node_blocks)));
+        const int npg = std::max(1, std::min(s.n_nodes, (s.sum_in ? plan_->opt.sum_lds_kib : kWeightLdsKiB) / std::max(1, s.node_blocks)));
         const int n_groups = (s.n_nodes + npg - 1) / npg;
         static const int shapes[][2] = {{8, 2}, {8, 1}, {4, 2}, {4, 1}};      // 8 x 1 before 4 x 2 (layer 7: 20.6 -> 19.0 us)
         const Shape sh = sweep_shape(shapes, n_tiles, n_groups);
@@ -1123,6 +1144,7 @@ private:
         // other shape of this call (one tile per wave: small batches) takes the generic remainder-tile loop, which tests per block
         StageFn fn = s.pk_kbi >= 0 ? (kbf == 3 ? pick_stage(s.mt1, s.mt2, T, s.rem4, kbf, fs, s.pk_kbi) : nullptr) : pick_stage(s.mt1, s.mt2, T, s.rem4, kbf, fs);
         if (!fn) fn = pick_stage(s.mt1, s.mt2, T, s.rem4, 0, false);
+        if (s.sum_in) fn = pick_stage_sum(s.mt1, s.mt2, T, fs);      // hoisted first affine: hg_fused_sum.hip
         const int tile_parts = sweep_tile_parts(n_groups, tile_groups, resident_blocks(fn, nw * 64, lds_bytes));
         P.nodes_per_group = npg;
         P.nodes_per_wg = npg;
@@ -1134,7 +1156,7 @@ private:
         if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
 #ifdef HIGSFA_DIAG
         const bool stamp_kbf3 = s.mt1 == 3 && s.mt2 == 3 && T == 2 && s.rem4 && kbf == 3;
-        if (plan_->opt.stamp_stage == si && (stamp_kbf3 || (s.mt1 == s.mt2 && (s.mt1 == 4 || s.mt1 == 3) && T == 2 && !s.rem4 && kbf == 0))) {
+        if (plan_->opt.stamp_stage == si && !s.sum_in && (stamp_kbf3 || (s.mt1 == s.mt2 && (s.mt1 == 4 || s.mt1 == 3) && T == 2 && !s.rem4 && kbf == 0))) {
             // diagnostic instantiation with s_memtime stamps (never used in timed runs)
             fn = stamp_kbf3 ? (StageFn)k_stage<3, 3, 2, true, true, 3> : s.mt1 == 4 ? (StageFn)k_stage<4, 4, 2, true> : (StageFn)k_stage<3, 3, 2, true>;
             stamps_begin(P, (int)blocks, 8, st);
@@ -1308,6 +1330,8 @@ private:
         S.mto = hs.mto;
         S.mt1 = hs.mt1;
         S.mt2 = hs.mt2;
+        S.sum_in = hs.sum_in ? 1 : 0;
+        S.n_kids = hs.n_kids;
         for (int fi = 0; fi < hs.nf; ++fi) {
             S.funcp |= (uint32_t)hs.funcs[fi].kind << (4 * fi);
             S.expo[fi] = (float)hs.funcs[fi].expo;
@@ -1376,7 +1400,9 @@ private:
 }  // namespace
 
 std::unique_ptr<Executor> make_fused_executor(const TNode& root, std::string* why_not) {
-    auto plan = fused::build_fused_plan(root, fused::FusedOptions::from_env(), why_not);
+    fused::FusedOptions opt = fused::FusedOptions::from_env();
+    opt.hoist = getenv("HIGSFA_NO_HOIST") == nullptr;      // (an executor's switch, not the planner's: DESIGN.md §9)
+    auto plan = fused::build_fused_plan(root, opt, why_not);
     if (!plan) return nullptr;
     return std::make_unique<FusedExecutor>(std::move(plan));
 }

@@ -74,6 +74,10 @@ struct StageParams {
     int32_t* err;       // host-visible error word: a bounded poll that ran out writes here (checked by the host at the next call)
     int32_t whatif;     // diagnostic build only (HIGSFA_WHATIF): bit 0 = k_stage reads every input block from the tile's first block (cache-hot),
                         // bit 1 = node_tail stores nothing — timing experiments, results are wrong
+    // Hoisted link (HostStage::sum_in): the layer below already multiplied by this layer's first affine.  No A1 fragments (afrag = A2 only);
+    // kb1tab lists the children's tiles child-major, kb1 = n_kids x MT1, entry i feeds z tile i % MT1, .y = 1 (real) or 0 (padding, last);
+    // z[mt] = ((bias + child 0's tile) + child 1's tile) + ... in table order, in every kernel that runs such a layer.
+    int32_t sum_in, n_kids;
 };
 
 __device__ __forceinline__ unsigned long long stamp_now() {
@@ -293,7 +297,9 @@ __device__ __forceinline__ float* packed_slot_ptr(const StageParams& P, int tile
 // wA2 / b2 point at this node's A2 fragments (+lane) and bias-2 fragment; address space (LDS or
 // global) is resolved after inlining.
 // FS: the expansion is (identity, |x|^p) and known at compile time (as in the front kernel): no function loop, no kind branches.
-template <int MT1, int MT2, int T, bool REM = false, bool FS = false, typename WP, typename BP>
+// LEAN (with FS): m-tile-outer GEMMs and no fragment prefetch — 28 registers fewer, for callers that hold prefetched input blocks across this
+// call (k_stage_sum); the same MFMAs in the same order per accumulator.
+template <int MT1, int MT2, int T, bool REM = false, bool FS = false, bool LEAN = false, typename WP, typename BP>
 __device__ __forceinline__ void node_tail(const StageParams& P, WP wA2, BP b2, int node, f32x4 (&z)[MT1][T],
                                           const int (&tile)[T], int lane, float* rscr = nullptr) {      // rscr: this wave's 256 floats for rem4_total_lds (REM)
     const int g = lane >> 4;
@@ -338,6 +344,12 @@ __device__ __forceinline__ void node_tail(const StageParams& P, WP wA2, BP b2, i
 #pragma unroll
                 for (int t = 0; t < T; ++t) e[t] = pow_abs4(z[mt1][t], ex1);
                 gemm_block_rem<MT2, T>(wA2 + (mt1 * 2 + 1) * MT2 * 64, e, y, d4, nk1);
+            } else if constexpr (LEAN) {
+                gemm_block<MT2, T>(wA2 + (mt1 * 2) * MT2 * 64, z[mt1], y, nk0);
+                f32x4 e[T];
+#pragma unroll
+                for (int t = 0; t < T; ++t) e[t] = pow_abs4(z[mt1][t], ex1);
+                gemm_block<MT2, T>(wA2 + (mt1 * 2 + 1) * MT2 * 64, e, y, nk1);
             } else if constexpr (!HG_POW_PREFETCH) {
                 gemm_block<MT2, T, true>(wA2 + (mt1 * 2) * MT2 * 64, z[mt1], y, nk0);
                 f32x4 e[T];
@@ -409,6 +421,7 @@ struct TailStage {
     const float* bias;
     const int2* kb1tab;
     int32_t n_nodes, kb1, nf, has_exp, node_blocks, bias_floats, nb_out, mto, mt1, mt2;
+    int32_t sum_in, n_kids;      // hoisted link: as in StageParams
     uint32_t nk2p[kMaxMT], funcp;
     float expo[kMaxFuncs];
 };
@@ -446,6 +459,7 @@ StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq);       // every wave o
 StageFn pick_igsfa(int ms, int mo, int T, int kb1);                   // hg_fused_igsfa.hip
 StageFn pick_igfold(int mo, int T, bool fs = false);
 StageFn pick_prod(int mt1, int mt2, int T);                           // hg_fused_prod.hip
+StageFn pick_stage_sum(int mt1, int mt2, int T, bool fs);             // hg_fused_sum.hip: k_stage for a layer whose first affine was hoisted
 void launch_igfold_split(const StageParams& P, int mo, int n_tiles, hipStream_t st);                                                          // hg_fused_igsfa.hip
 void launch_im2frag(const void* x, int x_dtype, int64_t ldx, int64_t n_rows, int n_tiles, int nb, const int32_t* gcol, f32x4* out,
                     int vec4, hipStream_t st);

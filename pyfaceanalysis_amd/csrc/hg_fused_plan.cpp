@@ -10,18 +10,14 @@
 #include <tuple>
 
 #include "hg_fused_plan.hpp"
+#include "hg_fused_stages.hpp"
 
 namespace hg {
 namespace fused {
 
 namespace {
 
-// ---- host-side normal form ---------------------------------------------------------------------
-struct Aff {  // y = (x - a) W + b
-    int in = 0, out = 0;
-    std::vector<double> a, W, b;
-};
-
+// ---- host-side normal form (Aff, FNode, FStage: hg_fused_stages.hpp) ------------------------------
 Aff aff_of(const TNode& n) { return Aff{(int)n.in_dim, (int)n.out_dim, n.a, n.W, n.b}; }
 
 Aff fold(const Aff& f, const Aff& s) {  // s(f(x)) = (x - f.a)(f.W s.W) + (f.b - s.a) s.W + s.b
@@ -43,28 +39,6 @@ Aff fold(const Aff& f, const Aff& s) {  // s(f(x)) = (x - f.a)(f.W s.W) + (f.b -
     }
     return r;
 }
-
-struct FNode {
-    int in_off = 0, in_dim = 0, out_dim = 0;
-    Aff A1, A2;
-    bool has_exp = false;
-    std::vector<ExpFunc> funcs;
-    bool has_prod = false;              // cross-column products in the expansion -> k_stage_prod
-    bool has_clip = false;              // CutoffNode between expansion and second affine
-    double clip_lo = 0, clip_hi = 0;
-    // iGSFA node: x0 = x - mean; s = sfa(expand(x0)) (scale folded in);
-    // r = x0 - lr(s); q = pca(r); y = [s, q]
-    bool is_ig = false, ig_has_lr = false;
-    int ig_k = 0;
-    std::vector<double> ig_mean;
-    Aff ig_sfa, ig_lr, ig_pca;
-};
-
-struct FStage {
-    std::vector<int32_t> conn;  // stage input column -> column of the previous frame (or of x)
-    std::vector<FNode> nodes;
-    int out_w = 0;
-};
 
 typedef std::vector<const TNode*> LeafSeq;
 
@@ -267,6 +241,8 @@ bool canon(const ChainT& c, int in_off, FNode& fn, std::string& why, const Fused
     return true;
 }
 
+}  // namespace
+
 bool build_stages(const TNode& root, std::vector<FStage>& stages, std::string& why, const FusedOptions& opt) {
     std::vector<int32_t> pending;  // composition of switchboards since the last layer group
     bool have_pending = false;
@@ -349,6 +325,114 @@ bool build_stages(const TNode& root, std::vector<FStage>& stages, std::string& w
     return true;
 }
 
+// Hoisted links.  Between a child's second affine (y_c = e_c A2_c + const) and its parent's first affine (z_p = (x_p - a_p) A1_p) there
+// is only a Switchboard, so where every child column is read exactly once, and all of one child's by one parent,
+//     z_p = sum_c e_c (A2_c A1_p[rows of c, :]) + const_p:
+// the child multiplies its expanded input by the folded matrix, stores z's partial tiles instead of its own output, and the parent
+// adds its children's tiles and ONE bias vector — no first GEMM.  Taken where that makes the child's output no wider (P of the
+// parent <= S of each child) and both stages are ordinary layers on plain 16-row tiles; the links into stage 1 and below stay
+// (the front kernels read those stages' own layout).  Products stay fp32 MFMAs; the fold itself is float64, like fold() above.
+std::vector<int> hoist_first_affines(std::vector<FStage>& fs, const FusedOptions& opt) {
+    (void)opt;
+    std::vector<int> parents;
+    auto ordinary = [](const FStage& st) {
+        for (auto& n : st.nodes)
+            if (n.is_ig || n.has_prod || n.has_clip || !n.has_exp) return false;
+        return true;
+    };
+    auto rem_tile = [](int d) {      // the last 16-row tile of d outputs holds 1..4 rows: a 4x4 remainder tile (or a packed block) could apply
+        const int r = d - 16 * ((d + 15) / 16 - 1);
+        return r >= 1 && r <= 4;
+    };
+    for (size_t l = 1; l + 1 < fs.size(); ++l) {
+        FStage& ch = fs[l];
+        FStage& pa = fs[l + 1];
+        if (!ordinary(ch) || !ordinary(pa)) continue;
+        const int nc = (int)ch.nodes.size(), np = (int)pa.nodes.size();
+        std::vector<int> owner, col0(nc, 0);      // column of the child frame -> child node
+        for (int ci = 0; ci < nc; ++ci) {
+            col0[ci] = (int)owner.size();
+            owner.insert(owner.end(), ch.nodes[ci].out_dim, ci);
+        }
+        std::vector<int> reads(owner.size(), 0), parent_of(nc, -1);
+        std::vector<std::vector<int>> kids(np);
+        bool ok = true;
+        int p_max = 0;
+        for (int pj = 0; pj < np && ok; ++pj) {
+            const FNode& pn = pa.nodes[pj];
+            p_max = std::max(p_max, pn.A1.out);
+            if (pn.A1.in != pn.in_dim || !pn.sum_bias.empty()) ok = false;
+            for (int c = 0; c < pn.in_dim && ok; ++c) {
+                const int pc = pa.conn[pn.in_off + c];
+                if (pc < 0 || pc >= (int)owner.size() || ++reads[pc] > 1) { ok = false; break; }
+                const int ci = owner[pc];
+                if (parent_of[ci] < 0) {
+                    parent_of[ci] = pj;
+                    kids[pj].push_back(ci);
+                } else if (parent_of[ci] != pj) {
+                    ok = false;
+                }
+            }
+            if (kids[pj].empty() || kids[pj].size() > 8) ok = false;
+        }
+        for (int r : reads) ok = ok && r == 1;      // every child column is read by exactly one parent, exactly once
+        for (int ci = 0; ci < nc && ok; ++ci) {
+            if (parent_of[ci] < 0) { ok = false; break; }
+            const FNode& cn = ch.nodes[ci];
+            if (cn.A2.out != cn.out_dim || pa.nodes[parent_of[ci]].A1.out > cn.A2.out) ok = false;
+        }
+        if (!ok || rem_tile(p_max)) continue;
+
+        for (int pj = 0; pj < np; ++pj) {
+            FNode& pn = pa.nodes[pj];
+            const int P = pn.A1.out;
+            pn.sum_bias = pn.A1.b;
+            pn.kids = kids[pj];
+            std::vector<std::vector<double>> Wf(nc);      // (only this parent's children are filled)
+            for (int ci : kids[pj]) Wf[ci].assign((size_t)ch.nodes[ci].A2.in * P, 0.0);
+            for (int c = 0; c < pn.in_dim; ++c) {
+                const int pc = pa.conn[pn.in_off + c], ci = owner[pc], k = pc - col0[ci];
+                const Aff& A2 = ch.nodes[ci].A2;
+                const double* w1 = &pn.A1.W[(size_t)c * P];
+                const double d = A2.b[k] - pn.A1.a[c];
+                for (int o = 0; o < P; ++o) pn.sum_bias[o] += d * w1[o];
+                std::vector<double>& W = Wf[ci];
+                for (int e = 0; e < A2.in; ++e) {
+                    const double w2 = A2.W[(size_t)e * A2.out + k];
+                    if (w2 == 0.0) continue;
+                    for (int o = 0; o < P; ++o) W[(size_t)e * P + o] += w2 * w1[o];
+                }
+            }
+            for (int ci : kids[pj]) {
+                FNode& cn = ch.nodes[ci];
+                for (int e = 0; e < cn.A2.in; ++e) {
+                    const double a = cn.A2.a[e];
+                    if (a == 0.0) continue;
+                    for (int o = 0; o < P; ++o) pn.sum_bias[o] -= a * Wf[ci][(size_t)e * P + o];
+                }
+                Aff f;
+                f.in = cn.A2.in;
+                f.out = P;
+                f.a.assign(f.in, 0.0);
+                f.W = std::move(Wf[ci]);
+                f.b.assign(P, 0.0);
+                cn.A2 = std::move(f);
+                cn.out_dim = P;
+            }
+            pn.A1.a.clear();
+            pn.A1.W.clear();
+            pn.A1.b.clear();
+        }
+        ch.out_w = 0;
+        for (auto& cn : ch.nodes) ch.out_w += cn.out_dim;
+        pa.sum_in = true;
+        parents.push_back((int)l + 1);
+    }
+    return parents;
+}
+
+namespace {
+
 inline int q_of_row(int i) { return 4 * (i & 3) + (i >> 2); }  // tile row -> tile-local feature (involution)
 
 constexpr int kStage0ChunkCols = 128;   // columns of one sub-image staged per chunk (T = 4 tiles -> ~66 KiB LDS)
@@ -415,7 +499,16 @@ struct Planner : FusedPlan {
             for (int ni = 0; ni < n; ++ni) {
                 FNode& nd = st.nodes[ni];
                 NodeK& K = nks[ni];
-                if (si == 0) {
+                if (st.sum_in) {      // child-major: entry i is tile i % mt1 of child i / mt1 (the layer below stores whole blocks, mto = mt1)
+                    const HostStage& below = stages[stages.size() - 2];
+                    if (below.kind != 0 || below.pack_out || below.mto != hs.mt1) fail(HG_ERR_FORMAT, "internal: hoisted link over a layer of another layout");
+                    for (int ci : nd.kids)
+                        for (int mt = 0; mt < hs.mt1; ++mt) {
+                            K.src.push_back(ci * below.mto + mt);
+                            K.nk.push_back(1);      // (a flag here: the block is added, not multiplied)
+                            for (int qq = 0; qq < 16; ++qq) K.kpos.emplace_back();
+                        }
+                } else if (si == 0) {
                     const int nkb = (nd.in_dim + 15) / 16;
                     for (int kb = 0; kb < nkb; ++kb) {
                         // K slot (k-step r, lane group g) <- input position s0_pos(r, g) of this block
@@ -453,7 +546,10 @@ struct Planner : FusedPlan {
                 }
                 hs.kb1 = std::max(hs.kb1, (int)K.src.size());
             }
-            hs.node_blocks = hs.kb1 * hs.mt1 + (hs.has_exp ? hs.mt1 * hs.nf * hs.mt2 : 0);
+            hs.sum_in = st.sum_in;
+            hs.n_kids = st.sum_in ? hs.kb1 / hs.mt1 : 0;
+            const int a1_blocks = st.sum_in ? 0 : hs.kb1 * hs.mt1;      // a hoisted first affine has no fragments
+            hs.node_blocks = a1_blocks + (hs.has_exp ? hs.mt1 * hs.nf * hs.mt2 : 0);
             hs.bias_floats = (hs.mt1 + (hs.has_exp ? hs.mt2 : 0)) * 16;
             if (si > 0 && (size_t)hs.node_blocks * 1024 + (size_t)hs.bias_floats * 4 + (size_t)hs.kb1 * 8 > 150 * 1024)
                 fail(HG_ERR_FORMAT, "fused: one node needs %d KiB of weight fragments, more than a workgroup's LDS", hs.node_blocks);
@@ -470,8 +566,8 @@ struct Planner : FusedPlan {
                 float* bnode = hs.bias.data() + (size_t)ni * hs.bias_floats;
                 // bias 1: (x - a) W + b = x W + (b - a W); stage 0 subtracts fl32(a) in the loader and
                 // keeps only the fp64 remainder here
-                std::vector<double> bias1 = nd.A1.b;
-                for (int c = 0; c < nd.in_dim; ++c) {
+                std::vector<double> bias1 = st.sum_in ? nd.sum_bias : nd.A1.b;
+                for (int c = 0; c < nd.in_dim && !st.sum_in; ++c) {
                     double av = si == 0 ? nd.A1.a[c] - (double)(float)nd.A1.a[c] : nd.A1.a[c];
                     if (av == 0.0) continue;
                     for (int o = 0; o < p; ++o) bias1[o] -= av * nd.A1.W[(size_t)c * p + o];
@@ -488,6 +584,7 @@ struct Planner : FusedPlan {
                         hs.kb1tab[((size_t)ni * hs.kb1 + kb) * 2] = K.src[kb];
                         hs.kb1tab[((size_t)ni * hs.kb1 + kb) * 2 + 1] = K.nk[kb] | (r0 << 8);
                     }
+                    if (st.sum_in) continue;
                     hs.mfma_per_tile += (int64_t)(K.nk[kb] - r0) * hs.mt1;
                     hs.ks1_tile += K.nk[kb] - r0;
                     for (int mt = 0; mt < hs.mt1; ++mt) {
@@ -527,7 +624,7 @@ struct Planner : FusedPlan {
                     std::vector<double> bias2 = nd.A2.b;
                     for (int c = 0; c < nd.A2.in; ++c)
                         for (int o = 0; o < s; ++o) bias2[o] -= nd.A2.a[c] * nd.A2.W[(size_t)c * s + o];
-                    float* w2 = wnode + (size_t)hs.kb1 * hs.mt1 * 256;
+                    float* w2 = wnode + (size_t)a1_blocks * 256;
                     for (int mt1 = 0; mt1 < hs.mt1; ++mt1)
                         for (int fi = 0; fi < hs.nf; ++fi) {
                             const int used = nd.funcs[fi].used(p);
@@ -563,7 +660,7 @@ struct Planner : FusedPlan {
             {
                 const int r1 = hs.p_max - 16 * (hs.mt1 - 1), r2 = hs.s_max - 16 * (hs.mt2 - 1);
                 hs.rem4 = si >= 1 && hs.has_exp && n > 4 && hs.mt1 == hs.mt2 && (hs.mt1 == 2 || hs.mt1 == 3) && r1 >= 1 && r1 <= 4 &&
-                          r2 >= 1 && r2 <= 4 && !opt.no_rem4;
+                          r2 >= 1 && r2 <= 4 && !opt.no_rem4 && !st.sum_in;
                 if (hs.rem4) {
                     auto to4x4 = [](float* blk) {
                         float old[256];
@@ -642,6 +739,7 @@ struct Planner : FusedPlan {
             padded_flops += (hs.mfma16_tile * 2048 + hs.mfma4_tile * 512) / 16;
             std::ostringstream os;
             os << "fused stage " << si << (hs.rem4 ? (hs.pack_out ? " (4x4 remainder tiles, packed four to a block)" : " (4x4 remainder tiles)") : "") << ": " << hs.n_nodes << " nodes, K-blocks " << hs.kb1 << ", tiles " << hs.mt1 << "x" << hs.mt2
+               << (hs.sum_in ? " (first affine folded into the layer below's second, plain 16-row tiles only: z = bias + the tiles of " + std::to_string(hs.n_kids) + " children)" : "")
                << ", " << hs.mfma_per_tile << " MFMA/tile (issued: " << hs.mfma16_tile << " x 16x16x4 + " << hs.mfma4_tile << " x 4x4x1), " << hs.afrag.size() * 4 / 1024
                << " KiB weights, out " << hs.nb_out << " blocks/tile";
             hs.name = os.str();
@@ -1500,8 +1598,23 @@ std::unique_ptr<const FusedPlan> build_fused_plan(const TNode& root, const Fused
         }
     }
     if (why_not) why_not->clear();
+    // hg_info's padded_flops_per_row stays the figure of the flow as given, every layer with its own first affine: where a link
+    // is hoisted, the unhoisted plan is built once more for that count alone (load time only)
+    int64_t given = -1;
+    if (opt.hoist) {
+        std::vector<FStage> plain = stages;
+        if (!hoist_first_affines(stages, opt).empty()) {
+            try {
+                FusedOptions o = opt;
+                o.hoist = false;
+                given = Planner(root, std::move(plain), o).padded_flops;
+            } catch (const Error&) {
+            }
+        }
+    }
     try {
         Planner p(root, std::move(stages), opt);
+        p.padded_flops_given = given >= 0 ? given : p.padded_flops;
         return std::make_unique<const FusedPlan>(std::move(static_cast<FusedPlan&>(p)));
     } catch (const Error& e) {      // a structure the fused kernels do not cover: generic plan instead
         if (why_not) *why_not = e.what();

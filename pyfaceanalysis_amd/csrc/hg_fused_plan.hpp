@@ -45,6 +45,9 @@ struct FusedOptions {
     int subtree_max_wgs = 256;    // HIGSFA_SUBTREE_WGS: ... while sub-trees x tiles stays within this many workgroups
     int splitm_max_nodes = 4;     // experiments: HIGSFA_SPLITM_MAX
     int splitm_max_wgs = 512;     // HIGSFA_SPLITM_WGS: largest k_stage_splitm grid for layers of more than splitm_max_nodes nodes
+    int sum_lds_kib = 32;         // HIGSFA_SUM_LDS: KiB of second-affine fragments a k_stage_sum workgroup keeps in LDS (node group of a hoisted layer)
+    bool hoist = false;           // fold each parent's first affine into its children's second affine where the link allows it (hoist_first_affines);
+                                  // not an environment switch of the planner: the executor turns it on unless HIGSFA_NO_HOIST is set
     static FusedOptions from_env() {
         FusedOptions o;
         o.no_rem4 = getenv("HIGSFA_NO_REM4") != nullptr;
@@ -62,6 +65,7 @@ struct FusedOptions {
         if (const char* e = getenv("HIGSFA_SPLITM_WGS")) o.splitm_max_wgs = atoi(e);
         if (const char* e = getenv("HIGSFA_SUBTREE")) o.subtree_max_tiles = std::max(0, atoi(e));
         if (const char* e = getenv("HIGSFA_SUBTREE_WGS")) o.subtree_max_wgs = std::max(0, atoi(e));
+        if (const char* e = getenv("HIGSFA_SUM_LDS")) o.sum_lds_kib = std::max(1, atoi(e));
         if (const char* e = getenv("HIGSFA_TAIL")) o.tail_max = std::max(0, std::min(atoi(e), kMaxTail));
         return o;
     }
@@ -112,6 +116,8 @@ struct HostStage {
     int64_t mfma16_tile = 0, mfma4_tile = 0;      // instructions issued per batch tile, all nodes of the layer
     int64_t ks1_tile = 0, ks2_tile = 0;      // k-steps of the first / second affine summed over the layer's nodes (per batch tile): issue accounting
     std::string name;
+    bool sum_in = false;     // hoisted link: no first affine; kb1tab lists the children's tiles child-major (entry i: z tile i % mt1; k-steps = 1 real, 0 padding)
+    int n_kids = 0;          // ... children per node (kb1 / mt1)
 };
 
 struct FusedPlan {
@@ -124,7 +130,8 @@ struct FusedPlan {
     int tail_act_blocks = 0, tail_e_blocks = 0;
     std::vector<SubRun> sub_runs;       // k_subtree runs (short batches)
     int max_nb = 0;
-    int64_t padded_flops = 0;
+    int64_t padded_flops = 0;           // FLOPs per row this plan issues (hoisted links included)
+    int64_t padded_flops_given = 0;     // ... the plan of the same flow with no link hoisted issues: what hg_info reports (== padded_flops where nothing was hoisted)
 
     // The per-call choices: pure functions of the plan and the batch's 16-row tiles.
     // Three fused layers pay off from ~1400 rows on (call times against N, profiles/r03_call_times.txt: 16 waves per workgroup walk

@@ -109,13 +109,39 @@ __device__ __forceinline__ void tail_layer(const TailParams& P, const TailStage&
     if (g2) {
 #pragma unroll
         for (int k = 0; k < KB; ++k)
-            if (k < k2n) a2[k] = wnode[((size_t)S.kb1 * mt1n + (size_t)k * mt2n + mw) * 64];
+            if (k < k2n) a2[k] = wnode[((size_t)(S.sum_in ? 0 : S.kb1 * mt1n) + (size_t)k * mt2n + mw) * 64];
     }
     if (g1) {
         f32x4 z[T];
         const f32x4 bb = *(const f32x4*)(bnode + mw * 16);
 #pragma unroll
         for (int t = 0; t < T; ++t) z[t] = bb;
+        if (S.sum_in) {
+            // hoisted first affine (StageParams::sum_in): no weight blocks to request; z tile mw = ((bias + child 0's tile mw) + child 1's) + ...
+            int on[KB];
+            f32x4 bf[KB][T];
+#pragma unroll
+            for (int k = 0; k < KB; ++k) {
+                const bool real = k < S.n_kids;
+                const int2 e = kt[(real ? k : 0) * mt1n + mw];
+                on[k] = real ? e.y : 0;
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    if constexpr (FIRST) bf[k][t] = P.in[(size_t)(trow[t] + (uint32_t)e.x) * 64 + lane];
+                    else bf[k][t] = src[((size_t)e.x * T + t) * 64 + lane];
+                }
+            }
+#ifdef HIGSFA_DIAG
+            TAIL_LOADS_DONE();
+            TAIL_STAMP(1 + 5 * sidx);
+#endif
+#pragma unroll
+            for (int k = 0; k < KB; ++k)
+                if (on[k]) {
+#pragma unroll
+                    for (int t = 0; t < T; ++t) z[t] += bf[k][t];
+                }
+        } else
         for (int k0 = 0; k0 < S.kb1; k0 += KB) {
             // the whole batch of K-block entries first (scalar loads that do not wait for one another; the table has 8 spare
             // entries behind the last node), then every weight / input block of the batch, then the MFMAs
