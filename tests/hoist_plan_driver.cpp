@@ -3,6 +3,8 @@
 //                                      with FusedOptions::hoist on (tests/plan_digest.hpp), or the reason it refuses
 //   hoist_plan_driver --dump FILE      the normal form after hoist_first_affines, in full float64: per hoisted parent node its children
 //                                      and bias vector, per child node the folded second affine
+//   hoist_plan_driver --links FILE...  for every blob, per node of a hoisted stage: stage, node, columns of z, children in the order
+//                                      their tiles are added
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -63,8 +65,34 @@ static int dump(const char* path) {
     return 0;
 }
 
+static int links(int argc, char** argv) {
+    using namespace hg::fused;
+    for (int i = 2; i < argc; ++i) {
+        const auto b = slurp(argv[i]);
+        const auto tree = hg::parse_blob(b.data(), b.size());
+        FusedOptions opt = FusedOptions::from_env();
+        opt.hoist = true;
+        std::vector<FStage> fs;
+        std::string why;
+        printf("== %d\n", i - 2);
+        if (!build_stages(*tree, fs, why, opt)) {
+            printf("refused: %s\n", why.c_str());
+            continue;
+        }
+        for (int pi : hoist_first_affines(fs, opt))
+            for (size_t j = 0; j < fs[pi].nodes.size(); ++j) {
+                const FNode& n = fs[pi].nodes[j];
+                printf("parent %d %zu cols %zu kids", pi, j, n.sum_bias.size());
+                for (int k : n.kids) printf(" %d", k);
+                printf("\n");
+            }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "--dump")) return dump(argv[2]);
+    if (argc >= 3 && !strcmp(argv[1], "--links")) return links(argc, argv);
     hg::fused::FusedOptions opt = hg::fused::FusedOptions::from_env();
     opt.hoist = true;
     for (int i = 1; i < argc; ++i) {
