@@ -598,6 +598,7 @@ constexpr int kWeightLdsKiB = 64;       // target size of a node group's weights
 // order; filled by to_device(), freed by release().
 struct StageDev {
     DevBuf afrag, bias, kb1tab, chunks, runs, piece, koff, kmean, kcol, gcol, etab, pack_slot;
+    DevBuf fold_frag, fold_bias;      // stage 1 of a plan with the link 0 -> 1 folded
 };
 struct SubRunDev {
     DevBuf nodes[kMaxTail], tab[kMaxTail];
@@ -627,6 +628,8 @@ public:
     int plan_kind() const override { return HG_PLAN_FUSED; }
     int n_stages() const override { return (int)plan_->stages.size() + 1; }
     std::string stage_name(int i) const override {
+        if (i == 1 && plan_->fuse01 && !plan_->opt.fold01)
+            return plan_->stages[i].name + "  [link 0 -> 1 stays as it is: switched off (HIGSFA_NO_FOLD01)]";
         if (i < (int)plan_->stages.size()) return plan_->stages[i].name;
         return plan_->tail_begin >= 0 ? std::string("row-major y written by the top-of-hierarchy launch (no unpack pass)")
                                       : std::string("fused unpack (fragment order -> row-major y)");
@@ -654,7 +657,21 @@ public:
         for (size_t si = 0; si < dev_.size(); ++si) {
             const HostStage& s = plan_->stages[si];
             StageDev& d = dev_[si];
-            d.afrag.upload(s.afrag.data(), s.afrag.size() * 4);
+            if (plan_->fold01 && si < 2) {
+                // the link 0 -> 1 folded: no kernel reads stage 0's second-affine or stage 1's first-affine fragments any more; the
+                // blocks that are read go up node by node (stage 0: A1 = block 0; stage 1: A2 = the blocks behind kb1 x mt1)
+                const size_t first = si == 0 ? 0 : (size_t)s.kb1 * s.mt1, count = si == 0 ? (size_t)s.kb1 * s.mt1 : (size_t)s.node_blocks - first;
+                std::vector<float> part((size_t)s.n_nodes * count * 256);
+                for (int ni = 0; ni < s.n_nodes; ++ni)
+                    std::copy_n(s.afrag.data() + ((size_t)ni * s.node_blocks + first) * 256, count * 256, part.data() + (size_t)ni * count * 256);
+                d.afrag.upload(part.data(), part.size() * 4);
+                if (si == 1) {
+                    d.fold_frag.upload(s.fold_frag.data(), s.fold_frag.size() * 4);
+                    d.fold_bias.upload(s.fold_bias.data(), s.fold_bias.size() * 4);
+                }
+            } else {
+                d.afrag.upload(s.afrag.data(), s.afrag.size() * 4);
+            }
             d.bias.upload(s.bias.data(), s.bias.size() * 4);
             if (!s.kb1tab.empty()) d.kb1tab.upload(s.kb1tab.data(), s.kb1tab.size() * 4);
             if (!s.gcol.empty()) d.gcol.upload(s.gcol.data(), s.gcol.size() * 4);
@@ -885,6 +902,12 @@ private:
         R.a4x4 = hs.rem4 ? 1 : 0;
         R.sum_in = hs.sum_in ? 1 : 0;
         R.n_kids = hs.n_kids;
+        if (plan_->fold01 && (&hs == &plan_->stages[0] || &hs == &plan_->stages[1])) {      // what to_device uploaded of these two stages
+            const bool first = &hs == &plan_->stages[0];
+            R.node_blocks = first ? hs.kb1 * hs.mt1 : hs.node_blocks - hs.kb1 * hs.mt1;
+            R.fold_frag = (const f32x4*)d.fold_frag.p;
+            R.fold_bias = (const float*)d.fold_bias.p;
+        }
         for (int fi = 0; fi < hs.nf; ++fi) {
             R.funcp |= (uint32_t)hs.funcs[fi].kind << (4 * fi);
             R.expo[fi] = (float)hs.funcs[fi].expo;
@@ -1048,14 +1071,19 @@ private:
             fspec = id_pow(s) && id_pow(plan_->stages[1]) && !plan_->opt.no_fspec;
         }
         const int FT = stage01p_tiles(rem4, fspec);      // batch tiles per pass of the fused front kernel
-        if (plan_->fuse01 && P.vec4 && n_tiles >= FT) {
+        // A folded plan has ONE arithmetic, the front pair kernels': they also take what otherwise falls through to the unfused
+        // kernels — a batch shorter than a pass (k_stage01p guards every tile and row) and rows that allow no 16-byte loads
+        // (k_stage01p's scalar staging branch).
+        const bool fold = plan_->fold01;
+        if (fold && !(rem4 && plan_->fuse01)) fail(HG_ERR_STATE, "internal: the link 0 -> 1 is folded but the front kernel's remainder-tile form does not apply");
+        if (plan_->fuse01 && ((P.vec4 && n_tiles >= FT) || fold)) {
             // layers 0 and 1 in one persistent kernel; layer 1 writes where its own launch would
             StageParams Q = stage_params(plan_->stages[1], dev_[1], nullptr, out1, n_tiles);
             // every wave on its own (k_stage01d) where the input layout allows it, else the LDS-staged kernel
             const size_t esz = dtype_size(x_dtype);
-            const bool direct = fspec && rem4 && s.direct_ok && plan_->stages[1].pack_out && (int64_t)16 * ldx * (int64_t)esz + 2048 < 0x7fffffffll && s.max_chunk_nodes <= 8 && !plan_->opt.no_direct;   // (k_stage01d: 32-bit byte offsets inside a tile's rows; at most four waves)
+            const bool direct = P.vec4 && fspec && rem4 && s.direct_ok && plan_->stages[1].pack_out && (int64_t)16 * ldx * (int64_t)esz + 2048 < 0x7fffffffll && s.max_chunk_nodes <= 8 && !plan_->opt.no_direct;   // (k_stage01d: 32-bit byte offsets inside a tile's rows; at most four waves)
             const bool wgq = !plan_->opt.no_wgq;       // k_stage01d: one tile queue per chunk, shared by the waves of a workgroup
-            StageFn2 fn = direct ? pick_stage01d(x_dtype, false, wgq) : pick_stage01p(x_dtype, false, rem4, fspec);
+            StageFn2 fn = direct ? pick_stage01d(x_dtype, false, wgq, fold) : pick_stage01p(x_dtype, false, rem4, fspec, fold, fold && !P.vec4);
             const int thr01 = 64 * std::max(1, (s.max_chunk_nodes + 1) / 2);   // one wave per pair of layer-0 nodes
             // LDS: the tile buffers of FT batch tiles (k_stage01p only) + 10 vectors of 16 floats (means, biases) per wave
             const size_t lds2 = direct ? (size_t)4 * 160 * 4 + 32 * 4 + (size_t)4 * 256 * 4      // constants | ring + progress words | reduction scratch per wave
@@ -1065,8 +1093,8 @@ private:
             P.tile_parts = std::max(1, std::min(groups2, 256 * occ / std::max(1, P.n_chunks)));
             if (plan_->opt.debug) fprintf(stderr, "[front] occ %d threads %d lds %zu chunks %d tile_parts %d\n", occ, thr01, lds2, P.n_chunks, P.tile_parts);
 #ifdef HIGSFA_DIAG
-            if (plan_->opt.stamp_stage == 0 && x_dtype == HG_F32) {
-                fn = direct ? pick_stage01d(HG_F32, true, wgq) : pick_stage01p(HG_F32, true, rem4, fspec);
+            if (plan_->opt.stamp_stage == 0 && x_dtype == HG_F32 && (direct || !fold)) {      // (the folded k_stage01p has no stamped form)
+                fn = direct ? pick_stage01d(HG_F32, true, wgq, fold) : pick_stage01p(HG_F32, true, rem4, fspec, fold);
                 stamps_begin(P, P.n_chunks * P.tile_parts, 12, st);
             }
 #endif
@@ -1086,6 +1114,7 @@ private:
 #endif
             return true;
         }
+        if (fold) fail(HG_ERR_STATE, "internal: an unfused first-layer kernel on a plan whose link 0 -> 1 is folded");
         const bool persistent = T == 4 && P.vec4 && s.contig4 && s.has_exp && s.mt1 == 1 && s.mt2 == 1 && s.kb1 == 1 &&
                                 s.nf <= 2 && s.max_chunk_nodes <= 16 && 64 * s.max_chunk_pieces <= 8 * 512;
         if (persistent) {
@@ -1402,6 +1431,7 @@ private:
 std::unique_ptr<Executor> make_fused_executor(const TNode& root, std::string* why_not) {
     fused::FusedOptions opt = fused::FusedOptions::from_env();
     opt.hoist = getenv("HIGSFA_NO_HOIST") == nullptr;      // (an executor's switch, not the planner's: DESIGN.md §9)
+    opt.fold01 = getenv("HIGSFA_NO_FOLD01") == nullptr;    // likewise
     auto plan = fused::build_fused_plan(root, opt, why_not);
     if (!plan) return nullptr;
     return std::make_unique<FusedExecutor>(std::move(plan));

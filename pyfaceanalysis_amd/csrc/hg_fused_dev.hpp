@@ -78,6 +78,11 @@ struct StageParams {
     // kb1tab lists the children's tiles child-major, kb1 = n_kids x MT1, entry i feeds z tile i % MT1, .y = 1 (real) or 0 (padding, last);
     // z[mt] = ((bias + child 0's tile) + child 1's tile) + ... in table order, in every kernel that runs such a layer.
     int32_t sum_in, n_kids;
+    // The link 0 -> 1 folded (stage 1 of a FusedPlan::fold01 plan, front kernels' FOLD instantiations): HostStage::fold_frag / fold_bias.
+    // Such a plan uploads of stage 0 the first-affine block of every node alone (node_blocks = 1) and of stage 1 the second-affine
+    // blocks alone (node_blocks = 8, no first-affine blocks in front of them).
+    const f32x4* fold_frag;
+    const float* fold_bias;
 };
 
 __device__ __forceinline__ unsigned long long stamp_now() {
@@ -453,9 +458,9 @@ typedef void (*StageFn2)(StageParams, StageParams);
 // kernels living in the other translation units
 StageFn pick_stage0(int mt1, int mt2, int T, int x_dtype);            // hg_fused_front.hip
 StageFn pick_stage0p(int x_dtype);
-StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec);
+StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold = false, bool scalar = false);      // fold: FusedPlan::fold01 (REM4 forms only); scalar: rows without 16-byte loads (fold only)
 int stage01p_tiles(bool rem4, bool fspec);
-StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq);       // every wave on its own, no LDS tile (hg_fused_front.hip)
+StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold = false);       // every wave on its own, no LDS tile (hg_fused_front.hip)
 StageFn pick_igsfa(int ms, int mo, int T, int kb1);                   // hg_fused_igsfa.hip
 StageFn pick_igfold(int mo, int T, bool fs = false);
 StageFn pick_prod(int mt1, int mt2, int T);                           // hg_fused_prod.hip

@@ -240,7 +240,15 @@ __global__ void __launch_bounds__(512) k_stage0p(StageParams P) {
 // FSPEC = 1: both layers expand with exactly (identity, |x|^p) — the expansion of every preset network — known at compile
 // time: no function-kind branches, the second-tile k-step count of a REM4 layer 1 is the constant 1, and the loop body is
 // one basic block in which the scheduler can place a wave's expansion arithmetic in the shadow of its own MFMAs.
-template <typename XT, bool STAMP = false, bool REM4 = false, int TT = 2, int FSPEC = 0>
+// FOLD (REM4 only; FusedPlan::fold01): the link 0 -> 1 folded.  Layer 0's output never exists, not even in registers: with the folded
+// fragments ff[child][function][tile] (StageParams::fold_frag) z1 = bias' + sum_c [z0_c, |z0_c|^p] F_c.  ONE order of products, here
+// and in k_stage01d: z1 tile 0 starts from the folded bias, the 4x4-form accumulator d4 of tile 1 from zero; then child 0, then child
+// 1, each with the identity's k-steps 0..3 and then |x|^p's k-steps 0..3, every k-step one 16x16x4 into z1 tile 0 and one 4x4x1
+// into d4; after the 16 k-steps ONE lane-group sum of d4 goes onto tile 1's bias (add_rem4 here, rem4_total_lds there: the same bits).
+// SCALAR (with FOLD: a folded plan has no unfused first layer to fall back on): for rows that allow no 16-byte loads (odd base or
+// pitch, P.vec4 == 0); the tile is filled through the chunk's run list with scalar loads, as k_stage0 does, unpipelined.  An
+// instantiation of its own: as a run-time branch it costs the pipelined form 44 bytes of scratch.
+template <typename XT, bool STAMP = false, bool REM4 = false, int TT = 2, int FSPEC = 0, bool FOLD = false, bool SCALAR = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 2 ? 3 : TT == 1 ? 4 : 2, TT == 2 ? 3 : TT == 1 ? 4 : 2))) k_stage01p(StageParams P, StageParams Q) {
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
     float* lds = (float*)smem;
@@ -287,24 +295,37 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
         if (j == 0) *(f32x4*)(cst + (C_MU + sl) * 16 + g * 4) = *(const f32x4*)(P.kmean + ent);
         const f32x4* wp = P.afrag + (size_t)ni * P.node_blocks * 64 + lane;
         w_a1[sl] = wp[0];
-        w_a2[sl][0] = wp[64];
-        w_a2[sl][1] = P.nf > 1 ? wp[128] : wp[64];
+        if constexpr (!FOLD) {
+            w_a2[sl][0] = wp[64];
+            w_a2[sl][1] = P.nf > 1 ? wp[128] : wp[64];
+        }
         const float* bp = P.bias + (size_t)ni * P.bias_floats + g * 4;
         if (j == 0) {
             *(f32x4*)(cst + (C_B1 + sl) * 16 + g * 4) = *(const f32x4*)bp;
-            *(f32x4*)(cst + (C_B2 + sl) * 16 + g * 4) = *(const f32x4*)(bp + 16);
+            if constexpr (!FOLD) *(f32x4*)(cst + (C_B2 + sl) * 16 + g * 4) = *(const f32x4*)(bp + 16);
         }
     }
     // layer-1 node of this wave: A1 [kb 0..1][mt 0..1], A2 [mt1 0..1][fi 0..1][mt2 0..1], biases
+    // (FOLD: ff in place of w_a2 and q_a1; a folded plan uploads stage 1's second-affine fragments alone, Q.node_blocks = 8)
     const int n1 = (ck.node_begin >> 1) + (w_ok ? wave : 0);
-    f32x4 q_a1[2][2], q_a2[2][2][2];
+    f32x4 q_a1[2][2], q_a2[2][2][2], ff[2][2][2];
     {
         const f32x4* wq = Q.afrag + (size_t)n1 * Q.node_blocks * 64 + lane;
+        if constexpr (FOLD) {
+            const f32x4* wf = Q.fold_frag + (size_t)n1 * 8 * 64 + lane;
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
+            for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) q_a1[kb][mt] = wq[(kb * 2 + mt) * 64];
-        const f32x4* wq2 = wq + Q.kb1 * 2 * 64;
+                for (int fi = 0; fi < 2; ++fi)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) ff[sl][fi][mt] = wf[((sl * 2 + fi) * 2 + mt) * 64];
+        } else {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) q_a1[kb][mt] = wq[(kb * 2 + mt) * 64];
+        }
+        const f32x4* wq2 = FOLD ? wq : wq + Q.kb1 * 2 * 64;
 #pragma unroll
         for (int m1 = 0; m1 < 2; ++m1)
 #pragma unroll
@@ -312,10 +333,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
 #pragma unroll
                 for (int mt = 0; mt < 2; ++mt) q_a2[m1][fi][mt] = wq2[((m1 * Q.nf + (fi < Q.nf ? fi : 0)) * 2 + mt) * 64];
         const float* bq = Q.bias + (size_t)n1 * Q.bias_floats + g * 4;
+        const float* bq1 = FOLD ? Q.fold_bias + (size_t)n1 * 32 + g * 4 : bq;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
             if (j == 0) {
-                *(f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4) = *(const f32x4*)(bq + mt * 16);
+                *(f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4) = *(const f32x4*)(bq1 + mt * 16);
                 *(f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4) = *(const f32x4*)(bq + 32 + mt * 16);
             }
     }
@@ -325,9 +347,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
         const int src = ((lane & 48) | ((lane & 3) << 2)) << 2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+            if constexpr (!FOLD) {
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                q_a1[kb][1][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q_a1[kb][1][r])));
+                for (int kb = 0; kb < 2; ++kb)
+                    q_a1[kb][1][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q_a1[kb][1][r])));
+            }
 #pragma unroll
             for (int m1 = 0; m1 < 2; ++m1)
 #pragma unroll
@@ -351,6 +375,21 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
                 v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     };
+    // SCALAR: nothing is prefetched, stage_scalar fills the tile at the top of the iteration
+    constexpr bool scalar_in = SCALAR;
+    auto stage_scalar = [&](int grp, float* tile_lds) {
+        const int nw = nthr >> 6;
+        for (int sj = wave; sj < T * 16; sj += nw) {
+            const int64_t row = (int64_t)grp * (T * 16) + sj;
+            const bool ok = row < P.n_rows;
+            const XT* srow = x + (ok ? row : 0) * P.ldx;
+            float* dst = tile_lds + sj * stride;
+            for (int ri = 0; ri < ck.run_count; ++ri) {
+                const DRun rn = P.runs[ck.run_begin + ri];
+                for (int e = lane; e < rn.len; e += 64) dst[rn.lds_off + e] = ok ? (float)srow[rn.start + e] : 0.f;
+            }
+        }
+    };
     f32x4 v[NB];
     // tile-group queue (StageParams::work_ctr): this workgroup's first group is `part`, the rest are grabbed by thread 0
     // two iterations ahead and passed through an LDS slot that alternates with the tile buffers
@@ -368,7 +407,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
     uint32_t q_raw = 0;                        // thread 0: the grab in flight (group of the iteration after next)
     bool q_more = tid == 0;                    // thread 0: no grab has failed yet
     if (q_more) q_raw = grab_raw();
-    if (part < n_groups) fetch(part, v);
+    if (part < n_groups && !scalar_in) fetch(part, v);
     // two LDS tiles, used alternately: one barrier per tile group is enough (a wave that writes tile
     // i+1 has passed barrier i, i.e. every wave has finished reading tile i-1, which shares its buffer)
     const int buf_words = T * 16 * stride;
@@ -411,9 +450,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
             __syncthreads();   // single tile: every wave is done with the previous tile group
         }
         flip ^= 1;
+        if (scalar_in) {
+            stage_scalar(grp, lds);
+        } else {
 #pragma unroll
-        for (int k = 0; k < NB; ++k)
-            if (p_dst[k] >= 0) *(f32x4*)(lds + (p_dst[k] & 0xffffff)) = v[k];
+            for (int k = 0; k < NB; ++k)
+                if (p_dst[k] >= 0) *(f32x4*)(lds + (p_dst[k] & 0xffffff)) = v[k];
+        }
         if (tid < T * 16) lds[tid * stride + stride - 1] = 0.f;
         if (tid == 0) {
             const int q_next = q_more ? grab_group(q_raw) : n_groups;
@@ -423,7 +466,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
         __syncthreads();
         const int grp_next = __builtin_amdgcn_readfirstlane(qslot[slot]);
         if (STAMP) { unsigned long long t = stamp_now(); t_w += t - ts; ts = t; }
-        if (grp_next < n_groups) fetch(grp_next, v);
+        if (grp_next < n_groups && !scalar_in) fetch(grp_next, v);
         if (DEFER) flush();      // after the loads: the compiler waits for everything outstanding before it reuses their registers
         if (q_more) q_raw = grab_raw();      // likewise the next grab: issued here, looked at one iteration later
         if (STAMP) { unsigned long long t = stamp_now(); t_f += t - ts; ts = t; }
@@ -431,6 +474,50 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
             int tile[T];
 #pragma unroll
             for (int t = 0; t < T; ++t) tile[t] = grp * T + t;
+            f32x4 z1[2][T], y1[2][T];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    z1[mt][t] = *(const f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4);
+                    y1[mt][t] = *(const f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4);
+                }
+            f32x4 d4[T];      // REM4: 4x4-form accumulators of the second tile (rows x k partial sums)
+#pragma unroll
+            for (int t = 0; t < T; ++t) d4[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (FOLD) {
+                // ---- layer 0's first affine, then layer 1's first affine folded with layer 0's second (order: see the head comment)
+#pragma unroll
+                for (int sl = 0; sl < NPW; ++sl) {
+                    f32x4 z[T], bf[T];
+                    const f32x4 mu = *(const f32x4*)(cst + (C_MU + sl) * 16 + g * 4);
+                    const f32x4 cb1 = *(const f32x4*)(cst + (C_B1 + sl) * 16 + g * 4);
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        bf[t] = *(const f32x4*)(lds + (t * 16 + j) * stride + w_off[sl]) - mu;
+                        z[t] = cb1;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int t = 0; t < T; ++t) z[t] = MFMA16(w_a1[sl][r], bf[t][r], z[t]);
+#pragma unroll
+                    for (int fi = 0; fi < 2; ++fi) {
+                        f32x4 e[T];
+#pragma unroll
+                        for (int t = 0; t < T; ++t)
+                            e[t] = FSPEC == 1 ? (fi == 0 ? z[t] : pow_abs4(z[t], ex1)) : apply_func(fi == 0 ? fk0 : fk1, fi == 0 ? ex0 : ex1, z[t]);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+                            for (int t = 0; t < T; ++t) z1[0][t] = MFMA16(ff[sl][fi][0][r], e[t][r], z1[0][t]);
+#pragma unroll
+                            for (int t = 0; t < T; ++t) d4[t] = MFMA4(ff[sl][fi][1][r], e[t][r], d4[t]);
+                        }
+                    }
+                }
+                if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
+            } else {
             // ---- layer 0: two children
             f32x4 y0[NPW][T];
 #pragma unroll
@@ -469,17 +556,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
             }
             if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
             // ---- layer 1: K-blocks of the first affine are the children's accumulators
-            f32x4 z1[2][T], y1[2][T];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    z1[mt][t] = *(const f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4);
-                    y1[mt][t] = *(const f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4);
-                }
-            f32x4 d4[T];      // REM4: 4x4-form accumulators of the second tile (rows x k partial sums)
-#pragma unroll
-            for (int t = 0; t < T; ++t) d4[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -492,6 +568,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
                         else z1[1][t] = MFMA16(q_a1[kb][1][r], y0[kb][t][r], z1[1][t]);
                     }
                 }
+            }
             if constexpr (REM4) {
 #pragma unroll
                 for (int t = 0; t < T; ++t) {
@@ -586,7 +663,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
 // at nearly the same time and the 128-byte input lines and packed output blocks they share are fetched and written once
 // (the per-wave queues decorrelate them: 389 MB read / 235 MB written against 279 / 201).  No barrier in the loop: a
 // follower waits only when it is more than one pass ahead of wave 0, wave 0 only when a follower is eight passes behind.
-template <typename XT, bool STAMP = false, bool WGQ = true>
+// FOLD: the link 0 -> 1 folded, as in k_stage01p (same products, same order).
+template <typename XT, bool STAMP = false, bool WGQ = true, bool FOLD = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) k_stage01d(StageParams P, StageParams Q) {
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
     unsigned long long rt_entry = 0;
@@ -622,26 +700,40 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (j == 0) *(f32x4*)(cst + (C_MU + sl) * 16 + g * 4) = *(const f32x4*)(P.kmean + ent);
         const f32x4* wp = P.afrag + (size_t)ni * P.node_blocks * 64 + lane;
         w_a1[sl] = wp[0];
-        w_a2[sl][0] = wp[64];
-        w_a2[sl][1] = wp[128];
+        if constexpr (!FOLD) {
+            w_a2[sl][0] = wp[64];
+            w_a2[sl][1] = wp[128];
+        }
         const float* bp = P.bias + (size_t)ni * P.bias_floats + g * 4;
         if (j == 0) {
             *(f32x4*)(cst + (C_B1 + sl) * 16 + g * 4) = *(const f32x4*)bp;
-            *(f32x4*)(cst + (C_B2 + sl) * 16 + g * 4) = *(const f32x4*)(bp + 16);
+            if constexpr (!FOLD) *(f32x4*)(cst + (C_B2 + sl) * 16 + g * 4) = *(const f32x4*)(bp + 16);
         }
     }
     const int n1 = (ck.node_begin >> 1) + wave;
     // layer-1 weights: first affine [kb][mt]; second affine, first z tile [fi][mt]; of the second z tile (four real rows = ONE
     // k-step) only that k-step's value per lane is kept
-    f32x4 q_a1[2][2], q_a2[2][2];
+    // FOLD: ff[child][function][tile] (StageParams::fold_frag, tile 1 in 4x4 form already) in place of w_a2 and q_a1 — the same 32 registers;
+    // a folded plan uploads stage 1's second-affine fragments alone (Q.node_blocks = 8, no first-affine blocks in front)
+    f32x4 q_a1[2][2], q_a2[2][2], ff[2][2][2];
     float q_a2t[2][2];
     {
         const f32x4* wq = Q.afrag + (size_t)n1 * Q.node_blocks * 64 + lane;
+        if constexpr (FOLD) {
+            const f32x4* wf = Q.fold_frag + (size_t)n1 * 8 * 64 + lane;
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
+            for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) q_a1[kb][mt] = wq[(kb * 2 + mt) * 64];
-        const f32x4* wq2 = wq + Q.kb1 * 2 * 64;
+                for (int fi = 0; fi < 2; ++fi)
+#pragma unroll
+                    for (int mt = 0; mt < 2; ++mt) ff[sl][fi][mt] = wf[((sl * 2 + fi) * 2 + mt) * 64];
+        } else {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) q_a1[kb][mt] = wq[(kb * 2 + mt) * 64];
+        }
+        const f32x4* wq2 = FOLD ? wq : wq + Q.kb1 * 2 * 64;
 #pragma unroll
         for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
@@ -650,10 +742,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 q_a2t[fi][mt] = wq2[((2 + fi) * 2 + mt) * 64][0];
             }
         const float* bq = Q.bias + (size_t)n1 * Q.bias_floats + g * 4;
+        const float* bq1 = FOLD ? Q.fold_bias + (size_t)n1 * 32 + g * 4 : bq;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
             if (j == 0) {
-                *(f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4) = *(const f32x4*)(bq + mt * 16);
+                *(f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4) = *(const f32x4*)(bq1 + mt * 16);
                 *(f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4) = *(const f32x4*)(bq + 32 + mt * 16);
             }
     }
@@ -661,9 +754,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         const int bsrc = ((lane & 48) | ((lane & 3) << 2)) << 2;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+            if constexpr (!FOLD) {
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-                q_a1[kb][1][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(bsrc, __float_as_int(q_a1[kb][1][r])));
+                for (int kb = 0; kb < 2; ++kb)
+                    q_a1[kb][1][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(bsrc, __float_as_int(q_a1[kb][1][r])));
+            }
 #pragma unroll
             for (int fi = 0; fi < 2; ++fi)
                 q_a2[fi][1][r] = __int_as_float(__builtin_amdgcn_ds_bpermute(bsrc, __float_as_int(q_a2[fi][1][r])));
@@ -783,6 +878,31 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         flush();
         if (grabber && q_more && lane == 0) q_raw = grab_raw();
         if (STAMP) { unsigned long long t = stamp_now(); t_top += t - ts; ts = t; }
+        f32x4 z1[2], y1[2];
+        f32x4 d4 = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (FOLD) {
+            // ---- layer 1, first affine folded with layer 0's second (order of products: see k_stage01p)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                z1[mt] = *(const f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4);
+                y1[mt] = *(const f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4);
+            }
+#pragma unroll
+            for (int sl = 0; sl < 2; ++sl) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    z1[0] = MFMA16(ff[sl][0][0][r], z0[sl][r], z1[0]);
+                    d4 = MFMA4(ff[sl][0][1][r], z0[sl][r], d4);
+                }
+                const f32x4 e = pow_abs4(z0[sl], ex1);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    z1[0] = MFMA16(ff[sl][1][0][r], e[r], z1[0]);
+                    d4 = MFMA4(ff[sl][1][1][r], e[r], d4);
+                }
+            }
+            if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
+        } else {
         f32x4 y0[2];
 #pragma unroll
         for (int sl = 0; sl < 2; ++sl) {
@@ -795,13 +915,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
         if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
         // ---- layer 1
-        f32x4 z1[2], y1[2];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             z1[mt] = *(const f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4);
             y1[mt] = *(const f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4);
         }
-        f32x4 d4 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -809,6 +927,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 z1[0] = MFMA16(q_a1[kb][0][r], y0[kb][r], z1[0]);
                 d4 = MFMA4(q_a1[kb][1][r], y0[kb][r], d4);
             }
+        }
         if constexpr (HG_REM4_LDS) z1[1][0] += rem4_total_lds(d4, rscr, lane);
         else add_rem4(z1[1], d4);
         d4 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -847,10 +966,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 }
 
-StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq) {
+StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold) {
 #ifdef HIGSFA_DIAG
+    if (stamp && x_dtype == HG_F32 && fold) return wgq ? (StageFn2)k_stage01d<float, true, true, true> : (StageFn2)k_stage01d<float, true, false, true>;
     if (stamp && x_dtype == HG_F32) return wgq ? (StageFn2)k_stage01d<float, true, true> : (StageFn2)k_stage01d<float, true, false>;
 #endif
+    if (fold) {
+        if (!wgq) return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, false, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, false, true> : (StageFn2)k_stage01d<double, false, false, true>;
+        return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, true, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, true, true> : (StageFn2)k_stage01d<double, false, true, true>;
+    }
     if (!wgq) return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, false> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, false> : (StageFn2)k_stage01d<double, false, false>;
     return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float> : (StageFn2)k_stage01d<double>;
 }
@@ -893,7 +1017,21 @@ StageFn pick_stage0p(int x_dtype) {
 // tiles at three waves), the generic form two tiles at three waves (168 VGPRs).
 int stage01p_tiles(bool rem4, bool fspec) { return fspec ? 1 : 2; }
 
-StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec) {
+StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold, bool scalar) {
+    if (rem4 && fold && scalar) {
+        if (fspec)
+            return x_dtype == HG_U8 ? (StageFn2)k_stage01p<uint8_t, false, true, 1, 1, true, true>
+                                    : x_dtype == HG_F32 ? (StageFn2)k_stage01p<float, false, true, 1, 1, true, true> : (StageFn2)k_stage01p<double, false, true, 1, 1, true, true>;
+        return x_dtype == HG_U8 ? (StageFn2)k_stage01p<uint8_t, false, true, 2, 0, true, true>
+                                : x_dtype == HG_F32 ? (StageFn2)k_stage01p<float, false, true, 2, 0, true, true> : (StageFn2)k_stage01p<double, false, true, 2, 0, true, true>;
+    }
+    if (rem4 && fold) {      // (no stamped form)
+        if (fspec)
+            return x_dtype == HG_U8 ? (StageFn2)k_stage01p<uint8_t, false, true, 1, 1, true>
+                                    : x_dtype == HG_F32 ? (StageFn2)k_stage01p<float, false, true, 1, 1, true> : (StageFn2)k_stage01p<double, false, true, 1, 1, true>;
+        return x_dtype == HG_U8 ? (StageFn2)k_stage01p<uint8_t, false, true, 2, 0, true>
+                                : x_dtype == HG_F32 ? (StageFn2)k_stage01p<float, false, true, 2, 0, true> : (StageFn2)k_stage01p<double, false, true, 2, 0, true>;
+    }
     if (rem4) {
 #ifdef HIGSFA_DIAG
         if (stamp && x_dtype == HG_F32) return fspec ? (StageFn2)k_stage01p<float, true, true, 1, 1> : (StageFn2)k_stage01p<float, true, true>;

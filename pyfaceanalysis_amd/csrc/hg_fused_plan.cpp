@@ -162,6 +162,7 @@ void fold_igsfa(FNode& fn, bool nofold) {
     fn.A1 = std::move(A1);
     fn.A2 = std::move(A2);
     fn.is_ig = false;
+    fn.was_ig = true;
 }
 
 bool canon(const ChainT& c, int in_off, FNode& fn, std::string& why, const FusedOptions& opt) {
@@ -325,6 +326,48 @@ bool build_stages(const TNode& root, std::vector<FStage>& stages, std::string& w
     return true;
 }
 
+namespace {
+// One parent's share of a link, in float64: per child c (of `kids`) the folded matrix A2_c A1_p[rows of c, :] ([A2_c.in x P], W[c];
+// the other entries of W stay empty) and the ONE bias vector b1_p + sum_c (b2_c - a_p[rows c]) A1_p[rows c, :] - sum_c a2_c W[c].
+// owner / col0: column of the child frame -> child node / first column of a child.  Changes nothing: hoist_first_affines stores
+// the result in the normal form, the link 0 -> 1 keeps it beside the two stages (Planner::plan_fold01).
+struct LinkFold {
+    std::vector<double> bias;
+    std::vector<std::vector<double>> W;
+};
+LinkFold fold_link(const FStage& ch, const FStage& pa, int pj, const std::vector<int>& owner, const std::vector<int>& col0, const std::vector<int>& kids) {
+    const FNode& pn = pa.nodes[pj];
+    const int P = pn.A1.out;
+    LinkFold lf;
+    lf.bias = pn.A1.b;
+    lf.W.resize(ch.nodes.size());
+    for (int ci : kids) lf.W[ci].assign((size_t)ch.nodes[ci].A2.in * P, 0.0);
+    for (int c = 0; c < pn.in_dim; ++c) {
+        const int pc = pa.conn[pn.in_off + c], ci = owner[pc], k = pc - col0[ci];
+        const Aff& A2 = ch.nodes[ci].A2;
+        const double* w1 = &pn.A1.W[(size_t)c * P];
+        const double d = A2.b[k] - pn.A1.a[c];
+        for (int o = 0; o < P; ++o) lf.bias[o] += d * w1[o];
+        std::vector<double>& W = lf.W[ci];
+        for (int e = 0; e < A2.in; ++e) {
+            const double w2 = A2.W[(size_t)e * A2.out + k];
+            if (w2 == 0.0) continue;
+            for (int o = 0; o < P; ++o) W[(size_t)e * P + o] += w2 * w1[o];
+        }
+    }
+    for (int ci : kids) {
+        const Aff& A2 = ch.nodes[ci].A2;
+        for (int e = 0; e < A2.in; ++e) {
+            const double a = A2.a[e];
+            if (a == 0.0) continue;
+            for (int o = 0; o < P; ++o) lf.bias[o] -= a * lf.W[ci][(size_t)e * P + o];
+        }
+    }
+    return lf;
+}
+
+}  // namespace
+
 // Hoisted links.  Between a child's second affine (y_c = e_c A2_c + const) and its parent's first affine (z_p = (x_p - a_p) A1_p) there
 // is only a Switchboard, so where every child column is read exactly once, and all of one child's by one parent,
 //     z_p = sum_c e_c (A2_c A1_p[rows of c, :]) + const_p:
@@ -386,30 +429,12 @@ std::vector<int> hoist_first_affines(std::vector<FStage>& fs, const FusedOptions
         for (int pj = 0; pj < np; ++pj) {
             FNode& pn = pa.nodes[pj];
             const int P = pn.A1.out;
-            pn.sum_bias = pn.A1.b;
+            LinkFold lf = fold_link(ch, pa, pj, owner, col0, kids[pj]);
+            pn.sum_bias = std::move(lf.bias);
             pn.kids = kids[pj];
-            std::vector<std::vector<double>> Wf(nc);      // (only this parent's children are filled)
-            for (int ci : kids[pj]) Wf[ci].assign((size_t)ch.nodes[ci].A2.in * P, 0.0);
-            for (int c = 0; c < pn.in_dim; ++c) {
-                const int pc = pa.conn[pn.in_off + c], ci = owner[pc], k = pc - col0[ci];
-                const Aff& A2 = ch.nodes[ci].A2;
-                const double* w1 = &pn.A1.W[(size_t)c * P];
-                const double d = A2.b[k] - pn.A1.a[c];
-                for (int o = 0; o < P; ++o) pn.sum_bias[o] += d * w1[o];
-                std::vector<double>& W = Wf[ci];
-                for (int e = 0; e < A2.in; ++e) {
-                    const double w2 = A2.W[(size_t)e * A2.out + k];
-                    if (w2 == 0.0) continue;
-                    for (int o = 0; o < P; ++o) W[(size_t)e * P + o] += w2 * w1[o];
-                }
-            }
+            std::vector<std::vector<double>>& Wf = lf.W;
             for (int ci : kids[pj]) {
                 FNode& cn = ch.nodes[ci];
-                for (int e = 0; e < cn.A2.in; ++e) {
-                    const double a = cn.A2.a[e];
-                    if (a == 0.0) continue;
-                    for (int o = 0; o < P; ++o) pn.sum_bias[o] -= a * Wf[ci][(size_t)e * P + o];
-                }
                 Aff f;
                 f.in = cn.A2.in;
                 f.out = P;
@@ -749,6 +774,7 @@ struct Planner : FusedPlan {
         if (fuse01) {
             stages[0].name += "  [+ stage 1 fused in the same persistent kernel when the input allows 16-byte loads]";
         }
+        if (opt.fold01) plan_fold01(fs);
         col_base.resize(out_dim);
         col_of.assign((size_t)std::max(prev_nb, 1) * 16, -1);      // inverse map for k_tail: (output block, feature of the tile) -> caller column
         for (int c = 0; c < out_dim; ++c) {
@@ -1515,6 +1541,114 @@ struct Planner : FusedPlan {
         }
     }
 
+    // The link 0 -> 1 (DESIGN.md §3.1 "Hoisted links").  hoist_first_affines leaves it alone: folding it would widen layer 0's stored
+    // output.  In the front kernels that output is never stored — a wave holds both children's z0 and feeds them on — so there the
+    // fold costs no bytes: with F_c = A2_c A1_q[rows of c, :],
+    //     z1_q = bias'_q + sum_c [z0_c, |z0_c|^p] F_c,
+    // 16 k-steps of (one 16x16x4 + one 4x4x1) in place of layer 0's second affine (16 x 16x16x4) and layer 1's first (8 + 8).
+    // Taken where layers 0 and 1 share the front kernel (fuse01), both expand with exactly (identity, |x|^p) and layer 1 has 4x4
+    // remainder tiles; a function of the flow and of no_rem4 alone, so every front variant runs the same arithmetic.  The fold is
+    // fold_link's, float64 rounded once.  HostStages 0 and 1 stay whole; the folded fragments and bias are added to stage 1.
+    void plan_fold01(const std::vector<FStage>& fs) {
+        if (stages.size() < 2) return;
+        auto refuse = [&](const std::string& why) {
+            fold01_note = "link 0 -> 1 stays as it is: " + why;
+            stages[1].name += "  [" + fold01_note + "]";
+        };
+        if (!fuse01) {
+            bool ig = false;
+            for (size_t l = 0; l < 2 && l < fs.size(); ++l)
+                for (auto& n : fs[l].nodes) ig = ig || n.is_ig || n.was_ig;
+            return refuse(ig ? "an iGSFA front end" : "layers 0 and 1 do not share the front kernel");
+        }
+        const FStage &ch = fs[0], &pa = fs[1];
+        HostStage &a = stages[0], &b = stages[1];
+        for (auto& n : pa.nodes)
+            if (n.was_ig) return refuse("layer 1 is an iGSFA layer (identity first affine, no remainder tiles)");
+        for (auto& n : ch.nodes)
+            if (n.was_ig) return refuse("layer 0 is an iGSFA layer");
+        auto id_pow = [](const HostStage& hs) { return hs.nf == 2 && hs.funcs[0].kind == E_IDENTITY && hs.funcs[1].kind == E_ABS_POW; };
+        if (!id_pow(a) || !id_pow(b)) return refuse("both layers must expand with exactly (identity, |x|^p)");
+        if (opt.no_rem4) return refuse("4x4 remainder tiles are switched off (HIGSFA_NO_REM4)");
+        if (!(b.p_max >= 17 && b.p_max <= 20 && b.s_max >= 17 && b.s_max <= 20 && b.nk2[1][0] <= 1 && b.nk2[1][1] <= 1))
+            return refuse("layer 1 has no 4x4 remainder tiles (affines of " + std::to_string(b.p_max) + " and " + std::to_string(b.s_max) + " outputs, not 17..20)");
+        const int nc = (int)ch.nodes.size(), np = (int)pa.nodes.size();
+        std::vector<int> owner, col0(nc, 0);
+        for (int ci = 0; ci < nc; ++ci) {
+            col0[ci] = (int)owner.size();
+            owner.insert(owner.end(), ch.nodes[ci].out_dim, ci);
+        }
+        for (int q = 0; q < np; ++q) {      // (can_fuse01 checked the source blocks; the same on columns)
+            const FNode& pn = pa.nodes[q];
+            if (pn.A1.in != pn.in_dim) return refuse("internal: layer-1 first affine");
+            for (int c = 0; c < pn.in_dim; ++c) {
+                const int pc = pa.conn[pn.in_off + c];
+                if (pc < 0 || pc >= (int)owner.size() || owner[pc] >> 1 != q) return refuse("a layer-1 node reads other nodes than 2n and 2n + 1");
+            }
+        }
+        b.fold_frag.assign((size_t)np * 8 * 256, 0.f);
+        b.fold_bias.assign((size_t)np * 32, 0.f);
+        auto to4x4 = [](float* blk) {      // as for HostStage::rem4
+            float old[256];
+            std::copy(blk, blk + 256, old);
+            for (int l = 0; l < 64; ++l) {
+                const int src = (l & 48) | ((l & 3) << 2);
+                for (int r = 0; r < 4; ++r) blk[l * 4 + r] = old[src * 4 + r];
+            }
+        };
+        for (int q = 0; q < np; ++q) {
+            const FNode& pn = pa.nodes[q];
+            const int P = pn.A1.out;
+            const LinkFold lf = fold_link(ch, pa, q, owner, col0, {2 * q, 2 * q + 1});
+            for (int sl = 0; sl < 2; ++sl) {
+                const FNode& cn = ch.nodes[2 * q + sl];
+                const std::vector<double>& F = lf.W[2 * q + sl];
+                const int p0 = cn.A1.out;
+                int eo = 0;
+                for (int fi = 0; fi < 2; ++fi) {
+                    const int used = cn.funcs[fi].used(p0);
+                    for (int mt = 0; mt < 2; ++mt) {
+                        float* blk = b.fold_frag.data() + ((((size_t)q * 2 + sl) * 2 + fi) * 2 + mt) * 256;
+                        for (int lane = 0; lane < 64; ++lane) {
+                            const int i = lane & 15, gg = lane >> 4;
+                            const int fo = 16 * mt + q_of_row(i);
+                            if (fo >= P) continue;
+                            for (int r = 0; r < 4; ++r) {
+                                const int fz = 4 * r + gg;
+                                if (fz >= used) continue;
+                                blk[lane * 4 + r] = (float)F[(size_t)(eo + fz) * P + fo];
+                            }
+                        }
+                        if (mt == 1) to4x4(blk);
+                    }
+                    eo += cn.funcs[fi].out_dim(p0);
+                }
+            }
+            for (int mt = 0; mt < 2; ++mt)
+                for (int gg = 0; gg < 4; ++gg)
+                    for (int r = 0; r < 4; ++r) {
+                        const int fo = 16 * mt + 4 * r + gg;
+                        b.fold_bias[(size_t)q * 32 + mt * 16 + gg * 4 + r] = fo < P ? (float)lf.bias[fo] : 0.f;
+                    }
+        }
+        // what the front kernels issue now: layer 0 its first affine alone; layer 1 the folded first affine (the k-steps of layer
+        // 0's second affine, each one 16x16x4 + one 4x4x1) and its own second
+        const int64_t before = padded_flops;
+        padded_flops -= (a.mfma16_tile * 2048 + a.mfma4_tile * 512) / 16 + (b.mfma16_tile * 2048 + b.mfma4_tile * 512) / 16;
+        a.mfma16_tile = a.ks1_tile;
+        a.mfma4_tile = 0;
+        b.mfma16_tile = a.ks2_tile + b.ks2_tile;
+        b.mfma4_tile = a.ks2_tile + b.ks2_tile;
+        padded_flops += (a.mfma16_tile * 2048 + a.mfma4_tile * 512) / 16 + (b.mfma16_tile * 2048 + b.mfma4_tile * 512) / 16;
+        fold01_flops = padded_flops - before;
+        fold01 = true;
+        fold01_note = "link 0 -> 1 folded: layer 0's second affine multiplied into this layer's first, z = bias' + sum over the two children of "
+                      "[z0, |z0|^p] (A2 A1[rows of the child, :]) inside the front kernel, which then issues " + std::to_string(a.mfma16_tile) +
+                      " x 16x16x4 for layer 0 and " + std::to_string(b.mfma16_tile) + " x 16x16x4 + " + std::to_string(b.mfma4_tile) +
+                      " x 4x4x1 for this layer (the counts on the two stage lines are the flow's as given)";
+        b.name += "  [" + fold01_note + "]";
+    }
+
     // Layers 0 and 1 can share one kernel when a wave's two layer-0 node slots are exactly the two
     // children of one layer-1 node (see k_stage01p).
     bool can_fuse01() const {
@@ -1607,6 +1741,7 @@ std::unique_ptr<const FusedPlan> build_fused_plan(const TNode& root, const Fused
             try {
                 FusedOptions o = opt;
                 o.hoist = false;
+                o.fold01 = false;
                 given = Planner(root, std::move(plain), o).padded_flops;
             } catch (const Error&) {
             }
@@ -1614,7 +1749,7 @@ std::unique_ptr<const FusedPlan> build_fused_plan(const TNode& root, const Fused
     }
     try {
         Planner p(root, std::move(stages), opt);
-        p.padded_flops_given = given >= 0 ? given : p.padded_flops;
+        p.padded_flops_given = given >= 0 ? given : p.padded_flops - p.fold01_flops;
         return std::make_unique<const FusedPlan>(std::move(static_cast<FusedPlan&>(p)));
     } catch (const Error& e) {      // a structure the fused kernels do not cover: generic plan instead
         if (why_not) *why_not = e.what();

@@ -48,6 +48,8 @@ struct FusedOptions {
     int sum_lds_kib = 32;         // HIGSFA_SUM_LDS: KiB of second-affine fragments a k_stage_sum workgroup keeps in LDS (node group of a hoisted layer)
     bool hoist = false;           // fold each parent's first affine into its children's second affine where the link allows it (hoist_first_affines);
                                   // not an environment switch of the planner: the executor turns it on unless HIGSFA_NO_HOIST is set
+    bool fold01 = false;          // fold layer 0's second affine into layer 1's first inside the front kernels (Planner::plan_fold01); like hoist,
+                                  // the executor's switch: on unless HIGSFA_NO_FOLD01 is set
     static FusedOptions from_env() {
         FusedOptions o;
         o.no_rem4 = getenv("HIGSFA_NO_REM4") != nullptr;
@@ -118,12 +120,19 @@ struct HostStage {
     std::string name;
     bool sum_in = false;     // hoisted link: no first affine; kb1tab lists the children's tiles child-major (entry i: z tile i % mt1; k-steps = 1 real, 0 padding)
     int n_kids = 0;          // ... children per node (kb1 / mt1)
+    // The link 0 -> 1 folded (FusedPlan::fold01; stage 1 only).  Everything above stays as it is; the front kernels read these INSTEAD of
+    // stage 0's second-affine and stage 1's first-affine fragments and of both biases between them:
+    // fold_frag [node][child 0..1][function 0..1][tile: 0 = 16x16 form, 1 = 4x4 form][lane][4]: A fragments of F_c = A2_c A1[rows of c, :]
+    // (k = z0 feature 4 r + lane group of child c, per function; rows = z1 features), fold_bias [node][2 x 16]: z1's ONE bias vector.
+    std::vector<float> fold_frag, fold_bias;
 };
 
 struct FusedPlan {
     FusedOptions opt;
     int out_dim = 0;
     bool s0_transpose = false, fuse01 = false;
+    bool fold01 = false;                // the front kernels run the link 0 -> 1 folded (stages[1].fold_frag / fold_bias); implies fuse01
+    std::string fold01_note;            // why, or why not (stage 1's line of hg_flow_describe); empty where FusedOptions::fold01 is off
     std::vector<HostStage> stages;
     std::vector<int32_t> col_base, col_of;
     int tail_begin = -1;          // first stage of the top-of-hierarchy launch (k_tail); -1: none
@@ -131,6 +140,7 @@ struct FusedPlan {
     std::vector<SubRun> sub_runs;       // k_subtree runs (short batches)
     int max_nb = 0;
     int64_t padded_flops = 0;           // FLOPs per row this plan issues (hoisted links included)
+    int64_t fold01_flops = 0;           // ... what folding the link 0 -> 1 changed in it (<= 0)
     int64_t padded_flops_given = 0;     // ... the plan of the same flow with no link hoisted issues: what hg_info reports (== padded_flops where nothing was hoisted)
 
     // The per-call choices: pure functions of the plan and the batch's 16-row tiles.

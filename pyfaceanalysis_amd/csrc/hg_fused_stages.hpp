@@ -26,6 +26,7 @@ struct FNode {
     // iGSFA node: x0 = x - mean; s = sfa(expand(x0)) (scale folded in);
     // r = x0 - lr(s); q = pca(r); y = [s, q]
     bool is_ig = false, ig_has_lr = false;
+    bool was_ig = false;                // an iGSFA node that fold_igsfa turned into an ordinary one
     int ig_k = 0;
     std::vector<double> ig_mean;
     Aff ig_sfa, ig_lr, ig_pca;

@@ -26,6 +26,11 @@ for line in desc.splitlines():
     if m:
         stages.append(dict(zip(("stage", "nodes", "kb1", "mt1", "mt2", "tiles16", "m16", "m4"), map(int, m.groups()))))
 assert len(stages) == 11, desc
+# the link 0 -> 1 folded: the two stage lines keep the flow's counts as given, what the front kernel issues is in the note
+m = re.search(r"which then issues (\d+) x 16x16x4 for layer 0 and (\d+) x 16x16x4 \+ (\d+) x 4x4x1 for this layer", desc)
+if m:
+    stages[0]["m16"], stages[0]["m4"] = int(m.group(1)), 0
+    stages[1]["m16"], stages[1]["m4"] = int(m.group(2)), int(m.group(3))
 ctr = json.load(open(os.path.join(ROOT, "profiles", tag + "_counters.json")))
 launch_of = {}
 for key, v in ctr.items():
