@@ -366,6 +366,72 @@ int hg_frame_resize_host(int filter, const void* src, int format, int h, int w, 
 int hg_patcher_resize_device(hg_patcher* p, int filter, int flags, const void* src_dev, int format, int h, int w, int64_t ld_bytes,
                              int out_format, void* dst_dev, int out_h, int out_w, int64_t dst_ld_bytes, void* stream);
 
+/* --- Pose-normalised face crops: face_normalization_tools.normalize_image ---------------------------------------------------------
+ * What the reference does with the purged rows next (face_analysis.py:983-1013, 256 x 192 crops from approximate eyes; :1170-1222,
+ * 256 x 260 crops from the located eyes, the input of age / race / gender estimation): normalize_image (face_normalization_tools.py:111-329)
+ * for the one configuration both callers use — centering_mode "mid_eyes_inferred-mouth", rotation_mode "EyeLineRotation" or "noRotation",
+ * integer_rotation_center, no random background, mode "L", the mouth inferred from the eyes, and the scale methods
+ * "eyes_inferred-mouth_area" / "eyes_inferred-mouth_areaZ".  Bit for bit against PIL.
+ * Geometry, per face on the HOST, float64, the reference's operation order, one rounding per operation, the host's libm (the one Python's
+ * math uses), from eyes (lx, ly, rx, ry) in the coordinates of the frame passed in and its size (fw, fh):
+ *   exm = (rx + lx) / 2, eym = (ry + ly) / 2; dist = sqrt((lx - rx)^2 + (ly - ry)^2); eye_line_angle = atan2(ry - ly, rx - lx) * 180 / pi
+ *   mouth  mx = exm - (42 / 37)(ry - ly), my = eym + (42 / 37)(rx - lx); height = sqrt((exm - mx)^2 + (eym - my)^2); area = dist height / 2
+ *   scale  = sqrt(area / (37 * 42 / 2 * (37.5 / 37)^2)); ori_w = out_w scale, ori_h = out_h scale, each / 2 for areaZ
+ *   centre cx = (exm + mx) / 2, cy = (eym + my) / 2; cxi = (int)(cx + 0.5), cyi = (int)(cy + 0.5) (truncation)
+ *   crop   W = (int)(2 max(fw - 1 - cxi + 0.5, cxi + 0.5) + 0.5), H likewise (both odd); crop_x0 = cxi - (W - 1) / 2, crop_y0 likewise
+ *   angle  = eye_line_angle, or 0 when consts.rotate == 0; rad = -angle * pi / 180; Dx = cx - cxi, Dy = cy - cyi;
+ *          shift = (Dx cos(rad) - Dy sin(rad), Dy cos(rad) + Dx sin(rad))
+ *   box    ncx = (W - 1) / 2 + shift[0], ncy likewise; (ncx - (ori_w - 1) / 2, ncy - (ori_h - 1) / 2, ncx + (ori_w - 1) / 2 + 1, ncy + (ori_h - 1) / 2 + 1)
+ *   m      the matrix Image.rotate(angle) builds on a W x H image, default centre (W / 2, H / 2): round(cos, 15), round(sin, 15) of
+ *          -radians(angle % 360.0), m2 = m0 (-W / 2) + m1 (-H / 2) + 0 + W / 2, m5 likewise; rotated = 0 where angle % 360.0 == 0 (m the identity)
+ * Pixels, PIL composed as the reference composes it:
+ *   crop = im.transform((W, H), EXTENT, (crop_x0, crop_y0, crop_x0 + W, crop_y0 + H))      NEAREST, an integer box: a shift, 0 outside the frame
+ *   rot  = crop.rotate(angle, BICUBIC)                                                     the rule this build owns for cuicuilco's rotate_improved
+ *   out  = rot.transform((out_w, out_h), EXTENT, box, BICUBIC)
+ * with the BICUBIC arithmetic of hg_patcher_extract_filter_device above, applied RELATIVE TO THE CROP: clipping and the outside test use
+ * W x H, the crop's zero padding takes part in the taps, rot is uint8.  Only the rectangle of rot the final cut reads is ever computed
+ * (rect: columns x - 1 .. x + 2 of every output column that is inside, clipped to [0, W); rows likewise); the crop is never materialised.
+ * status, per face (a refused face has an all-zero image and geom; its neighbours are untouched; never an error of the whole call):
+ *   HG_NORM_OK 0; HG_NORM_EYES_SWAPPED 1: lx > rx (the reference exits); HG_NORM_NOT_FINITE 2: a coordinate, or the eye distance computed from them, is not finite;
+ *   HG_NORM_ZERO_DISTANCE 3: dist == 0; HG_NORM_CENTRE_RANGE 4: |cx| or |cy| above 2^20 (guards the int conversion). */
+#define HG_NORM_AREA  0   /* "eyes_inferred-mouth_area"  */
+#define HG_NORM_AREAZ 1   /* "eyes_inferred-mouth_areaZ": ori_w / 2, ori_h / 2 */
+enum hg_norm_status { HG_NORM_OK = 0, HG_NORM_EYES_SWAPPED = 1, HG_NORM_NOT_FINITE = 2, HG_NORM_ZERO_DISTANCE = 3, HG_NORM_CENTRE_RANGE = 4 };
+typedef struct hg_norm_consts {
+    int32_t out_w, out_h;     /* 1 .. 4096 each */
+    int32_t method;           /* HG_NORM_AREA / HG_NORM_AREAZ */
+    int32_t rotate;           /* 1: EyeLineRotation, 0: noRotation */
+} hg_norm_consts;
+typedef struct hg_norm_geom {
+    int32_t crop_x0, crop_y0, W, H;
+    double angle;
+    double shift[2];          /* Delta_x_rotated, Delta_y_rotated */
+    double m[6];
+    double box[4];
+    int32_t rotated, status;
+    int32_t rect[4];          /* x0, y0, width, height of the part of rot the cut reads (width = height = 0: no output pixel is inside) */
+} hg_norm_geom;
+/* eyes: (n, 4) doubles; geoms_out: n records.  HG_ERR_ARG: null pointers with n > 0, n < 0, out_w / out_h outside 1 .. 4096, an unknown
+ * method, rotate not 0 / 1, frame_w / frame_h outside 1 .. 2^24.  Plain C++, no device. */
+int hg_normalize_geometry_host(const double* eyes, int64_t n, int frame_w, int frame_h, const hg_norm_consts* consts, hg_norm_geom* geoms_out);
+/* The whole pixel rule on the host (no device): frame is frame_h rows of frame_w grey bytes, ld >= frame_w apart, any base address;
+ * out is n images of out_h x out_w bytes, ldo >= out_w * out_h apart.  Refusals as for the device entry below. */
+int hg_normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,
+                            uint8_t* out, int64_t ldo);
+/* The same on the patcher's device, enqueued on `stream`, no host wait; geoms_host is consumed before the call returns.  Grey uint8
+ * frames only (a colour frame goes through hg_frame_to_gray_device first).  All launch and scratch sizes come from the geoms.
+ *   staged       pass A computes every pixel of a face's rect ONCE into per-face scratch (uint8), pass B is the BICUBIC cut from it
+ *   tap by tap   a face whose rect holds more pixels than the cut has taps (16 out_w out_h: shrunk more than about 4 x per axis) computes
+ *                each tap's rotated pixel where it is used; no scratch.  Scratch is so at most 16 out_w out_h bytes per face.
+ * Both give the same bytes.  flags: bit 0 forces staging (refused, HG_ERR_ARG, if a rect exceeds 2^26 pixels), bit 1 forces tap by tap
+ * (for tests and A/B runs; not both); other bits must be 0.  The face records and the scratch live with the patcher and grow on demand
+ * (growing waits for `stream`); ONE STREAM PER PATCHER, as for the other entries.
+ * HG_ERR_ARG, nothing launched: a null pointer, a non-positive size, out_w / out_h above 4096, ld < frame_w, ldo < out_w * out_h, n < 0,
+ * a geom whose W / H disagree with the frame size (W != 2 max(frame_w - 1 - cxi, cxi) + 1 for cxi = crop_x0 + (W - 1) / 2) or whose rect
+ * leaves [0, W) x [0, H).  n == 0: HG_OK, nothing launched.  Faces with status != 0 get an all-zero image. */
+int hg_patcher_normalize_device(hg_patcher* p, int flags, const uint8_t* frame_dev, int frame_h, int frame_w, int64_t ld,
+                                const hg_norm_geom* geoms_host, int64_t n, int out_w, int out_h, uint8_t* out_dev, int64_t ldo, void* stream);
+
 /* --- Cascade glue on the device (the reference's stage loop between two hot calls) -----------------
  * update_current_subimage_coordinates (face_analysis.py:803-840) + identify_patches_to_discard (:842-887) for n
  * candidates from their regression outputs, then the boolean-mask compaction of FaceDetectUpdated.py:739-759 as

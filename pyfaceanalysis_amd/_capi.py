@@ -25,6 +25,7 @@ _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane
 _ENTRIES_SINCE_COLOR = ("hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format")
 _ENTRIES_SINCE_MULTI_TRACKING = ("hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device")
 _ENTRIES_SINCE_RESIZE = ("hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter")
+_ENTRIES_SINCE_NORMALIZE = ("hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device")
 _lib = None
 
 
@@ -57,6 +58,16 @@ class HgEyeConsts(C.Structure):         # hg_eye_consts (include/higsfa.h)
 class HgTrackedConsts(C.Structure):     # hg_tracked_consts (include/higsfa.h)
     _fields_ = [(n, C.c_double) for n in ("subimage_width", "subimage_height", "regression_width", "regression_height", "net_Dx", "net_Dy")]
 
+
+class HgNormConsts(C.Structure):        # hg_norm_consts (include/higsfa.h)
+    _fields_ = [(n, C.c_int32) for n in ("out_w", "out_h", "method", "rotate")]
+
+
+# hg_norm_geom as a numpy record (include/higsfa.h): 144 bytes, no padding
+NORM_GEOM_DTYPE = np.dtype([("crop_x0", np.int32), ("crop_y0", np.int32), ("W", np.int32), ("H", np.int32), ("angle", np.float64),
+                            ("shift", np.float64, (2,)), ("m", np.float64, (6,)), ("box", np.float64, (4,)), ("rotated", np.int32),
+                            ("status", np.int32), ("rect", np.int32, (4,))])
+HG_NORM_AREA, HG_NORM_AREAZ = 0, 1
 
 HG_STAGE = {"Disc": 0, "PosX": 1, "PosY": 2, "PAng": 3, "Scale": 4}
 
@@ -143,6 +154,9 @@ def lib():
         "hg_frame_resize_host": (C.c_int, [i32, vp, i32, i32, i32, i64, i32, vp, i32, i32, i64]),
         "hg_patcher_resize_device": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, i64, i32, vp, i32, i32, i64, vp]),
         "hg_cascade_set_prescale_filter": (C.c_int, [vp, i32]),
+        "hg_normalize_geometry_host": (C.c_int, [vp, i64, i32, i32, C.POINTER(HgNormConsts), vp]),
+        "hg_normalize_faces_host": (C.c_int, [vp, i32, i32, i64, vp, i64, i32, i32, vp, i64]),
+        "hg_patcher_normalize_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, i32, i32, vp, i64, vp]),
         "hg_eyes_set_interpolation": (C.c_int, [vp, i32]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
@@ -180,7 +194,8 @@ def lib():
         except AttributeError:
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
-            if name in _ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE and os.environ.get("HIGSFA_LIB"):
+            if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
+                        _ENTRIES_SINCE_NORMALIZE) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -207,6 +222,7 @@ EXPORTED_SYMBOLS = (
     "hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_patcher_extract_format_device", "hg_cascade_set_frame_format",
     "hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device",
     "hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter",
+    "hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

@@ -17,6 +17,7 @@
 
 #include "hg_common.hpp"
 #include "hg_hostpipe.hpp"
+#include "hg_normalize.hpp"
 #include "hg_resample.hpp"
 
 namespace {
@@ -654,6 +655,28 @@ int hg_frame_resize_host(int filter, const void* src, int format, int h, int w, 
         why = hg::frame_resize_host(filter, src, format, h, w, ld_bytes, out_format, dst, out_h, out_w, dst_ld_bytes);
     } catch (const std::bad_alloc&) {
         hg::set_last_error("resize: out of host memory");
+        return HG_ERR_NOMEM;
+    }
+    if (!why) return HG_OK;
+    hg::set_last_error(why);
+    return HG_ERR_ARG;
+}
+
+// Pose-normalised face crops on the host: the geometry and the pixel rule are plain C++ in hg_normalize.cpp
+int hg_normalize_geometry_host(const double* eyes, int64_t n, int frame_w, int frame_h, const hg_norm_consts* consts, hg_norm_geom* geoms_out) {
+    const char* why = hg::normalize_geometry_host(eyes, n, frame_w, frame_h, consts, geoms_out);
+    if (!why) return HG_OK;
+    hg::set_last_error(why);
+    return HG_ERR_ARG;
+}
+
+int hg_normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,
+                            uint8_t* out, int64_t ldo) {
+    const char* why = nullptr;
+    try {
+        why = hg::normalize_faces_host(frame, frame_h, frame_w, ld, geoms, n, out_w, out_h, out, ldo);
+    } catch (const std::bad_alloc&) {
+        hg::set_last_error("normalize: out of host memory");
         return HG_ERR_NOMEM;
     }
     if (!why) return HG_OK;

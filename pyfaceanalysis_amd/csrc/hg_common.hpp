@@ -184,5 +184,8 @@ int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* 
 void resample_state_free(void* state);
 void*& patcher_resample_state(hg_patcher* p);
 int patcher_device(const hg_patcher* p);
+// hg_normalize.hip: pose-normalised face crops (hg_patcher_normalize_device); its state hangs off the patcher the same way.
+void normalize_state_free(void* state);
+void*& patcher_normalize_state(hg_patcher* p);
 
 }  // namespace hg

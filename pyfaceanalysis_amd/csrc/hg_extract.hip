@@ -50,20 +50,21 @@ struct hg_patcher {
     Keyed keyed[4];
     int keyed_next = 0;
     void* resample = nullptr;   // hg_patcher_resize_device: the tables and the intermediate image (hg_resample.hip owns and frees it)
-    ~hg_patcher() { hg::resample_state_free(resample); }
+    void* normalize = nullptr;  // hg_patcher_normalize_device: face records and the staged rectangles (hg_normalize.hip owns and frees it)
+    ~hg_patcher() {
+        hg::resample_state_free(resample);
+        hg::normalize_state_free(normalize);
+    }
 };
 
 namespace hg { void set_last_error(const std::string& s); }
 
 // No contraction anywhere below: under hipcc's -ffp-contract=fast-honor-pragmas the __dadd_rn / __dmul_rn of the HIP headers are plain
-// operators, so a multiply feeding an add may become one fma.  The helpers are defined under the pragma: each operation rounds on its
-// own, as PIL's C doubles and Python floats do (tests/test_fp_contract.py checks the fma count).
+// operators, so a multiply feeding an add may become one fma.  The helpers (d_add ..., hg_filter_dev.hpp) are defined under the pragma:
+// each operation rounds on its own, as PIL's C doubles and Python floats do (tests/test_fp_contract.py checks the fma count).
 #pragma clang fp contract(off)
 namespace {
-__device__ __forceinline__ double d_add(double a, double b) { return a + b; }
-__device__ __forceinline__ double d_sub(double a, double b) { return a - b; }
-__device__ __forceinline__ double d_mul(double a, double b) { return a * b; }
-__device__ __forceinline__ double d_div(double a, double b) { return a / b; }
+#include "hg_filter_dev.hpp"      // d_add / d_sub / d_mul / d_div, FiltEnt, filter_coord, bicubic, filter_sample (shared with hg_normalize.hip)
 
 // Source index tables, one entry per thread.  PIL steps the source coordinate by repeated addition
 // (o += a per output pixel); to land on the same pixel in every case each thread repeats that sum from the start
@@ -465,37 +466,14 @@ __global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict_
 }
 
 // ---- BILINEAR / BICUBIC windows (include/higsfa.h, hg_patcher_extract_filter_device) --------------------------------------------
-// PIL's ImagingGenericTransform with affine_transform and bilinear_filter8 / bicubic_filter8 (Geometry.c), for uint8 frames.  An
-// EXTENT window is separable: the source coordinate of output column ox depends on ox alone, so a box has a table of w + h
-// entries as for NEAREST, each holding the integer part and the fraction of its coordinate (`i` = kFiltOutside where PIL's range test
-// leaves the output pixel 0).  Unlike the NEAREST tables these are closed forms, one multiply-add per entry: PIL evaluates the affine
-// map per pixel, it has no running sum here.
-struct FiltEnt {
-    double d;       // fraction: (xs - 0.5) - floor(xs - 0.5)
-    int32_t i;      // floor(xs - 0.5), in [-1, size - 1]
-    int32_t pad;
-};
-constexpr int32_t kFiltOutside = INT32_MIN;
+// PIL's ImagingGenericTransform with affine_transform and bilinear_filter8 / bicubic_filter8 (Geometry.c), for uint8 frames: the
+// coordinate entries (FiltEnt, filter_coord) and the filters (bicubic, filter_sample) are in hg_filter_dev.hpp.
 
 // Image.rotate's matrix as doubles (the 16.16 fixed point is NEAREST's); rotated = 0: angle % 360 == 0, the window is cut from the frame itself
 struct RotAff {
     double m[6];
     int32_t rotated, pad;
 };
-
-__device__ __forceinline__ FiltEnt filter_coord(double s, int lim) {
-    FiltEnt e;
-    e.pad = 0;
-    if (!(s >= 0.0 && s < (double)lim)) {       // (a NaN coordinate is outside too: nothing below may turn it into an index)
-        e.i = kFiltOutside;
-        e.d = 0.0;
-        return e;
-    }
-    s = d_sub(s, 0.5);
-    e.i = s < 0.0 ? (int)floor(s) : (int)s;      // Geometry.c FLOOR()
-    e.d = d_sub(s, (double)e.i);
-    return e;
-}
 
 // a0 xin + a1 yin + a2 with a = ((x1 - x0) / w, 0, x0, 0, (y1 - y0) / h, y0): the zero product adds nothing to the sum
 __device__ __forceinline__ FiltEnt filter_entry(const double* __restrict__ box, int e, int w, int h, int fw, int fh) {
@@ -517,40 +495,6 @@ __global__ void k_filter_tables(const double* __restrict__ boxes, int64_t n, int
         RotAff ra{};
         ra.rotated = rot_matrix(boxes, angs, b, ra.m) ? 1 : 0;
         rot[b] = ra;
-    }
-}
-
-__device__ __forceinline__ double bicubic(double v1, double v2, double v3, double v4, double d) {      // Geometry.c BICUBIC(), a = -0.5
-    const double p1 = v2;
-    const double p2 = d_add(-v1, v3);
-    const double p3 = d_sub(d_add(d_mul(2.0, d_sub(v1, v2)), v3), v4);
-    const double p4 = d_add(d_sub(d_add(-v1, v2), v3), v4);
-    return d_add(p1, d_mul(d, d_add(p2, d_mul(d, d_add(p3, d_mul(d, p4))))));
-}
-
-// One filtered, quantised pixel at (x + dx, y + dy) of a W x H uint8 image whose pixels come from tap(column, row); every
-// coordinate handed to tap lies inside the image.
-template <int F, typename Tap>
-__device__ __forceinline__ uint8_t filter_sample(Tap&& tap, int x, double dx, int y, double dy, int W, int H) {
-    auto clipx = [&](int v) { return v < 0 ? 0 : v < W ? v : W - 1; };
-    if constexpr (F == HG_FILTER_BILINEAR) {
-        const int x0 = clipx(x), x1 = clipx(x + 1);
-        auto row = [&](int yy) {
-            const double p0 = tap(x0, yy), p1 = tap(x1, yy);
-            return d_add(p0, d_mul(d_sub(p1, p0), dx));
-        };
-        const double v1 = row(y < 0 ? 0 : y);
-        const double v2 = y + 1 < H ? row(y + 1) : v1;
-        return (uint8_t)(int)d_add(v1, d_mul(d_sub(v2, v1), dy));
-    } else {
-        const int x0 = clipx(x - 1), x1 = clipx(x), x2 = clipx(x + 1), x3 = clipx(x + 2);
-        auto row = [&](int yy) { return bicubic(tap(x0, yy), tap(x1, yy), tap(x2, yy), tap(x3, yy), dx); };
-        const double r1 = row(y - 1 < 0 ? 0 : y - 1);
-        const double r2 = y >= 0 ? row(y) : r1;          // (y <= H - 1 always)
-        const double r3 = y + 1 < H ? row(y + 1) : r2;
-        const double r4 = y + 2 < H ? row(y + 2) : r3;
-        const double v = bicubic(r1, r2, r3, r4, dy);
-        return v <= 0.0 ? (uint8_t)0 : v >= 255.0 ? (uint8_t)255 : (uint8_t)(int)v;
     }
 }
 
@@ -979,6 +923,7 @@ int hg_patcher_extract(hg_patcher* p, const void* frame, int frame_dtype, int fr
 
 namespace hg {
 void*& patcher_resample_state(hg_patcher* p) { return p->resample; }
+void*& patcher_normalize_state(hg_patcher* p) { return p->normalize; }
 int patcher_device(const hg_patcher* p) { return p->device; }
 
 // NEAREST, unrotated windows from a frame of any format (hg_patcher_extract_format_device; key as for patcher_extract: the cascade's

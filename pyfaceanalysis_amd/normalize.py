@@ -1,0 +1,203 @@
+"""Pose-normalised face crops: ``face_normalization_tools.normalize_image`` on the device (include/higsfa.h, "normalize_image").
+
+What the reference does with the rows of ``detect_faces`` / ``FaceTracker`` next: ``save_pose_normalized_face_detections``
+(face_analysis.py:983-1013) makes 256 x 192 crops from the approximate eyes of every surviving box, ``estimate_age_race_gender``
+(face_analysis.py:1170-1222) 256 x 260 crops from the located eyes of every purged face — the image age, race and gender estimation
+starts from.  Both call ``normalize_image`` in one configuration, the one restated here: ``centering_mode="mid_eyes_inferred-mouth"``,
+``rotation_mode`` "EyeLineRotation" or "noRotation", ``integer_rotation_center=True``, ``allow_random_background=False``,
+``convert_format="L"``, the mouth inferred from the eyes, ``normalization_method`` "eyes_inferred-mouth_area" or
+"eyes_inferred-mouth_areaZ", any ``out_size``.  Everything else is refused with a ValueError that names it.
+
+The geometry is computed per face on the host in float64 (hg_normalize_geometry_host: the reference's operation order and the libm
+Python's ``math`` uses); the pixels are PIL's, bit for bit — ``crop.rotate(angle, BICUBIC)`` of the zero-padded crop around the face,
+then ``transform(out_size, EXTENT, box, BICUBIC)`` — computed on the device for the few thousand rotated pixels the cut reads
+(hg_patcher_normalize_device), or on the host (``normalize_host``).  Frames are grey uint8; a colour frame goes through
+``frames.to_gray`` first.
+
+EYE COORDINATES ARE IN THE COORDINATES OF THE FRAME PASSED IN.  The rows of ``detect_faces`` refer to the frame the cascade read —
+the prescaled one — so the caller passes that frame (``DeviceCascade.prescale(frame)``, or ``frames.resize(frame, size, "NEAREST")``)
+with ``faces[:, 5:9]``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+
+assert _capi.NORM_GEOM_DTYPE.itemsize == 144
+
+METHODS = {"eyes_inferred-mouth_area": _capi.HG_NORM_AREA, "eyes_inferred-mouth_areaZ": _capi.HG_NORM_AREAZ}
+ROTATION_MODES = {"EyeLineRotation": True, "noRotation": False}
+# the two callers of the reference: (out_size, normalization_method), face_analysis.py:1172-1179 and :986-995
+PRESETS = {"age": ((256, 260), "eyes_inferred-mouth_areaZ"), "pose": ((256, 192), "eyes_inferred-mouth_area")}
+STATUS = {0: "ok", 1: "left eye right of the right eye", 2: "a coordinate is not finite", 3: "the eyes coincide", 4: "the centre is beyond 2^20"}
+
+
+def check_configuration(normalization_method="eyes_inferred-mouth_area", centering_mode="mid_eyes_inferred-mouth", rotation_mode="EyeLineRotation",
+                        integer_rotation_center=True, allow_random_background=False, convert_format="L"):
+    """``normalize_image``'s keyword arguments -> (method code, rotate) for the configuration this build restates, or a ValueError naming
+    the argument that is not offered."""
+    if normalization_method not in METHODS:
+        raise ValueError("normalization_method %r is not offered (one of %s; \"eyes_mouth_area\" needs a real mouth)" % (normalization_method, ", ".join(METHODS)))
+    if centering_mode != "mid_eyes_inferred-mouth":
+        raise ValueError("centering_mode %r is not offered (only \"mid_eyes_inferred-mouth\")" % (centering_mode,))
+    if rotation_mode not in ROTATION_MODES:
+        raise ValueError("rotation_mode %r is not offered (\"EyeLineRotation\" or \"noRotation\")" % (rotation_mode,))
+    if not integer_rotation_center:
+        raise ValueError("integer_rotation_center=False is not offered")
+    if allow_random_background:
+        raise ValueError("allow_random_background=True is not offered")
+    if convert_format != "L":
+        raise ValueError("convert_format %r is not offered (only \"L\")" % (convert_format,))
+    return METHODS[normalization_method], ROTATION_MODES[rotation_mode]
+
+
+def _consts(out_size, method, rotate):
+    if isinstance(method, str):
+        if method not in METHODS:
+            raise ValueError("normalization_method %r is not offered (one of %s; \"eyes_mouth_area\" needs a real mouth)" % (method, ", ".join(METHODS)))
+        method = METHODS[method]
+    ow, oh = int(out_size[0]), int(out_size[1])
+    if not (1 <= ow <= 4096 and 1 <= oh <= 4096):
+        raise ValueError("out_size must be (width, height) with 1 .. 4096 pixels each, got %r" % (out_size,))
+    c = _capi.HgNormConsts()
+    c.out_w, c.out_h, c.method, c.rotate = ow, oh, int(method), 1 if rotate else 0
+    return c
+
+
+def _eyes(eyes):
+    e = np.asarray(eyes, dtype=np.float64)
+    if e.ndim > 2 or (e.ndim == 2 and e.shape[1] != 4) or e.size % 4:
+        raise ValueError("eyes must be (n, 4): left eye x, left eye y, right eye x, right eye y")
+    return np.ascontiguousarray(e.reshape(-1, 4))
+
+
+def geometry(eyes, frame_size, out_size=(256, 192), method="eyes_inferred-mouth_area", rotate=True):
+    """The geometry of ``normalize_image`` per face (hg_normalize_geometry_host): a record array of ``_capi.NORM_GEOM_DTYPE`` —
+    ``crop_x0, crop_y0, W, H, angle, shift, m, box, rotated, status, rect``.  ``frame_size``: (width, height), PIL's order."""
+    e = _eyes(eyes)
+    c = _consts(out_size, method, rotate)
+    g = np.zeros(e.shape[0], dtype=_capi.NORM_GEOM_DTYPE)
+    _capi.check(_capi.lib().hg_normalize_geometry_host(e.ctypes.data_as(C.c_void_p), e.shape[0], int(frame_size[0]), int(frame_size[1]), C.byref(c),
+                                                       g.ctypes.data_as(C.c_void_p)))
+    return g
+
+
+def _check_geoms(geoms):
+    g = np.ascontiguousarray(geoms)
+    if g.dtype != _capi.NORM_GEOM_DTYPE or g.ndim != 1:
+        raise ValueError("geoms must be the 1-d record array geometry() returns")
+    return g
+
+
+def normalize_host(frame, eyes=None, out_size=(256, 192), method="eyes_inferred-mouth_area", rotate=True, geoms=None):
+    """The host twin (hg_normalize_faces_host: plain C++, no device): ``frame`` an (H, W) uint8 array whose rows may be any number of
+    bytes >= W apart (a crop view of a larger frame is fine).  Returns (images (n, out_h, out_w) uint8, status (n,) int32).  ``geoms``:
+    the records of ``geometry`` for this frame size and ``out_size`` instead of ``eyes``."""
+    a = np.asarray(frame)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("frame must be a non-empty (H, W) uint8 array (grey; colour frames go through frames.to_gray_host first)")
+    if (a.shape[1] > 1 and a.strides[1] != 1) or (a.shape[0] > 1 and a.strides[0] < a.shape[1]):
+        a = np.ascontiguousarray(a)
+    h, w = a.shape
+    g = geometry(eyes, (w, h), out_size, method, rotate) if geoms is None else _check_geoms(geoms)
+    ow, oh = int(out_size[0]), int(out_size[1])
+    out = np.zeros((g.shape[0], oh, ow), dtype=np.uint8)
+    _capi.check(_capi.lib().hg_normalize_faces_host(a.ctypes.data_as(C.c_void_p), h, w, a.strides[0] if h > 1 else w, g.ctypes.data_as(C.c_void_p),
+                                                    g.shape[0], ow, oh, out.ctypes.data_as(C.c_void_p), ow * oh))
+    return out, g["status"].astype(np.int32)
+
+
+def approximate_eye_coords(boxes, angles=None):
+    """The eye coordinates ``compute_approximate_eye_boxes_coordinates(box, face_sampling=0.825, eye_sampling=2.3719, rot_angle=angle)``
+    returns first (face_analysis.py:87-122), for every box: (n, 4) left eye x, left eye y, right eye x, right eye y — what
+    ``save_pose_normalized_face_detections`` feeds to ``normalize_image``.  numpy, the reference's operation order."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    x0, y0, x1, y1 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    rot_angle = np.zeros(b.shape[0]) if angles is None else np.asarray(angles, dtype=np.float64).reshape(-1)
+    if rot_angle.shape[0] != b.shape[0]:
+        raise ValueError("angles must have one entry per box")
+    fc_x = (x0 + x1) / 2.0
+    fc_y = (y0 + y1) / 2.0
+    eye_dx = (37.0 / 2.0) * (np.abs(x1 - x0) / 64.0) / (2 * 0.825)
+    eye_dy = (42.0 / 2.0) * (np.abs(y1 - y0) / 64.0) / (2 * 0.825)
+    rad = rot_angle * np.pi / 180
+    eye_right_dx_rotated = eye_dx * np.cos(rad) - eye_dy * np.sin(rad)
+    eye_right_dy_rotated = eye_dy * np.cos(rad) + eye_dx * np.sin(rad)
+    eye_left_dx_rotated = (-1 * eye_dx) * np.cos(rad) - eye_dy * np.sin(rad)
+    eye_left_dy_rotated = eye_dy * np.cos(rad) + (-1 * eye_dx) * np.sin(rad)
+    eye_left_x = fc_x + 1 * eye_left_dx_rotated
+    eye_right_x = fc_x + 1 * eye_right_dx_rotated
+    eye_left_y = fc_y - eye_left_dy_rotated
+    eye_right_y = fc_y - eye_right_dy_rotated
+    return np.stack([eye_left_x, eye_left_y, eye_right_x, eye_right_y], axis=1)
+
+
+class FaceNormalizer(object):
+    """``normalize_image`` for the faces of one frame, on the device.  ``preset``: "age" — (256, 260), areaZ, the crops
+    ``estimate_age_race_gender`` makes (face_analysis.py:1172-1179) — or "pose" — (256, 192), area, those of
+    ``save_pose_normalized_face_detections`` (:986-995); ``out_size`` / ``method`` override either part.  ``rotate``: True
+    "EyeLineRotation", False "noRotation".  ``patcher``: a ``patches.Patcher`` to share (one stream per patcher); None: its own."""
+
+    def __init__(self, device=0, preset="age", out_size=None, method=None, rotate=True, patcher=None):
+        from .patches import Patcher
+        if preset not in PRESETS:
+            raise ValueError("unknown preset %r (one of %s)" % (preset, ", ".join(PRESETS)))
+        size, meth = PRESETS[preset]
+        self.out_size = tuple(int(v) for v in (out_size if out_size is not None else size))
+        self.method = method if method is not None else meth
+        self.rotate = bool(rotate)
+        _consts(self.out_size, self.method, self.rotate)      # refuses what is not offered now, not at the first frame
+        self.device = int(device)
+        self._own = patcher is None
+        self._patcher = Patcher(self.device) if patcher is None else patcher
+
+    def geometry(self, eyes, frame_size):
+        """The records of every face for a frame of ``frame_size`` = (width, height)."""
+        return geometry(eyes, frame_size, self.out_size, self.method, self.rotate)
+
+    def normalize(self, frame, eyes=None, geoms=None, out=None, flags=0):
+        """``frame``: an (H, W) uint8 device tensor with contiguous rows, any row pitch (a pitched buffer, a crop of a larger frame);
+        ``eyes``: (n, 4) in that frame's coordinates (or ``geoms`` from ``geometry`` for that frame size).  Enqueued on the current
+        stream of the frame's device, no host wait.  Returns (images, status): images an (n, out_h, out_w) uint8 device tensor (``out``
+        if given: that shape, each image contiguous, ``stride(0) >= out_w * out_h``), all zero for a face whose status is not 0; status
+        an int32 ndarray (``STATUS``).  ``flags`` is for tests and A/B runs (1: every face staged, 2: every face tap by tap; same bytes)."""
+        import torch as t
+        from .eyes import check_frame
+        if not isinstance(frame, t.Tensor) or not frame.is_cuda:
+            raise ValueError("normalize takes a device tensor (normalize_host takes a host array)")
+        if frame.dtype != t.uint8:
+            raise ValueError("frame must be grey uint8 (a float frame is not offered; a colour frame goes through frames.to_gray first)")
+        check_frame(t, frame, frame.device)
+        h, w = int(frame.shape[0]), int(frame.shape[1])
+        if h == 0 or w == 0:
+            raise ValueError("frame must not be empty")
+        if (frame.device.index or 0) != self.device:
+            raise ValueError("frame is on %s, the normalizer on device %d" % (frame.device, self.device))
+        g = self.geometry(eyes, (w, h)) if geoms is None else _check_geoms(geoms)
+        n = int(g.shape[0])
+        ow, oh = self.out_size
+        if out is None:
+            out = t.empty((n, oh, ow), dtype=t.uint8, device=frame.device)
+        elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or out.device != frame.device or tuple(out.shape) != (n, oh, ow)
+              or (ow > 1 and out.stride(2) != 1) or (oh > 1 and out.stride(1) != ow) or (n > 1 and out.stride(0) < ow * oh)):
+            raise ValueError("out must be a (%d, %d, %d) uint8 tensor on %s whose images are contiguous" % (n, oh, ow, frame.device))
+        if n:
+            _capi.check(_capi.lib().hg_patcher_normalize_device(
+                self._patcher._handle(), int(flags), frame.data_ptr(), h, w, frame.stride(0) if h > 1 else w, g.ctypes.data_as(C.c_void_p), n, ow, oh,
+                out.data_ptr(), out.stride(0) if n > 1 else ow * oh, t.cuda.current_stream(frame.device).cuda_stream))
+        return out, g["status"].astype(np.int32)
+
+    def close(self):
+        """Frees the patcher it owns; the caller makes sure the device has finished with it (as for ``Patcher.close``)."""
+        if self._own and self._patcher is not None:
+            self._patcher.close()
+        self._patcher = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
