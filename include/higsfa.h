@@ -702,6 +702,59 @@ int hg_train_apply_device(const void* x_dev, int x_dtype, int64_t n, int64_t ldx
                           int32_t d, const double* mean_host, const double* w_host, int32_t p, int32_t n_funcs,
                           const int32_t* func_kinds, const double* func_expos, double* out_dev, int64_t ldo, int device);
 
+/* --- Age, race and gender estimation (estimate_age_race_gender, face_analysis.py:1170-1306; FaceDetectUpdated.py:1186-1187) ----------
+ * Per purged face: the pose-normalised crop (hg_patcher_normalize_device with crop_w x crop_h, method, rotate), ONE patch_w x patch_h
+ * sub-image of it with the contrast step, the age network (networks[num_networks - 3]; the Race and Gender stages have no network and
+ * reuse its features, Pipelines/Pipeline_experimental.txt:62-70), and up to three regressions on the same features: age with its std,
+ * race, gender.  The sub-image is cut by cuicuilco's load_image_data_monoprocessor, which is not available; the three rules are the
+ * build's, tested against PIL:
+ *   box       in crop coordinates, a plain parameter (pyfaceanalysis_amd.analysis.age_patch_box evaluates the reference's visible
+ *             expressions, :1182-1197: about (36.8, 31.96, 219.2, 214.36) for the reference's constants)
+ *   cut       crop.transform((patch_w, patch_h), EXTENT, box, filter): the rule of hg_patcher_extract_filter_device without rotation;
+ *             a box partly outside the crop reads zeros there
+ *   contrast  the eye step's: S1 = sum p, S2 = sum p^2 as int64 over the N patch pixels (the zeros included), mean = S1 / N,
+ *             std = sqrt((N S2 - S1^2) / (N N)), p' = (p - mean) / (std / target_std + 1e-8) + target_mean as float32; clip = 1 clips
+ *             p' to [0, 255] first (face_analysis.py:327, the only rule the reference shows), clip = 0 does not (the reference's
+ *             obj_avgs = 0.0 makes sense only unclipped).  The targets are required.
+ * Patches of at most 16384 pixels can go through one fused kernel (cut + contrast, one workgroup per face); larger ones, and any patch
+ * with flag bit 0, go through hg_patcher_extract_filter_device per face and a contrast kernel.  Same bits either way.  The default is
+ * the fused kernel where it measured faster (every case but BICUBIC with fewer than four faces; profiles/r16_analysis_times.txt). */
+typedef struct hg_estimator hg_estimator;
+typedef struct hg_estimator_consts {
+    int32_t crop_w, crop_h, method, rotate;   /* as hg_norm_consts: 256, 260, HG_NORM_AREAZ, 1                      */
+    int32_t patch_w, patch_h;                 /* 96 x 96; at most 4096 per side and 65536 pixels                    */
+    int32_t filter;                           /* enum hg_filter                                                     */
+    int32_t clip;                             /* 1 / 0                                                              */
+    double  box[4];                           /* x0, y0, x1, y1 in crop coordinates, finite                         */
+    double  target_mean, target_std;          /* required; target_std > 0                                           */
+    int32_t n_features, reserved;             /* feature columns kept (>= every classifier's input_dim); 0          */
+} hg_estimator_consts;
+/* Any of age / race / gender may be null (that estimate is not computed), not all three.  The flow's input width is patch_w * patch_h
+ * and it gives at least n_features columns; every classifier's input_dim is <= n_features.  The flow and the patcher live on `device`
+ * (the classifiers too).  HG_ERR_ARG / HG_ERR_DIM on a violation, checked in this order: constants, the flow's shape, the classifiers,
+ * the devices.  All handles stay owned by the caller and must outlive the estimator. */
+int hg_estimator_create(hg_flow* flow, hg_gauss* age, hg_gauss* race, hg_gauss* gender, const hg_estimator_consts* consts, hg_patcher* patcher,
+                        int device, hg_estimator** out);
+void hg_estimator_free(hg_estimator* e);
+/* The patch step alone: crops_dev n uint8 images of crop_h x crop_w, crop_stride >= crop_w * crop_h bytes apart -> patches_dev n rows of
+ * patch_w * patch_h float32, ldp >= that many floats apart.  flags: bit 0 forces the composed path, bit 1 the fused kernel (HG_ERR_ARG
+ * above 16384 pixels; not both); other bits HG_ERR_ARG.  Enqueued on `stream`. */
+int hg_estimator_patches_device(hg_estimator* e, int flags, const uint8_t* crops_dev, int64_t crop_stride, int64_t n, float* patches_dev, int64_t ldp,
+                                void* stream);
+/* The whole chain for the n faces of geoms_host (hg_normalize_geometry_host for this frame size and the estimator's crop constants;
+ * consumed before the call returns) on frame_dev ((frame_h, frame_w) grey uint8, rows ld bytes apart): normalise into the estimator's
+ * crop scratch, patches, hg_flow_execute_device (float32, n_features columns), age through hg_gauss_regression_device with its std, race
+ * and gender through hg_gauss_regression_multi_device, a finishing kernel.  Enqueued on `stream`; the host is not waited for.
+ * out_dev: (4, n) float64, rows out_stride >= n apart: age, age_std, race, gender.  The rows of an absent classifier hold the reference's
+ * initial values 0, 0, 10, 10 (face_analysis.py:1201-1204).  A refused face (geoms_host[i].status != 0) has NaN in all four rows; no
+ * other face's bits depend on it.  patches_dev (n, patch_w * patch_h) / features_dev (n, n_features), float32, contiguous, nullable:
+ * the intermediates.  flags as above.  Scratch (crops, patches, features, refused flags) grows on demand, and growing waits for `stream`;
+ * ONE STREAM PER ESTIMATOR, the patcher's rule (the patcher, the flow and the classifiers must not be in use elsewhere meanwhile).
+ * n == 0: HG_OK, nothing launched. */
+int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* frame_dev, int frame_h, int frame_w, int64_t ld,
+                                 const hg_norm_geom* geoms_host, int64_t n, double* out_dev, int64_t out_stride, float* patches_dev,
+                                 float* features_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ _ENTRIES_SINCE_COLOR = ("hg_frame_to_gray_device", "hg_frame_to_gray_host", "hg_
 _ENTRIES_SINCE_MULTI_TRACKING = ("hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device")
 _ENTRIES_SINCE_RESIZE = ("hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter")
 _ENTRIES_SINCE_NORMALIZE = ("hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device")
+_ENTRIES_SINCE_ESTIMATION = ("hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device")
 _lib = None
 
 
@@ -61,6 +62,11 @@ class HgTrackedConsts(C.Structure):     # hg_tracked_consts (include/higsfa.h)
 
 class HgNormConsts(C.Structure):        # hg_norm_consts (include/higsfa.h)
     _fields_ = [(n, C.c_int32) for n in ("out_w", "out_h", "method", "rotate")]
+
+
+class HgEstimatorConsts(C.Structure):   # hg_estimator_consts (include/higsfa.h)
+    _fields_ = ([(n, C.c_int32) for n in ("crop_w", "crop_h", "method", "rotate", "patch_w", "patch_h", "filter", "clip")] + [("box", C.c_double * 4)] +
+                [(n, C.c_double) for n in ("target_mean", "target_std")] + [(n, C.c_int32) for n in ("n_features", "reserved")])
 
 
 # hg_norm_geom as a numpy record (include/higsfa.h): 144 bytes, no padding
@@ -158,6 +164,10 @@ def lib():
         "hg_normalize_faces_host": (C.c_int, [vp, i32, i32, i64, vp, i64, i32, i32, vp, i64]),
         "hg_patcher_normalize_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, i32, i32, vp, i64, vp]),
         "hg_eyes_set_interpolation": (C.c_int, [vp, i32]),
+        "hg_estimator_create": (C.c_int, [vp, vp, vp, vp, C.POINTER(HgEstimatorConsts), vp, i32, C.POINTER(vp)]),
+        "hg_estimator_free": (None, [vp]),
+        "hg_estimator_patches_device": (C.c_int, [vp, i32, vp, i64, i64, vp, i64, vp]),
+        "hg_estimator_estimate_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, vp, i64, vp, vp, vp]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_gather_rows_device": (C.c_int, [i32, vp, vp, i64, vp, vp, i64, vp]),
@@ -195,7 +205,7 @@ def lib():
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
-                        _ENTRIES_SINCE_NORMALIZE) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -223,6 +233,7 @@ EXPORTED_SYMBOLS = (
     "hg_cascade_tracked_grid_multi_device", "hg_tracker_create_multi", "hg_tracker_step_frame_multi_device",
     "hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter",
     "hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device",
+    "hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,
