@@ -785,7 +785,7 @@ public:
             else if (s.from_x)
                 covered = launch_front(L, s, d, P, x, x_dtype, ldx, n, n_tiles, cur, st) ? 2 : 1;
             else if (s.kind == 3)
-                launch_prod(s, d, P, n_tiles, st);
+                launch_prod(s, d, P, n_tiles, si, st);
             else if (!launch_splitm(s, P, n_tiles, st))
                 launch_stage(s, P, n_tiles, si, st);
             if (covered == 1) std::swap(cur, nxt);      // (fused front: layer 1 wrote `cur`, which stage 2 reads)
@@ -1215,7 +1215,7 @@ private:
             fail(HG_ERR_ARG, "output dtype must be f32 or f64");
     }
 
-    void launch_prod(const HostStage& s, const StageDev& d, StageParams& P, int n_tiles, hipStream_t st) {
+    void launch_prod(const HostStage& s, const StageDev& d, StageParams& P, int n_tiles, int si, hipStream_t st) {
         // per-wave z image: T * mt1 KiB; the node group takes what is left of ~52 KiB (three workgroups per CU: the product
         // columns are LDS reads and multiplies between short MFMA runs, which only other waves can cover), more if one node needs it.
         // (The shape is chosen over single nodes: the node group follows from it.)
@@ -1245,6 +1245,7 @@ private:
         const int64_t blocks = (int64_t)((n_groups + 7) / 8) * 8 * tile_parts;
         if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
         set_lds_limit(fn, lds_bytes);
+        if (plan_->opt.debug) fprintf(stderr, "[prod stage %d] nodes %d mt1 %d mt2 %d neb %d shape %dx%d npg %d node_groups %d tile_groups %d parts %d\n", si, s.n_nodes, s.mt1, s.mt2, s.neb, nw, T, npg, n_groups, tile_groups, tile_parts);
         hipLaunchKernelGGL(fn, (unsigned)blocks, nw * 64, lds_bytes, st, P);
     }
 
