@@ -602,6 +602,51 @@ int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* 
                                          int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, int32_t* stage_counts,
                                          int64_t* rows_executed, void* stream);
 
+/* --- A stack of same-size frames through one pooled pass (the reference's batch mode: many images, one set of networks) -----
+ * One frame's windows do not fill the device; the windows of B frames of ONE size are one batch.  Every row of the cascade is
+ * independent of its batch and every compaction keeps row order, so each result below is DEFINED as what the per-frame entry returns
+ * for that frame, bit for bit (tests/test_frame_batch_gpu.py).
+ *
+ * The patcher: row i is the window boxes_dev[i], rotated by delta_angs_dev[i] if given, cut from frame row_frame_dev[i] of a stack of
+ * n_frames grey uint8 frames, all frame_h x frame_w with row stride ld, frame f starting frame_stride BYTES behind frame f - 1 — any
+ * value >= (frame_h - 1) ld + frame_w, not necessarily a multiple of ld: the frames may be slices of a larger buffer.  Rule, tables and
+ * bytes are those of hg_patcher_extract_filter_device on that one frame (NEAREST, BILINEAR, BICUBIC; rotated or not; any out_dtype).
+ * A row whose frame index lies outside [0, n_frames) is an all-zero window; no address is formed from such an index.
+ * HG_ERR_ARG, nothing launched and neither the handle nor a data pointer dereferenced: a null pointer (delta_angs_dev and stream may be
+ * null), n_frames < 1, frame_stride below the bound, ld < frame_w, n < 0, an unknown filter, a bad output size / dtype / ldo.  n == 0:
+ * HG_OK.  Enqueued on `stream`. */
+int hg_patcher_extract_frames_device(hg_patcher* p, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                                     int frame_w, int64_t ld, const double* boxes_dev, const double* delta_angs_dev,
+                                     const int32_t* row_frame_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo,
+                                     void* stream);
+/* hg_cascade_detect_frame_device for a stack: frames_dev is frame 0 of n_frames frames in the cascade's frame format, frame_stride
+ * and ld in bytes for a colour format as for the other entries.  Each frame is prescaled / converted by the code a single frame runs
+ * (one pass per frame, the configured prescale filter) into a cascade-owned grey stack; grey frames without a prescale are read in
+ * place.  The grid of the prescaled size is laid out once (n0 windows) and the candidates are n_frames copies of it: window f n0 + j is
+ * window j of frame f.  The stage loop is the one loop — groups, the count read after Disc groups, the chunked glue above 8192
+ * candidates — on n_frames n0 candidates.  Survivors come out ordered by frame and, within a frame, in that frame's own order:
+ * frame f's are rows frame_first[f] .. frame_first[f + 1] (frame_first: n_frames + 1 entries, host), out_orig_index the index within
+ * the frame's grid.  stage_counts / *rows_executed: the pooled totals — the sum of the per-frame counts where those are read, -1 where
+ * they are not (a single frame that has run out of candidates reports 0 for the stages behind without reading anything; pooled, such a
+ * stage is -1 as long as another frame has candidates).  HG_ERR_ARG before anything is launched or written: n_frames < 1 or > HG_MAX_STACK_FRAMES, n_frames n0 above the window
+ * bound of the other entries (2^31 / 64), a bad frame geometry (as the other entries, and frame_stride below
+ * (frame_h - 1) ld + frame_w bytes-per-pixel), a null frame_first.  Frames of different sizes do not share a call.  Synchronous. */
+#define HG_MAX_STACK_FRAMES 1024
+int hg_cascade_detect_frames_device(hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
+                                    int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels,
+                                    double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence, int64_t out_cap,
+                                    int32_t* frame_first, int32_t* stage_counts, int64_t* rows_executed, void* stream);
+/* hg_cascade_detect_faces_frame_device for a stack: the pooled stage loop, then the eye step on ALL survivors as one batch (every eye
+ * row cut from its face's frame), the discard and the row assembly, and the purge PER FRAME — it is a per-image rule — one workgroup per
+ * frame over that frame's rows.  out_rows: the kept rows ordered by frame, frame f's at frame_first[f] .. frame_first[f + 1];
+ * n_before_purge (n_frames entries): faces of every frame after the discard.  The host reads nothing between the stage loop's last
+ * survivor count and the one read-back of counts and rows.  HG_ERR_ARG, writing no row, when out_cap is below the kept total (a frame
+ * may keep its count + 1).  Refusals as above.  Synchronous. */
+int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                                          int frame_w, int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels,
+                                          int n_levels, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge,
+                                          int32_t* stage_counts, int64_t* rows_executed, void* stream);
+
 /* --- Tracking one face across a stream of frames (the reference's track_single_face mode) ---------------------------------
  * Once a frame has produced a face, its first purged detection is carried over (FaceDetectUpdated.py:1189-1195) and the next
  * frame searches NINE windows instead of the pyramid: one sampling value from the size of that box (face_analysis.py:576-585),

@@ -15,10 +15,11 @@ HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC = 0, 2, 3      # enum h
 # enum hg_resample: PIL's codes again, but a DIFFERENT operation (Image.resize, not Image.transform): frames.resize, the cascade's prescale
 HG_RESAMPLE_NEAREST, HG_RESAMPLE_LANCZOS, HG_RESAMPLE_BILINEAR, HG_RESAMPLE_BICUBIC, HG_RESAMPLE_BOX, HG_RESAMPLE_HAMMING = 0, 1, 2, 3, 4, 5
 HG_FRAME_L, HG_FRAME_RGB, HG_FRAME_BGR, HG_FRAME_RGBA, HG_FRAME_BGRA = 0, 1, 2, 3, 4      # frame formats (pyfaceanalysis_amd/frames.py)
+HG_MAX_STACK_FRAMES = 1024      # frames in one call of the stack entries (include/higsfa.h)
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
@@ -27,6 +28,7 @@ _ENTRIES_SINCE_MULTI_TRACKING = ("hg_cascade_tracked_grid_multi_device", "hg_tra
 _ENTRIES_SINCE_RESIZE = ("hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter")
 _ENTRIES_SINCE_NORMALIZE = ("hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device")
 _ENTRIES_SINCE_ESTIMATION = ("hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device")
+_ENTRIES_SINCE_FRAME_STACKS = ("hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device")
 _lib = None
 
 
@@ -184,6 +186,11 @@ def lib():
         "hg_purge_detections_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_cascade_detect_faces_frame_device": (C.c_int, [vp, vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
                                                            C.POINTER(i64), vp, C.POINTER(i64), vp]),
+        "hg_patcher_extract_frames_device": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, i64, vp, vp, vp, i64, i32, i32, vp, i32, i64, vp]),
+        "hg_cascade_detect_frames_device": (C.c_int, [vp, vp, i32, i64, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, vp, vp, vp, i64, vp, vp,
+                                                      C.POINTER(i64), vp]),
+        "hg_cascade_detect_faces_frames_device": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, vp, vp, vp,
+                                                            C.POINTER(i64), vp]),
         "hg_cascade_tracked_grid_device": (C.c_int, [i32, C.POINTER(HgTrackedConsts), vp, vp, vp, vp]),
         "hg_tracker_create": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), C.POINTER(vp)]),
         "hg_tracker_free": (None, [vp]),
@@ -205,7 +212,7 @@ def lib():
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
-                        _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -234,6 +241,7 @@ EXPORTED_SYMBOLS = (
     "hg_frame_resize_host", "hg_patcher_resize_device", "hg_cascade_set_prescale_filter",
     "hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device",
     "hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device",
+    "hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

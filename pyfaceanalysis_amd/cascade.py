@@ -315,6 +315,106 @@ class DeviceCascade(object):
         return dict(faces=rows[:n_out.value].copy(), n_before_purge=n_before.value, counts=counts.tolist(), rows_executed=n_rows.value,
                     n_windows=n0)
 
+    def _check_stack(self, stack):
+        """A stack of same-size frames as one tensor, or ValueError; None for an empty stack.  (B, H, W) uint8, (B, H, W, C) for a colour
+        ``frame_format``; rows contiguous (pixels packed), ``stride(1)`` at least a row's bytes — a broadcast view has 0 and is refused
+        as ``ld < frame_w`` is — and ``stride(0)`` at least a frame's reach, (H - 1) stride(1) + W C: the frames may be every second
+        frame of a larger stack or crops of larger frames.  A list or tuple of same-shaped tensors is stacked (``torch.stack``).
+        Shape, dtype and strides are checked before the device, which is checked before the library is touched."""
+        t = self.torch
+        c = frames.CHANNELS[self.frame_format]
+        color = self.frame_format != _capi.HG_FRAME_L
+        shape = "(B, H, W, %d)" % c if color else "(B, H, W)"
+        if isinstance(stack, (list, tuple)):
+            if len(stack) == 0:
+                return None
+            if any(not isinstance(f, t.Tensor) or f.shape != stack[0].shape or f.dtype != stack[0].dtype or f.device != stack[0].device for f in stack):
+                raise ValueError("a list of frames must hold tensors of one shape, dtype and device (frames of different sizes do not share a call)")
+            stack = t.stack(list(stack))
+        if not isinstance(stack, t.Tensor) or stack.dim() != (4 if color else 3) or stack.dtype != t.uint8 or (color and stack.shape[3] != c):
+            raise ValueError("a stack of frames must be a %s uint8 tensor" % shape)
+        b, fh, fw = int(stack.shape[0]), int(stack.shape[1]), int(stack.shape[2])
+        if b == 0:
+            return None
+        if fh == 0 or fw == 0:
+            raise ValueError("a stack of empty frames")
+        if b > _capi.HG_MAX_STACK_FRAMES:
+            raise ValueError("%d frames in a stack, at most %d" % (b, _capi.HG_MAX_STACK_FRAMES))
+        if (color and (stack.stride(3) != 1 or stack.stride(2) != c)) or (not color and stack.stride(2) != 1):
+            raise ValueError("the frames of a stack must have contiguous rows (packed pixels), got strides %s" % (tuple(stack.stride()),))
+        if fh > 1 and stack.stride(1) < fw * c:
+            raise ValueError("rows %d bytes apart hold %d bytes: a broadcast or overlapping view is not a frame" % (stack.stride(1), fw * c))
+        ld = stack.stride(1) if fh > 1 else fw * c
+        if b > 1 and stack.stride(0) < (fh - 1) * ld + fw * c:
+            raise ValueError("frames %d bytes apart reach over %d bytes: a broadcast or overlapping view is not a stack" %
+                             (stack.stride(0), (fh - 1) * ld + fw * c))
+        if stack.device != self.dev:
+            raise ValueError("the stack must live on %s" % (self.dev,))
+        return stack
+
+    def _stack_plan(self, what, stack, smallest_face, prescale_size):
+        """Everything a stack call needs that depends on (B, frame size, smallest_face, prescale size) alone, computed once and kept like
+        detect_frame's plans, and the geometry of this stack."""
+        b, fh, fw = int(stack.shape[0]), int(stack.shape[1]), int(stack.shape[2])
+        c = frames.CHANNELS[self.frame_format]
+        key = (what, b, fw, fh, float(smallest_face), int(prescale_size or 0))
+        plan = self._frames.get(key)
+        if plan is None:
+            pw, ph = grid.prescaled_size(fw, fh, prescale_size) if prescale_size else (fw, fh)
+            pre = (pw, ph) if (pw, ph) != (fw, fh) else (0, 0)
+            levels, n_levels, n0 = frame_levels(pw, ph, smallest_face, self.pipeline, (self.w, self.h))
+            first, counts = np.zeros(b + 1, dtype=np.int32), np.zeros(len(self.stages), dtype=np.int32)
+            if what == "stack":
+                bufs = (np.empty((b * n0, 4)), np.empty(b * n0), np.empty(b * n0, dtype=np.int32), np.empty(b * n0))
+            else:
+                bufs = (np.empty((b * (n0 + 1), 10)), np.zeros(b, dtype=np.int32))      # the purge may keep n + 1 rows of every frame
+            plan = self._frames[key] = (pre, levels, n_levels, n0, bufs, first, counts, C.c_int64())
+        ld = stack.stride(1) if fh > 1 else fw * c
+        stride = stack.stride(0) if b > 1 else (fh - 1) * ld + fw * c
+        return plan, (b, fh, fw, ld, stride)
+
+    def detect_frames(self, stack, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+        """``detect_frame`` for a stack of B same-size frames as ONE pooled pass (hg_cascade_detect_frames_device): the windows of all
+        frames are one batch of candidates through the stage loop.  stack: see ``_check_stack``.  Returns ``frames``, a list of B dicts
+        with coords, angles, orig_index, confidence — array for array what ``detect_frame`` returns for that frame — and the pooled
+        counts (the sum of the per-frame counts, -1 where those are -1), rows_executed and n_windows (B times one frame's).  An empty
+        stack returns an empty list without touching the library."""
+        t = self.torch
+        stack = self._check_stack(stack)
+        if stack is None:
+            return dict(frames=[], counts=[0] * len(self.stages), rows_executed=0, n_windows=0)
+        (pre, levels, n_levels, n0, bufs, first, counts, rows), (b, fh, fw, ld, stride) = self._stack_plan("stack", stack, smallest_face, prescale_size)
+        coords, angles, oidx, conf = bufs
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _capi.check(_capi.lib().hg_cascade_detect_frames_device(
+            self._handle(), stack.data_ptr(), b, stride, fh, fw, ld, pre[0], pre[1], levels, n_levels, vp(coords), vp(angles), vp(oidx), vp(conf), b * n0,
+            vp(first), vp(counts), C.byref(rows), t.cuda.current_stream(self.dev).cuda_stream))
+        out = []
+        for f in range(b):
+            lo, hi = int(first[f]), int(first[f + 1])
+            out.append(dict(coords=coords[lo:hi].copy(), angles=angles[lo:hi].copy(), orig_index=oidx[lo:hi].astype(np.int64),
+                            confidence=conf[lo:hi].copy()))
+        return dict(frames=out, counts=counts.tolist(), rows_executed=rows.value, n_windows=b * n0)
+
+    def detect_faces_frames(self, stack, eyes, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+        """``detect_faces`` for a stack of B same-size frames (hg_cascade_detect_faces_frames_device): the pooled stage loop, the eye step
+        on all survivors as one batch, the purge per frame.  Returns ``faces``, a list of B (m_b, 10) arrays — what ``detect_faces``
+        returns for that frame — ``n_before_purge``, a list of B, and the pooled counts, rows_executed, n_windows."""
+        t = self.torch
+        if eyes.device != self.device:
+            raise ValueError("eye locator on device %d, cascade on device %d" % (eyes.device, self.device))
+        stack = self._check_stack(stack)
+        if stack is None:
+            return dict(faces=[], n_before_purge=[], counts=[0] * len(self.stages), rows_executed=0, n_windows=0)
+        (pre, levels, n_levels, n0, bufs, first, counts, n_rows), (b, fh, fw, ld, stride) = self._stack_plan("stack faces", stack, smallest_face, prescale_size)
+        rows, before = bufs
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _capi.check(_capi.lib().hg_cascade_detect_faces_frames_device(
+            self._handle(), eyes._handle(), stack.data_ptr(), b, stride, fh, fw, ld, pre[0], pre[1], levels, n_levels, vp(rows), len(rows), vp(first),
+            vp(before), vp(counts), C.byref(n_rows), t.cuda.current_stream(self.dev).cuda_stream))
+        return dict(faces=[rows[int(first[f]):int(first[f + 1])].copy() for f in range(b)], n_before_purge=before.tolist(), counts=counts.tolist(),
+                    rows_executed=n_rows.value, n_windows=b * n0)
+
     def close(self):
         if self._h is not None:
             _capi.lib().hg_cascade_free(self._h)

@@ -27,6 +27,9 @@ void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int
                              const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts,
                              const int32_t** row_src, const int32_t** kept_idx, hipStream_t st);
 void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts);
+void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const double* boxes,
+                      const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n, double* out_rows, int64_t out_cap,
+                      int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
 int eyes_device(const hg_eyes* e);
 }
 
@@ -244,6 +247,28 @@ __global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coor
         conf[i] = 0.0;
         oidx[i] = i;
     }
+}
+
+// The start of a STACK of same-size frames (hg_cascade_detect_frames_device), after k_cascade_init_grid has laid out ONE frame's grid:
+// window f * n0 + j is window j of frame f — the same box and level constants, a candidate index of its own, from which the frame of a
+// row follows wherever it travels (index / n0).  Rows [n0, n) are written from rows [0, n0), which this kernel only reads.
+__global__ void k_cascade_init_frames(int n0, int n, double* __restrict__ orig_coords, double* __restrict__ orig_level, double* __restrict__ coords,
+                                      double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf, int32_t* __restrict__ oidx,
+                                      int32_t* __restrict__ count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *count = n;
+    if (i < n0 || i >= n) return;
+    const int j = i % n0;
+    for (int q = 0; q < 4; ++q) {
+        const double v = orig_coords[(size_t)j * 4 + q];
+        orig_coords[(size_t)i * 4 + q] = v;
+        coords[(size_t)i * 4 + q] = v;
+    }
+    for (int q = 0; q < 3; ++q) orig_level[(size_t)i * 3 + q] = orig_level[(size_t)j * 3 + q];
+    angles[i] = 0.0;
+    neg[i] = 0.0;
+    conf[i] = 0.0;
+    oidx[i] = i;
 }
 
 // The start of a TRACKED frame (the reference's track_single_face branch with a face found on the previous frame): nine windows from
@@ -665,6 +690,7 @@ struct hg_cascade {
     int pre_src_w = 0, pre_src_h = 0;    // ... the frame size pre_box was written for
     int frame_format = HG_FRAME_L;       // hg_cascade_set_frame_format: how frame_dev / ld of the detect entries are read
     hg::DevBuf gray_frame;               // a colour frame that is not prescaled, converted (grows on demand, like pre_frame)
+    hg::DevBuf frame_stack;              // hg_cascade_detect_frames_device: the prescaled / converted grey frames of a stack, dense, one after the other
     int prescale_filter = HG_RESAMPLE_NEAREST;      // hg_cascade_set_prescale_filter (enum hg_resample)
     int32_t* host_count = nullptr;       // pinned, device-visible: {count, sequence number} (publish_count)
     int32_t seq = 0;                     // sequence number of the last read-back asked for
@@ -810,6 +836,15 @@ struct Bounded {
     const int32_t* final_count;      // out
 };
 
+// A STACK of frames (`FS`, hg_cascade_detect_frames_device): frame_dev is frame 0 of n_frames grey frames of one size, `stride` bytes
+// apart; the candidates are n_frames copies of the grid of `T` (n0 = n_frames * FS->n0: k_cascade_init_frames) and every extraction
+// cuts row i from frame orig_index[i] / FS->n0 (hg::patcher_extract_frames).  Nothing else differs: rows are independent, the
+// compaction keeps their order, so the survivors come out by frame and, inside a frame, in the order the frame alone gives.
+struct FrameStack {
+    int n_frames;
+    int64_t stride, n0;
+};
+
 // Every frame-reading entry of this file refuses a bad frame as a bad ARGUMENT, before it launches or writes anything: a row stride
 // below the width (a broadcast view has 0) would have every row read its neighbours' pixels.
 void check_frame_geometry(int frame_h, int frame_w, int64_t ld, int bpp = 1) {
@@ -820,13 +855,14 @@ void check_frame_geometry(int frame_h, int frame_w, int64_t ld, int bpp = 1) {
 void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
                  const LevelTable* T, int64_t n0, double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence,
                  int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr,
-                 Bounded* B = nullptr) {
+                 Bounded* B = nullptr, const FrameStack* FS = nullptr) {
     if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
     if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
     if (n0 > 0 && (!frame_dev || (!T && !B && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
     // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
     if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
     // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
+    if (FS && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
     if (B && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
     set_dev(c->device);
     hipStream_t st = (hipStream_t)stream;
@@ -846,6 +882,10 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         hipLaunchKernelGGL(k_cascade_init_grid, (unsigned)((n0 + 255) / 256), 256, 0, st, *T, (double*)c->orig_coords.p, (double*)c->orig_level.p,
                            (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
                            (int32_t*)c->count.p);
+        if (FS && FS->n_frames > 1)
+            hipLaunchKernelGGL(k_cascade_init_frames, (unsigned)((n0 + 255) / 256), 256, 0, st, (int)FS->n0, (int)n0, (double*)c->orig_coords.p,
+                               (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p,
+                               (int32_t*)c->oidx[0].p, (int32_t*)c->count.p);
     } else {
         HG_HIP(hipMemcpyAsync(c->orig_coords.p, boxes_host, (size_t)n0 * 32, hipMemcpyHostToDevice, st));
         HG_HIP(hipMemcpyAsync(c->orig_level.p, level_host, (size_t)n0 * 24, hipMemcpyHostToDevice, st));
@@ -906,9 +946,13 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
             // (the first stage's angles are all zero: the plain EXTENT kernel — a window with delta_ang == 0 is cut from the frame itself —
             // and where the windows come from the level table they are a function of that table alone: their index tables are kept)
             // the stage's filter: interpolation_formats[network_serial] (FaceDetectUpdated.py:671, :686)
-            const int rc = hg::patcher_extract(c->patcher, k == 0 && T ? key_of(T, sizeof *T) : 0, c->interp[S.serial], frame_dev, HG_U8, frame_h, frame_w, ld,
-                                               (const double*)c->coords[cur].p, k == 0 ? nullptr : (const double*)c->neg.p, n_bound, c->w, c->h,
-                                               c->subs[sb].p, HG_U8, (int64_t)row, st);
+            const uint64_t key = k == 0 && T ? key_of(T, sizeof *T) : 0;
+            const double* dang = k == 0 ? nullptr : (const double*)c->neg.p;
+            const int rc = FS ? hg::patcher_extract_frames(c->patcher, key, FS->n0, c->interp[S.serial], frame_dev, FS->n_frames, FS->stride, frame_h, frame_w, ld,
+                                                           (const double*)c->coords[cur].p, dang, (const int32_t*)c->oidx[cur].p, (int)FS->n0, n_bound, c->w,
+                                                           c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
+                              : hg::patcher_extract(c->patcher, key, c->interp[S.serial], frame_dev, HG_U8, frame_h, frame_w, ld,
+                                                    (const double*)c->coords[cur].p, dang, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st);
             if (rc != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         }
         if (S.flow) {
@@ -1017,18 +1061,22 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
 // fr / fh / fw / fld: the frame the grid and the stage loop read — always grey.  A colour frame (hg_cascade_set_frame_format) is
 // prescaled by the same whole-frame box through the format gather, which converts the sampled pixels only; one that needs no
 // prescale is converted as a whole (gray_frame_of).
-void gray_frame_of(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, void* stream, const void*& fr, int64_t& fld) {
+// dst (here and in prescale_frame): where the grey frame goes instead of the cascade's single-frame buffer — a slot of a frame stack
+void gray_frame_of(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, void* stream, const void*& fr, int64_t& fld, void* dst = nullptr) {
     check_frame_geometry(frame_h, frame_w, ld, hg::frame_bpp(c->frame_format));
     set_dev(c->device);
-    c->gray_frame.alloc((size_t)frame_h * frame_w);
-    if (hg_frame_to_gray_device(c->device, frame_dev, c->frame_format, frame_h, frame_w, ld, (uint8_t*)c->gray_frame.p, frame_w, stream) != HG_OK)
+    if (!dst) {
+        c->gray_frame.alloc((size_t)frame_h * frame_w);
+        dst = c->gray_frame.p;
+    }
+    if (hg_frame_to_gray_device(c->device, frame_dev, c->frame_format, frame_h, frame_w, ld, (uint8_t*)dst, frame_w, stream) != HG_OK)
         hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
-    fr = c->gray_frame.p;
+    fr = dst;
     fld = frame_w;
 }
 
 void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
-                    const void*& fr, int& fh, int& fw, int64_t& fld) {
+                    const void*& fr, int& fh, int& fw, int64_t& fld, void* dst = nullptr) {
     fr = frame_dev;
     fh = frame_h;
     fw = frame_w;
@@ -1043,12 +1091,15 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
             c->pre_src_w = frame_w;
             c->pre_src_h = frame_h;
         }
-        c->pre_frame.alloc((size_t)prescale_w * prescale_h);
+        if (!dst) {
+            c->pre_frame.alloc((size_t)prescale_w * prescale_h);
+            dst = c->pre_frame.p;
+        }
         if (c->prescale_filter != HG_RESAMPLE_NEAREST) {      // im.convert("L").resize((w, h), filter): PIL's antialiased resize (hg_resample.hip)
             const int rc = hg_patcher_resize_device(c->patcher, c->prescale_filter, 0, frame_dev, c->frame_format, frame_h, frame_w, ld, HG_FRAME_L,
-                                                    c->pre_frame.p, prescale_h, prescale_w, prescale_w, stream);
+                                                    dst, prescale_h, prescale_w, prescale_w, stream);
             if (rc != HG_OK) hg::fail(rc, "%s", hg_last_error());
-            fr = c->pre_frame.p;
+            fr = dst;
             fh = prescale_h;
             fw = prescale_w;
             fld = prescale_w;
@@ -1056,16 +1107,70 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
         }
         const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
         if (hg::patcher_extract_format(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), c->frame_format, frame_dev, frame_h, frame_w, ld,
-                                       (const double*)c->pre_box.p, 1, prescale_w, prescale_h, c->pre_frame.p, HG_U8, (int64_t)prescale_w * prescale_h,
+                                       (const double*)c->pre_box.p, 1, prescale_w, prescale_h, dst, HG_U8, (int64_t)prescale_w * prescale_h,
                                        stream) != HG_OK)
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
-        fr = c->pre_frame.p;
+        fr = dst;
         fh = prescale_h;
         fw = prescale_w;
         fld = prescale_w;
     } else if (c->frame_format != HG_FRAME_L && frame_dev) {      // (a null frame: detect_impl's refusal)
-        gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, fr, fld);
+        gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, fr, fld, dst);
     }
+}
+
+// ---- a stack of same-size frames through one pooled pass (include/higsfa.h, hg_cascade_detect_frames_device) ----------------------
+// What both stack entries refuse, before anything is launched or written; returns the level table and the window count of ONE frame.
+LevelTable check_frame_stack(const hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                             int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, int64_t out_cap, const int32_t* frame_first) {
+    if (!c || !frame_first) hg::fail(HG_ERR_ARG, "null argument");
+    if (n_frames < 1 || n_frames > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "%d frames in a stack (1..%d)", n_frames, HG_MAX_STACK_FRAMES);
+    if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+    const LevelTable T = make_level_table(levels, n_levels);
+    if ((int64_t)n_frames * T.first[T.n_levels] > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "too many windows: %d frames of %d", n_frames, T.first[T.n_levels]);
+    const int bpp = hg::frame_bpp(c->frame_format);
+    check_frame_geometry(frame_h, frame_w, ld, bpp);
+    if (frame_stride < (int64_t)(frame_h - 1) * ld + (int64_t)frame_w * bpp)
+        hg::fail(HG_ERR_ARG, "frames %lld bytes apart, a frame reaches over %lld", (long long)frame_stride, (long long)((int64_t)(frame_h - 1) * ld + (int64_t)frame_w * bpp));
+    if (!frames_dev) hg::fail(HG_ERR_ARG, "null data pointer");
+    if ((prescale_w > 0 || prescale_h > 0) && (prescale_w <= 0 || prescale_h <= 0)) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
+    return T;
+}
+
+// The grey frames the pooled stage loop reads: grey frames without a prescale in place; otherwise every frame through prescale_frame —
+// the code a single frame runs, one pass per frame — into its slot of the cascade's dense grey stack.
+FrameStack stack_frames(hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, int prescale_w,
+                        int prescale_h, int64_t n0, void* stream, const void*& fr, int& fh, int& fw, int64_t& fld) {
+    const bool pre = prescale_w > 0 || prescale_h > 0;
+    fr = frames_dev;
+    fh = frame_h;
+    fw = frame_w;
+    fld = ld;
+    if (!pre && c->frame_format == HG_FRAME_L) return FrameStack{n_frames, frame_stride, n0};
+    const int oh = pre ? prescale_h : frame_h, ow = pre ? prescale_w : frame_w;
+    const size_t slot = (size_t)oh * ow;
+    set_dev(c->device);
+    c->frame_stack.alloc(slot * n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        const void* one;
+        prescale_frame(c, (const char*)frames_dev + (int64_t)f * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream, one, fh, fw, fld,
+                       (char*)c->frame_stack.p + slot * f);
+    }
+    fr = c->frame_stack.p;
+    return FrameStack{n_frames, (int64_t)slot, n0};
+}
+
+// detect_impl's survivors of a stack, as the caller gets them: the index within the frame's own grid, and the first row of every frame
+// (they are ordered by frame: the compaction keeps the candidates' order)
+void split_by_frame(int32_t* orig_index, int64_t n, int64_t n0, int n_frames, int32_t* frame_first) {
+    int f = 0;
+    frame_first[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int fi = (int)(orig_index[i] / n0);
+        while (f < fi && f < n_frames) frame_first[++f] = (int32_t)i;
+        orig_index[i] = (int32_t)(orig_index[i] - (int64_t)fi * n0);
+    }
+    while (f < n_frames) frame_first[++f] = (int32_t)n;
 }
 
 }  // namespace
@@ -1129,6 +1234,57 @@ int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* 
         detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
         hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
                             out_rows, out_cap, n_out, n_before_purge, (hipStream_t)stream);
+    });
+}
+
+int hg_cascade_detect_frames_device(hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                                    int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_coords, double* out_angles,
+                                    int32_t* out_orig_index, double* out_confidence, int64_t out_cap, int32_t* frame_first, int32_t* stage_counts,
+                                    int64_t* rows_executed, void* stream) {
+    return guarded([&] {
+        const LevelTable T = check_frame_stack(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_cap,
+                                               frame_first);
+        const int64_t n0 = T.first[T.n_levels], total = n0 * n_frames;
+        const void* fr;
+        int fh, fw;
+        int64_t fld;
+        const FrameStack FS = stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, n0, stream, fr, fh, fw, fld);
+        std::vector<int32_t> own_index;      // the frame of a survivor is read off its index: fetched even if the caller does not want it
+        if (!out_orig_index) {
+            own_index.resize((size_t)std::min<int64_t>(out_cap, total));
+            out_orig_index = own_index.data();
+        }
+        int64_t n = 0;
+        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, total, out_coords, out_angles, out_orig_index, out_confidence, out_cap, &n, stage_counts,
+                    rows_executed, stream, nullptr, nullptr, &FS);
+        split_by_frame(out_orig_index, n, n0, n_frames, frame_first);
+    });
+}
+
+// the pooled stage loop, then the eye step on ALL survivors as one batch and the purge per frame (hg::eyes_frames_tail), on the grey
+// stack the cascade read; as in hg_cascade_detect_faces_frame_device the host reads nothing between the stage loop's last survivor count
+// and the one read-back of the per-frame counts and the rows
+int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
+                                          int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows,
+                                          int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed,
+                                          void* stream) {
+    return guarded([&] {
+        if (!e) hg::fail(HG_ERR_ARG, "null argument");
+        const LevelTable T = check_frame_stack(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_cap,
+                                               frame_first);
+        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+        const int64_t n0 = T.first[T.n_levels], total = n0 * n_frames;
+        const void* fr;
+        int fh, fw;
+        int64_t fld;
+        const FrameStack FS = stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, n0, stream, fr, fh, fw, fld);
+        int64_t n = 0;
+        int cur = 0;
+        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, total, nullptr, nullptr, nullptr, nullptr, total, &n, stage_counts, rows_executed, stream, &cur,
+                    nullptr, &FS);
+        hg::eyes_frames_tail(e, fr, n_frames, FS.stride, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
+                             (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, n0, n, out_rows, out_cap, frame_first, n_before_purge,
+                             (hipStream_t)stream);
     });
 }
 

@@ -174,6 +174,14 @@ struct DevBuf {
 int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_dev, int frame_dtype, int frame_h, int frame_w, int64_t ld,
                     const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo,
                     void* stream);
+// hg_extract.hip: the same dispatch over a STACK of n_frames grey uint8 frames of one size, frame_stride bytes apart
+// (hg_patcher_extract_frames_device): row i is cut from frame row_frame_dev[i] / row_div, a row whose frame lies outside the stack is
+// all zero.  key != 0, no angles and 0 < tab_n < n: the boxes repeat with period tab_n (one frame's grid copied per frame) and the keyed
+// tables of the first tab_n serve all of them.  The pooled cascade passes its original-window indices with row_div = n0, the pooled eye
+// step a frame index per eye row with row_div = 1.
+int patcher_extract_frames(hg_patcher* p, uint64_t key, int64_t tab_n, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                           int frame_w, int64_t ld, const double* boxes_dev, const double* delta_angs_dev, const int32_t* row_frame_dev, int row_div, int64_t n,
+                           int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
 // hg_extract.hip: NEAREST, unrotated windows from a frame of format HG_FRAME_* (ld_bytes: row stride in bytes), the tables kept under
 // `key` as above.  What hg_patcher_extract_format_device (key = 0) and the cascade's prescale of a colour frame call.
 int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,

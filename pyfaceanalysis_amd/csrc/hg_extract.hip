@@ -126,17 +126,43 @@ __device__ __forceinline__ uint8_t px_load(const ColorPx<BPP, BGR>* __restrict__
     }
 }
 
+// Windows from a STACK of same-size frames (hg_patcher_extract_frames_device): every gather kernel below takes, as an optional LAST
+// argument, one FrameSel.  Without it (the instantiations every other entry launches) a kernel is the code it was before the stack
+// existed: frame_of() is then `true` and touches nothing.  With it the box's frame is looked up once per box — the box index is uniform
+// per workgroup — and `frame` moves to that frame's first pixel; a box whose frame index lies outside [0, n_frames) forms NO address
+// from it: it reads frame 0 through the kernels' clamped addresses and every pixel is masked to 0.
+struct FrameSel {
+    const int32_t* row_frame;      // per box; the box's frame is row_frame[b] / div (the cascade passes its original-window indices and n0)
+    int64_t stride;                // bytes from frame f to frame f + 1
+    int32_t n_frames, div;
+    int64_t tab_n;                 // unrotated boxes: box b reads the tables of box b % tab_n (a grid repeated per frame); n: a table per box
+};
+template <typename P>
+__device__ __forceinline__ bool frame_of(int64_t, P&, int64_t&) { return true; }
+template <typename P>
+__device__ __forceinline__ bool frame_of(int64_t b, P& frame, int64_t& tb, const FrameSel& s) {
+    const int32_t r = s.row_frame[b];
+    const int32_t f = r / s.div;
+    const bool in_stack = r >= 0 && f < s.n_frames;
+    if (in_stack) frame = (P)((const char*)frame + (int64_t)f * s.stride);
+    tb = b % s.tab_n;
+    return in_stack;
+}
+
 // One workgroup per (group of output rows, box): no index divisions, the row's source line and the column table are
 // read once; four output pixels per thread and one vector store when the output is uint8.  ld_bytes: the frame's row stride in
 // bytes (a colour frame's rows need not be a whole number of pixels apart).
-template <typename FT, typename OT>
-__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame, int64_t ld_bytes, const int32_t* __restrict__ tabs, int64_t n,
-                                                        int w, int h, OT* __restrict__ out, int64_t ldo) {
+template <typename FT, typename OT, typename... SEL>
+__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame0, int64_t ld_bytes, const int32_t* __restrict__ tabs, int64_t n,
+                                                        int w, int h, OT* __restrict__ out, int64_t ldo, SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;     // blockDim.y output rows per workgroup
     if (y >= h) return;
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const int32_t* t = tabs + b * (w + h);
-        const int ys = t[w + y];
+        const FT* frame = frame0;
+        int64_t tb = b;
+        const bool in_stack = frame_of(b, frame, tb, sel...);
+        const int32_t* t = tabs + tb * (w + h);
+        const int ys = in_stack ? t[w + y] : -1;
         const FT* src = (const FT*)((const char*)frame + (int64_t)(ys >= 0 ? ys : 0) * ld_bytes);
         OT* dst = out + b * ldo + (int64_t)y * w;
         if constexpr (sizeof(OT) == 1) {
@@ -219,13 +245,17 @@ __global__ void __launch_bounds__(256) k_frame_to_gray(const uint8_t* __restrict
 // (gfx950 runs in unaligned-access mode: the compiler itself emits global_load_dwordx2 for a byte-aligned 8-byte copy) replaces
 // four byte loads; one 16-byte store per row.  5 memory instructions per 16 pixels.  Same bytes: every pixel is still
 // frame[ytab[y]][xtab[x]] or 0.
-__global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __restrict__ frame, int64_t ld, int fw, const int32_t* __restrict__ tabs,
-                                                             int64_t n, int w, int h, uint8_t* __restrict__ out, int64_t ldo, int rows_per_wg) {
+template <typename... SEL>
+__global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __restrict__ frame0, int64_t ld, int fw, const int32_t* __restrict__ tabs,
+                                                             int64_t n, int w, int h, uint8_t* __restrict__ out, int64_t ldo, int rows_per_wg, SEL... sel) {
     const int tpr = w >> 4;                                   // threads per output row (a power of two, <= 256)
     const int tx = threadIdx.x & (tpr - 1), ty = threadIdx.x / tpr, rows_per_pass = 256 / tpr;
     const int y_begin = blockIdx.x * rows_per_wg, y_end = min(h, y_begin + rows_per_wg);
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const int32_t* t = tabs + b * (w + h);
+        const uint8_t* frame = frame0;
+        int64_t tb = b;
+        const bool in_stack = frame_of(b, frame, tb, sel...);      // (a box outside the stack: every row below reads as "outside the frame")
+        const int32_t* t = tabs + tb * (w + h);
         int xs[16];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -249,7 +279,7 @@ __global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __re
         if (wave8) {
 #pragma unroll 4
             for (int y = y_begin + ty; y < y_end; y += rows_per_pass) {      // (unrolled: the rows' loads overlap, one latency for four rows)
-                const int ys = t[w + y];
+                const int ys = in_stack ? t[w + y] : -1;
                 const uint8_t* src = frame + (int64_t)(ys >= 0 ? ys : 0) * ld;
                 uint32_t pk[4];
 #pragma unroll
@@ -269,7 +299,7 @@ __global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __re
             // 23.7 us against 20.2 for the first stage's 1738 windows; the third code path costs registers every wave pays for)
 #pragma unroll 2
             for (int y = y_begin + ty; y < y_end; y += rows_per_pass) {
-                const int ys = t[w + y];
+                const int ys = in_stack ? t[w + y] : -1;
                 const uint8_t* src = frame + (int64_t)(ys >= 0 ? ys : 0) * ld;
                 uint32_t pk[4];
 #pragma unroll
@@ -453,15 +483,24 @@ __device__ __forceinline__ void gather_rot_row(const FT* __restrict__ frame, int
 
 // Rotated windows, tables from memory (k_extent_tables, k_rot_coefs): the frame (<= a few MB) sits in L2; the access pattern is a
 // rotated scan line.
-template <typename FT, typename OT>
-__global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict__ frame, int64_t ld, int fw, int fh, const int32_t* __restrict__ tabs,
-                                                            const RotCoef* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo) {
+template <typename FT, typename OT, typename... SEL>
+__global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict__ frame0, int64_t ld, int fw, int fh, const int32_t* __restrict__ tabs,
+                                                            const RotCoef* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo,
+                                                            SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;
     if (y >= h) return;
     const bool packed = sizeof(OT) == 1 && (w & 3) == 0 && (ldo & 3) == 0 && ((uintptr_t)out & 3) == 0;
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const RotCoef rc = rot[b];
-        gather_rot_row<FT, OT>(frame, ld, fw, fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
+        if constexpr (sizeof...(SEL) == 0) {
+            const RotCoef rc = rot[b];
+            gather_rot_row<FT, OT>(frame0, ld, fw, fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
+        } else {
+            const FT* frame = frame0;
+            int64_t tb = b;      // (rotated boxes: a table per box)
+            RotCoef rc = rot[b];
+            if (!frame_of(b, frame, tb, sel...)) rc.mode = 3;      // a box outside the stack: as outside the fixed-point range, the window stays 0
+            gather_rot_row<FT, OT>(frame, ld, fw, fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
+        }
     }
 }
 
@@ -509,14 +548,18 @@ __device__ __forceinline__ uint8_t rot_pixel(const uint8_t* __restrict__ frame, 
 }
 
 // Unrotated windows: a workgroup per (group of output rows, box), a thread per output pixel
-template <int F, typename OT>
-__global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict__ frame, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
-                                                        int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo) {
+template <int F, typename OT, typename... SEL>
+__global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict__ frame0, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+                                                        int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo, SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;
     if (y >= h) return;
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const FiltEnt* t = tabs + b * (w + h);
-        const FiltEnt ey = t[w + y];
+        const uint8_t* frame = frame0;
+        int64_t tb = b;
+        const bool in_stack = frame_of(b, frame, tb, sel...);
+        const FiltEnt* t = tabs + tb * (w + h);
+        FiltEnt ey = t[w + y];
+        if (!in_stack) ey.i = kFiltOutside;      // a box outside the stack: every row outside the frame
         OT* dst = out + b * ldo + (int64_t)y * w;
         for (int x = threadIdx.x; x < w; x += blockDim.x) {
             const FiltEnt ex = t[x];
@@ -542,10 +585,10 @@ __global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict
 //     1.237 ms tap by tap, although it computes more rotated pixels: tap by tap, sixteen threads compute the same rotated pixel
 //     at the same time and every one of them reads the frame from L2, where the staged tile reads LDS.
 constexpr int kFiltTile = 16, kFiltPatch = 256 * 16 * 2;
-template <int F, typename OT>
-__global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __restrict__ frame, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+template <int F, typename OT, typename... SEL>
+__global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __restrict__ frame0, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
                                                             const RotAff* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo,
-                                                            int tiles_x) {
+                                                            int tiles_x, SEL... sel) {
     constexpr int LO = F == HG_FILTER_BICUBIC ? 1 : 0, HI = F == HG_FILTER_BICUBIC ? 2 : 1, TAPS = (LO + HI + 1) * (LO + HI + 1);
     constexpr int kStageLimit = TAPS * kFiltTile * kFiltTile * (F == HG_FILTER_BICUBIC ? 2 : 1);      // rotated pixels; see above
     static_assert(kStageLimit <= kFiltPatch, "the staged rectangle must fit the LDS patch");
@@ -555,13 +598,17 @@ __global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __rest
     const int ox = (int)(blockIdx.x % tiles_x) * kFiltTile + tx, oy = (int)(blockIdx.x / tiles_x) * kFiltTile + ty;
     const bool live = ox < w && oy < h;
     auto clip = [](int v, int lim) { return v < 0 ? 0 : v < lim ? v : lim - 1; };
+    const uint8_t* frame = frame0;
     auto frame_tap = [&](int xc, int yc) { return (double)frame[(int64_t)yc * ld + xc]; };
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {      // (every thread of the workgroup takes every trip: barriers below)
+        int64_t tb = b;      // (rotated boxes: a table per box)
+        frame = frame0;
+        const bool in_stack = frame_of(b, frame, tb, sel...);      // uniform per workgroup; a box outside the stack: no entry inside the frame
         const FiltEnt* t = tabs + b * (w + h);
         FiltEnt ex, ey;
         ex.i = ey.i = kFiltOutside;
         ex.d = ey.d = 0.0;
-        if (live) {
+        if (live && in_stack) {
             ex = t[ox];
             ey = t[w + oy];
         }
@@ -628,9 +675,10 @@ int guarded(F&& fn) {
 }
 
 // ld_bytes: the frame's row stride in bytes (ld * sizeof(FT) for the scalar pixel types)
-template <typename FT>
+// sel: nothing, or the FrameSel of a frame stack (the kernels' optional last argument)
+template <typename FT, typename... SEL>
 void launch_gather(const void* frame, int64_t ld_bytes, int fw, const int32_t* tabs, int64_t n, int w, int h, void* out, int out_dtype, int64_t ldo,
-                   hipStream_t st) {
+                   hipStream_t st, SEL... sel) {
     if constexpr (sizeof(FT) == 1) {
         const int tpr = w >> 4;
         if (out_dtype == HG_U8 && (w & 15) == 0 && tpr >= 1 && tpr <= 256 && (tpr & (tpr - 1)) == 0 && ((w + h) & 3) == 0 && (ldo & 15) == 0 &&
@@ -641,7 +689,7 @@ void launch_gather(const void* frame, int64_t ld_bytes, int fw, const int32_t* t
             while (passes > 1 && n * ((h + rows_per_pass * passes - 1) / (rows_per_pass * passes)) < 1024) passes = (passes + 1) / 2;
             const int rows_per_wg = rows_per_pass * passes;
             const dim3 grid((unsigned)((h + rows_per_wg - 1) / rows_per_wg), (unsigned)std::min<int64_t>(n, 65535));
-            hipLaunchKernelGGL(k_extent_gather_u8x16, grid, 256, 0, st, (const uint8_t*)frame, ld_bytes, fw, tabs, n, w, h, (uint8_t*)out, ldo, rows_per_wg);
+            hipLaunchKernelGGL((k_extent_gather_u8x16<SEL...>), grid, 256, 0, st, (const uint8_t*)frame, ld_bytes, fw, tabs, n, w, h, (uint8_t*)out, ldo, rows_per_wg, sel...);
             return;
         }
     }
@@ -649,9 +697,9 @@ void launch_gather(const void* frame, int64_t ld_bytes, int fw, const int32_t* t
     const dim3 thr(tx, 256 / tx);
     const dim3 grid((unsigned)((h + thr.y - 1) / thr.y), (unsigned)std::min<int64_t>(n, 65535));
     switch (out_dtype) {
-        case HG_U8: hipLaunchKernelGGL((k_extent_gather<FT, uint8_t>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (uint8_t*)out, ldo); break;
-        case HG_F32: hipLaunchKernelGGL((k_extent_gather<FT, float>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (float*)out, ldo); break;
-        default: hipLaunchKernelGGL((k_extent_gather<FT, double>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (double*)out, ldo); break;
+        case HG_U8: hipLaunchKernelGGL((k_extent_gather<FT, uint8_t, SEL...>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (uint8_t*)out, ldo, sel...); break;
+        case HG_F32: hipLaunchKernelGGL((k_extent_gather<FT, float, SEL...>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (float*)out, ldo, sel...); break;
+        default: hipLaunchKernelGGL((k_extent_gather<FT, double, SEL...>), grid, thr, 0, st, (const FT*)frame, ld_bytes, tabs, n, w, h, (double*)out, ldo, sel...); break;
     }
 }
 
@@ -667,9 +715,9 @@ void launch_gather_format(int format, const void* frame, int64_t ld_bytes, int f
     }
 }
 
-template <typename FT>
+template <typename FT, typename... SEL>
 void launch_gather_rot(const void* frame, int64_t ld, int fw, int fh, const int32_t* tabs, const RotCoef* rot, int64_t n, int w, int h, void* out,
-                       int out_dtype, int64_t ldo, hipStream_t st) {
+                       int out_dtype, int64_t ldo, hipStream_t st, SEL... sel) {
     // uint8 windows: a thread packs sixteen pixels where the row is a multiple of 16 (a 128-pixel row takes 8 threads and a
     // workgroup 32 rows), four otherwise
     const unsigned tx = out_dtype == HG_U8 ? ((w & 15) == 0 ? (w >= 2048 ? 128 : w >= 1024 ? 64 : w >= 512 ? 32 : w >= 256 ? 16 : w >= 128 ? 8 : 4)
@@ -678,23 +726,23 @@ void launch_gather_rot(const void* frame, int64_t ld, int fw, int fh, const int3
     const dim3 thr(tx, 256 / tx);
     const dim3 grid((unsigned)((h + thr.y - 1) / thr.y), (unsigned)std::min<int64_t>(n, 65535));
     switch (out_dtype) {
-        case HG_U8: hipLaunchKernelGGL((k_extent_gather_rot<FT, uint8_t>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (uint8_t*)out, ldo); break;
-        case HG_F32: hipLaunchKernelGGL((k_extent_gather_rot<FT, float>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (float*)out, ldo); break;
-        default: hipLaunchKernelGGL((k_extent_gather_rot<FT, double>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (double*)out, ldo); break;
+        case HG_U8: hipLaunchKernelGGL((k_extent_gather_rot<FT, uint8_t, SEL...>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (uint8_t*)out, ldo, sel...); break;
+        case HG_F32: hipLaunchKernelGGL((k_extent_gather_rot<FT, float, SEL...>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (float*)out, ldo, sel...); break;
+        default: hipLaunchKernelGGL((k_extent_gather_rot<FT, double, SEL...>), grid, thr, 0, st, (const FT*)frame, ld, fw, fh, tabs, rot, n, w, h, (double*)out, ldo, sel...); break;
     }
 }
 
-template <int F>
+template <int F, typename... SEL>
 void launch_filter(const uint8_t* frame, int64_t ld, int fw, int fh, const FiltEnt* tabs, const RotAff* rot, int64_t n, int w, int h, void* out, int out_dtype,
-                   int64_t ldo, hipStream_t st) {
+                   int64_t ldo, hipStream_t st, SEL... sel) {
     const unsigned ny = (unsigned)std::min<int64_t>(n, 65535);
     if (rot) {
         const int tiles_x = (w + kFiltTile - 1) / kFiltTile, tiles_y = (h + kFiltTile - 1) / kFiltTile;      // <= 256 each (check_args)
         const dim3 grid((unsigned)(tiles_x * tiles_y), ny);
         switch (out_dtype) {
-            case HG_U8: hipLaunchKernelGGL((k_filter_gather_rot<F, uint8_t>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (uint8_t*)out, ldo, tiles_x); break;
-            case HG_F32: hipLaunchKernelGGL((k_filter_gather_rot<F, float>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (float*)out, ldo, tiles_x); break;
-            default: hipLaunchKernelGGL((k_filter_gather_rot<F, double>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (double*)out, ldo, tiles_x); break;
+            case HG_U8: hipLaunchKernelGGL((k_filter_gather_rot<F, uint8_t, SEL...>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (uint8_t*)out, ldo, tiles_x, sel...); break;
+            case HG_F32: hipLaunchKernelGGL((k_filter_gather_rot<F, float, SEL...>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (float*)out, ldo, tiles_x, sel...); break;
+            default: hipLaunchKernelGGL((k_filter_gather_rot<F, double, SEL...>), grid, 256, 0, st, frame, ld, fw, fh, tabs, rot, n, w, h, (double*)out, ldo, tiles_x, sel...); break;
         }
         return;
     }
@@ -702,9 +750,9 @@ void launch_filter(const uint8_t* frame, int64_t ld, int fw, int fh, const FiltE
     const dim3 thr(tx, 256 / tx);
     const dim3 grid((unsigned)((h + thr.y - 1) / thr.y), ny);
     switch (out_dtype) {
-        case HG_U8: hipLaunchKernelGGL((k_filter_gather<F, uint8_t>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (uint8_t*)out, ldo); break;
-        case HG_F32: hipLaunchKernelGGL((k_filter_gather<F, float>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (float*)out, ldo); break;
-        default: hipLaunchKernelGGL((k_filter_gather<F, double>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (double*)out, ldo); break;
+        case HG_U8: hipLaunchKernelGGL((k_filter_gather<F, uint8_t, SEL...>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (uint8_t*)out, ldo, sel...); break;
+        case HG_F32: hipLaunchKernelGGL((k_filter_gather<F, float, SEL...>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (float*)out, ldo, sel...); break;
+        default: hipLaunchKernelGGL((k_filter_gather<F, double, SEL...>), grid, thr, 0, st, frame, ld, fw, fh, tabs, n, w, h, (double*)out, ldo, sel...); break;
     }
 }
 
@@ -751,6 +799,36 @@ const int32_t* nearest_tables(hg_patcher* p, uint64_t key, int frame_h, int fram
     hipLaunchKernelGGL(k_extent_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, tabs, (const double*)nullptr,
                        (RotCoef*)nullptr);
     return tabs;
+}
+
+// The BILINEAR / BICUBIC coordinate tables of n boxes (they hold coordinates, not taps: both filters share them), built on `st`, and,
+// for rotated boxes, their matrices (*rot).  key != 0 and no angles: kept per key under hg_patcher_extract_keyed_device's contract.
+const FiltEnt* filter_tables(hg_patcher* p, uint64_t key, int frame_h, int frame_w, const double* boxes_dev, const double* delta_angs_dev, int64_t n, int out_w,
+                             int out_h, hipStream_t st, const RotAff** rot) {
+    const int64_t n_ent = n * (out_w + out_h);
+    if ((n_ent + 255) / 256 > 0x7fffffffll) hg::fail(HG_ERR_ARG, "too many boxes");
+    *rot = nullptr;
+    if (key && !delta_angs_dev) {
+        hg_patcher::Keyed* K = nullptr;
+        for (auto& k : p->keyed)
+            if (k.key == key && k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
+        if (!K) {
+            K = &p->keyed[p->keyed_next];
+            p->keyed_next = (p->keyed_next + 1) % 4;
+            if (K->tabs.p && (size_t)n_ent * sizeof(FiltEnt) > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
+            K->tabs.alloc((size_t)n_ent * sizeof(FiltEnt));
+            K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 1;
+            hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)K->tabs.p,
+                               (const double*)nullptr, (RotAff*)nullptr);
+        }
+        return (const FiltEnt*)K->tabs.p;
+    }
+    p->ftabs.alloc((size_t)n_ent * sizeof(FiltEnt));
+    if (delta_angs_dev) p->frot.alloc((size_t)n * sizeof(RotAff));
+    hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)p->ftabs.p,
+                       delta_angs_dev, delta_angs_dev ? (RotAff*)p->frot.p : nullptr);
+    if (delta_angs_dev) *rot = (const RotAff*)p->frot.p;
+    return (const FiltEnt*)p->ftabs.p;
 }
 
 void check_device(int device) {
@@ -959,31 +1037,8 @@ int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_d
         if (n == 0) return;
         HG_HIP(hipSetDevice(p->device));
         hipStream_t st = (hipStream_t)stream;
-        const int64_t n_ent = n * (out_w + out_h);
-        if ((n_ent + 255) / 256 > 0x7fffffffll) fail(HG_ERR_ARG, "too many boxes");
-        const FiltEnt* tabs = nullptr;
-        if (key && !delta_angs_dev) {
-            hg_patcher::Keyed* K = nullptr;
-            for (auto& k : p->keyed)
-                if (k.key == key && k.filtered && k.n == n && k.out_w == out_w && k.out_h == out_h && k.frame_w == frame_w && k.frame_h == frame_h) K = &k;
-            if (!K) {
-                K = &p->keyed[p->keyed_next];
-                p->keyed_next = (p->keyed_next + 1) % 4;
-                if (K->tabs.p && (size_t)n_ent * sizeof(FiltEnt) > K->tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
-                K->tabs.alloc((size_t)n_ent * sizeof(FiltEnt));
-                K->key = key; K->n = n; K->out_w = out_w; K->out_h = out_h; K->frame_w = frame_w; K->frame_h = frame_h; K->filtered = 1;
-                hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)K->tabs.p,
-                                   (const double*)nullptr, (RotAff*)nullptr);
-            }
-            tabs = (const FiltEnt*)K->tabs.p;
-        } else {
-            p->ftabs.alloc((size_t)n_ent * sizeof(FiltEnt));
-            if (delta_angs_dev) p->frot.alloc((size_t)n * sizeof(RotAff));
-            hipLaunchKernelGGL(k_filter_tables, (unsigned)((n_ent + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h, (FiltEnt*)p->ftabs.p,
-                               delta_angs_dev, delta_angs_dev ? (RotAff*)p->frot.p : nullptr);
-            tabs = (const FiltEnt*)p->ftabs.p;
-        }
-        const RotAff* rot = delta_angs_dev ? (const RotAff*)p->frot.p : nullptr;
+        const RotAff* rot = nullptr;
+        const FiltEnt* tabs = filter_tables(p, key, frame_h, frame_w, boxes_dev, delta_angs_dev, n, out_w, out_h, st, &rot);
         if (filter == HG_FILTER_BILINEAR)
             launch_filter<HG_FILTER_BILINEAR>((const uint8_t*)frame_dev, ld, frame_w, frame_h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st);
         else
@@ -991,4 +1046,59 @@ int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_d
         HG_HIP(hipGetLastError());
     });
 }
+
+// The sibling of patcher_extract for a stack of same-size grey uint8 frames (hg_common.hpp; hg_patcher_extract_frames_device is this
+// with key = 0, tab_n = 0, row_div = 1): the same tables, the same kernels instantiated with a FrameSel.  Every refusal comes before
+// the handle or a data pointer is dereferenced and before anything is launched.
+int patcher_extract_frames(hg_patcher* p, uint64_t key, int64_t tab_n, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                           int frame_w, int64_t ld, const double* boxes_dev, const double* delta_angs_dev, const int32_t* row_frame_dev, int row_div, int64_t n,
+                           int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    return guarded([&] {
+        check_filter(filter, HG_U8);
+        if (!p || !frames_dev || !boxes_dev || !row_frame_dev || !out_dev) fail(HG_ERR_ARG, "null pointer");
+        if (n_frames < 1) fail(HG_ERR_ARG, "bad frame count %d", n_frames);
+        if (frame_h <= 0 || frame_w <= 0 || ld < frame_w) fail(HG_ERR_ARG, "bad frame geometry");
+        if (frame_stride < (int64_t)(frame_h - 1) * ld + frame_w)
+            fail(HG_ERR_ARG, "frames %lld bytes apart, a frame reaches over %lld", (long long)frame_stride, (long long)((int64_t)(frame_h - 1) * ld + frame_w));
+        if (out_dtype != HG_U8 && out_dtype != HG_F32 && out_dtype != HG_F64) fail(HG_ERR_ARG, "bad output dtype");
+        if (out_w <= 0 || out_h <= 0 || out_w > 4096 || out_h > 4096) fail(HG_ERR_ARG, "bad sub-image size");
+        if (n < 0 || ldo < (int64_t)out_w * out_h || row_div < 1 || tab_n < 0) fail(HG_ERR_ARG, "bad batch geometry");
+        if (n == 0) return;
+        HG_HIP(hipSetDevice(p->device));
+        hipStream_t st = (hipStream_t)stream;
+        if ((n * (out_w + out_h) + 255) / 256 > 0x7fffffffll) fail(HG_ERR_ARG, "too many boxes");
+        const bool repeat = key && tab_n > 0 && tab_n < n && !delta_angs_dev;      // the first tab_n boxes' tables serve every frame's copy of them
+        const int64_t n_tab = repeat ? tab_n : n;
+        const FrameSel sel{row_frame_dev, frame_stride, n_frames, row_div, n_tab};
+        if (filter == HG_FILTER_NEAREST) {
+            if (delta_angs_dev) {
+                if (frame_w >= 32768 || frame_h >= 32768) fail(HG_ERR_ARG, "rotated windows need a frame smaller than 32768 pixels per side");
+                p->tabs.alloc((size_t)n * (out_w + out_h) * 4);
+                p->rot.alloc((size_t)n * sizeof(RotCoef));
+                hipLaunchKernelGGL(k_extent_tables, (unsigned)((n * (out_w + out_h) + 255) / 256), 256, 0, st, boxes_dev, n, out_w, out_h, frame_w, frame_h,
+                                   (int32_t*)p->tabs.p, delta_angs_dev, (RotCoef*)p->rot.p);
+                launch_gather_rot<uint8_t>(frames_dev, ld, frame_w, frame_h, (const int32_t*)p->tabs.p, (const RotCoef*)p->rot.p, n, out_w, out_h, out_dev,
+                                           out_dtype, ldo, st, sel);
+            } else {
+                const int32_t* tabs = nearest_tables(p, key, frame_h, frame_w, boxes_dev, n_tab, out_w, out_h, st);
+                launch_gather<uint8_t>(frames_dev, ld, frame_w, tabs, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+            }
+        } else {
+            const RotAff* rot = nullptr;
+            const FiltEnt* tabs = filter_tables(p, key, frame_h, frame_w, boxes_dev, delta_angs_dev, n_tab, out_w, out_h, st, &rot);
+            if (filter == HG_FILTER_BILINEAR)
+                launch_filter<HG_FILTER_BILINEAR>((const uint8_t*)frames_dev, ld, frame_w, frame_h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+            else
+                launch_filter<HG_FILTER_BICUBIC>((const uint8_t*)frames_dev, ld, frame_w, frame_h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+        }
+        HG_HIP(hipGetLastError());
+    });
+}
 }  // namespace hg
+
+extern "C" int hg_patcher_extract_frames_device(hg_patcher* p, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
+                                                int64_t ld, const double* boxes_dev, const double* delta_angs_dev, const int32_t* row_frame_dev, int64_t n,
+                                                int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    return hg::patcher_extract_frames(p, 0, 0, filter, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, boxes_dev, delta_angs_dev, row_frame_dev, 1, n,
+                                      out_w, out_h, out_dev, out_dtype, ldo, stream);
+}

@@ -40,6 +40,7 @@ struct hg_eyes {
     hg::DevBuf eboxes, dang, pu8, pf32, sl, sl2, reg, ecoords, toofar, rows, purged, scratch, count;
     hg::DevBuf row_src, kept_idx;        // a tracker's slots: the face of every assembled row, the assembled row of every kept row
     int32_t* host_words = nullptr;       // pinned: {faces after the discard, faces after the purge}
+    hg::DevBuf row_frame, seg;           // a frame stack (eyes_frames_tail): the frame of every eye row; first row of every frame (n_frames + 1), rows kept per frame
 
     void reserve(int64_t n) {
         if (n <= cap) return;
@@ -255,17 +256,16 @@ __device__ __forceinline__ double rel_error(const double* a, const double* e) {
     return d_div(dr > dl ? dr : dl, de);
 }
 
-// rows (n_max, 10); n = min(*n_dev, n_max) when n_dev is given.  scratch: w (n doubles), then perm (n int32) and kept (n + 1 int32).
+// The purge of the n rows at `rows` by the workgroup that calls it (k_purge: all rows; k_purge_frames: one frame's rows).
+// scratch: w (n_max doubles), then perm (n_max int32) and kept (n_max + 1 int32).
 // out: room for n + 1 rows; *count = rows written.  kept_out (nullable, n_max + 1 entries): the index in `rows` of every row written.
-__global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows, int64_t n_max, const int32_t* __restrict__ n_dev,
-                                                double* __restrict__ out, int32_t* __restrict__ count, char* __restrict__ scratch,
-                                                int32_t* __restrict__ kept_out) {
+__device__ __forceinline__ void purge_rows(const double* __restrict__ rows, int64_t n, int64_t n_max, double* __restrict__ out, int32_t* __restrict__ count,
+                                           char* __restrict__ scratch, int32_t* __restrict__ kept_out) {
     __shared__ double tile[1024];
     __shared__ double redv[16];
     __shared__ int redf[16];
     __shared__ int nk_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
-    const int64_t n = (n_dev && *n_dev < n_max) ? (int64_t)*n_dev : n_max;
     if (n <= 1) {                       // :219-220: a copy
         for (int64_t q = tid; q < n * 10; q += blockDim.x) out[q] = rows[q];
         if (tid == 0 && n == 1 && kept_out) kept_out[0] = 0;
@@ -351,6 +351,46 @@ __global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows,
     if (tid == 0) *count = nk;
 }
 
+// rows (n_max, 10); n = min(*n_dev, n_max) when n_dev is given.
+__global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows, int64_t n_max, const int32_t* __restrict__ n_dev,
+                                                double* __restrict__ out, int32_t* __restrict__ count, char* __restrict__ scratch,
+                                                int32_t* __restrict__ kept_out) {
+    const int64_t n = (n_dev && *n_dev < n_max) ? (int64_t)*n_dev : n_max;
+    purge_rows(rows, n, n_max, out, count, scratch, kept_out);
+}
+
+// ---- a stack of frames: the purge is a per-image rule, so it runs per frame -----------------------------------------------------------
+// The frame of every eye row of n faces (left eyes [0, n), right eyes [n, 2n)): the face's original window / n0 (hg_cascade.hip, FrameStack)
+__global__ void k_eye_row_frames(int64_t n, const int32_t* __restrict__ orig_index, int n0, int32_t* __restrict__ row_frame) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t f = orig_index[i] / n0;
+    row_frame[i] = f;
+    row_frame[n + i] = f;
+}
+
+// The assembled rows (k_eyes_glue keeps the survivors' order: by frame) cut into frames: seg_first[f] = first row of frame f,
+// seg_first[n_frames] = *count.  Row j's frame: the original window of the survivor it was made from (row_src) / n0.  One workgroup;
+// thread j writes the entries of the frames that begin at row j (those without a row included).
+__global__ void __launch_bounds__(1024) k_frame_segments(const int32_t* __restrict__ row_src, const int32_t* __restrict__ count,
+                                                         const int32_t* __restrict__ orig_index, int n0, int n_frames, int32_t* __restrict__ seg_first) {
+    const int cnt = *count;
+    for (int j = threadIdx.x; j <= cnt; j += blockDim.x) {
+        const int f_prev = j == 0 ? -1 : orig_index[row_src[j - 1]] / n0;
+        const int f_here = j == cnt ? n_frames : orig_index[row_src[j]] / n0;
+        for (int f = (f_prev < -1 ? -1 : f_prev) + 1; f <= f_here && f <= n_frames; ++f) seg_first[f] = j;
+    }
+}
+
+// k_purge per frame: workgroup f purges rows [seg_first[f], seg_first[f + 1]).  Frame f's kept rows start at row seg_first[f] + f of
+// `out` and its scratch at 16 (seg_first[f] + f) bytes: every frame has room for its count + 1 rows (the first row appended twice).
+__global__ void __launch_bounds__(1024) k_purge_frames(const double* __restrict__ rows, const int32_t* __restrict__ seg_first, double* __restrict__ out,
+                                                       int32_t* __restrict__ seg_kept, char* __restrict__ scratch) {
+    const int f = blockIdx.x;
+    const int64_t lo = seg_first[f], n = seg_first[f + 1] - lo;
+    purge_rows(rows + lo * 10, n, n, out + (lo + f) * 10, seg_kept + f, scratch + (lo + f) * 16, nullptr);
+}
+
 void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, double* out, int32_t* count, void* scratch, hipStream_t st,
                   int32_t* kept_out = nullptr) {
     hipLaunchKernelGGL(k_purge, 1, 1024, 0, st, rows, n_max, n_dev, out, count, (char*)scratch, kept_out);
@@ -361,9 +401,15 @@ void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, doubl
 // discard and the row assembly as well (conf needed then).  n_dev (nullable): the face count stays on the device and n bounds it —
 // every launch is sized by n; k_eye_boxes gives the faces past the live count a defined window, so the extraction, the contrast
 // step and the networks read defined data in all 2n rows, and k_eyes_glue assembles the live faces only.
+// F (nullable): frame_dev is frame 0 of a stack and eye row i is cut from frame F->row_frame[i] (hg::patcher_extract_frames)
+struct EyeFrames {
+    int n_frames;
+    int64_t stride;
+    const int32_t* row_frame;      // 2n entries, on the device
+};
 void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles, const double* conf,
               int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st,
-              const int32_t* n_dev = nullptr, int32_t* row_src = nullptr) {
+              const int32_t* n_dev = nullptr, int32_t* row_src = nullptr, const EyeFrames* F = nullptr) {
     if (n == 0) {
         if (count) HG_HIP(hipMemsetAsync(count, 0, 4, st));
         return;
@@ -373,9 +419,11 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
     const int64_t wh = (int64_t)c.eye_w * c.eye_h, n2 = 2 * n;
     hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, n_dev, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
     HG_HIP(hipGetLastError());
-    if (hg_patcher_extract_filter_device(e->patcher, e->filter, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p, (const double*)e->dang.p, n2,
-                                         c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st) != HG_OK)
-        hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
+    const int rc_x = F ? hg::patcher_extract_frames(e->patcher, 0, 0, e->filter, frame_dev, F->n_frames, F->stride, frame_h, frame_w, ld, (const double*)e->eboxes.p,
+                                                    (const double*)e->dang.p, F->row_frame, 1, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st)
+                       : hg_patcher_extract_filter_device(e->patcher, e->filter, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p,
+                                                          (const double*)e->dang.p, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st);
+    if (rc_x != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
     float* pf = patches ? patches : (float*)e->pf32.p;
     hipLaunchKernelGGL(k_eye_contrast, (unsigned)n2, 256, 0, st, (const uint8_t*)e->pu8.p, pf, wh, c.target_mean, c.target_std);
     HG_HIP(hipGetLastError());
@@ -445,6 +493,56 @@ void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int
     *counts = (const int32_t*)e->count.p;
     *row_src = (const int32_t*)e->row_src.p;
     *kept_idx = (const int32_t*)e->kept_idx.p;
+}
+
+// The tail of hg_cascade_detect_faces_frames_device: the eye step on the n survivors of a STACK of frames as one batch (frame_dev: frame 0
+// of n_frames grey frames, frame_stride bytes apart; survivor i belongs to frame orig_index[i] / n0, the survivors are ordered by frame),
+// the discard and the rows, then the purge PER FRAME; one read-back of the per-frame counts and the rows at the end.
+// frame_first (n_frames + 1): frame f's kept rows are out_rows[frame_first[f] .. frame_first[f + 1]); n_before_purge (n_frames).
+void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const double* boxes,
+                      const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n, double* out_rows, int64_t out_cap,
+                      int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
+    if (!e || !frame_first) fail(HG_ERR_ARG, "null argument");
+    for (int f = 0; f <= n_frames; ++f) frame_first[f] = 0;
+    for (int f = 0; f < n_frames && n_before_purge; ++f) n_before_purge[f] = 0;
+    if (n == 0) return;
+    // before any workspace pointer is taken (see eyes_frame_tail); n + n_frames: the purged rows and the scratch hold count + 1 per frame
+    e->reserve(n + n_frames);
+    e->row_frame.alloc((size_t)n * 2 * 4);
+    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
+    int32_t* seg_first = (int32_t*)e->seg.p;
+    int32_t* seg_kept = seg_first + n_frames + 1;
+    hipLaunchKernelGGL(k_eye_row_frames, (unsigned)((n + 255) / 256), 256, 0, st, n, orig_index, (int)n0, (int32_t*)e->row_frame.p);
+    HG_HIP(hipGetLastError());
+    const EyeFrames F{n_frames, frame_stride, (const int32_t*)e->row_frame.p};
+    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st, nullptr,
+             (int32_t*)e->row_src.p, &F);
+    hipLaunchKernelGGL(k_frame_segments, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, (int)n0, n_frames, seg_first);
+    hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
+                       (char*)e->scratch.p);
+    HG_HIP(hipGetLastError());
+    std::vector<int32_t> seg((size_t)2 * n_frames + 1);
+    std::vector<double> purged((size_t)(n + n_frames) * 10);
+    HG_HIP(hipMemcpyAsync(seg.data(), e->seg.p, seg.size() * 4, hipMemcpyDeviceToHost, st));
+    HG_HIP(hipMemcpyAsync(purged.data(), e->purged.p, purged.size() * 8, hipMemcpyDeviceToHost, st));      // (rows no frame wrote are never looked at)
+    HG_HIP(hipStreamSynchronize(st));
+    int64_t kept = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t lo = seg[(size_t)f], nb = seg[(size_t)f + 1] - lo, kf = seg[(size_t)n_frames + 1 + f];
+        if (lo < 0 || nb < 0 || lo + nb > n || kf < 0 || kf > nb + 1) fail(HG_ERR_STATE, "frame %d: bad row bounds from the device", f);
+        kept += kf;
+    }
+    if (kept > out_cap) fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)out_cap);
+    if (kept > 0 && !out_rows) fail(HG_ERR_ARG, "null output rows");
+    int64_t at = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t lo = seg[(size_t)f], kf = seg[(size_t)n_frames + 1 + f];
+        frame_first[f] = (int32_t)at;
+        if (n_before_purge) n_before_purge[f] = (int32_t)(seg[(size_t)f + 1] - lo);
+        if (kf) memcpy(out_rows + at * 10, purged.data() + (size_t)(lo + f) * 10, (size_t)kf * 80);
+        at += kf;
+    }
+    frame_first[n_frames] = (int32_t)at;
 }
 
 // What the tracker's hand-over kernel reads after an ordinary frame's tail (eyes_frame_tail with n > 0): the same two buffers.

@@ -75,6 +75,18 @@ class Patcher(object):
             C.c_void_p(boxes_ptr), C.c_void_p(delta_angs_ptr) if delta_angs_ptr else None, int(n), w, h, C.c_void_p(out_ptr),
             _capi.np_dtype_code(out_dtype), int(ldo), C.c_void_p(stream)))
 
+    def extract_frames_device(self, frames_ptr, n_frames, frame_stride, frame_h, frame_w, ld, boxes_ptr, row_frame_ptr, n, out_size, out_ptr, out_dtype,
+                              ldo, stream=0, delta_angs_ptr=None, interpolation=0):
+        """Windows from a stack of same-size grey uint8 frames (hg_patcher_extract_frames_device): raw device pointers (ints); row i is
+        cut from frame ``row_frame[i]`` (int32 on the device), the bytes ``extract_device`` gives on that frame alone; a row whose frame
+        lies outside [0, n_frames) is all zero.  ``frame_stride``: bytes from one frame to the next.  Enqueued on ``stream``."""
+        filt = _capi.filter_code(interpolation)
+        w, h = int(out_size[0]), int(out_size[1])
+        _capi.check(_capi.lib().hg_patcher_extract_frames_device(
+            self._handle(), filt, C.c_void_p(frames_ptr), int(n_frames), int(frame_stride), int(frame_h), int(frame_w), int(ld), C.c_void_p(boxes_ptr),
+            C.c_void_p(delta_angs_ptr) if delta_angs_ptr else None, C.c_void_p(row_frame_ptr), int(n), w, h, C.c_void_p(out_ptr),
+            _capi.np_dtype_code(out_dtype), int(ldo), C.c_void_p(stream)))
+
     def close(self):
         if self._h is not None:
             _capi.lib().hg_patcher_free(self._h)
