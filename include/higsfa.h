@@ -731,12 +731,17 @@ int hg_tracker_step_frame_multi_device(hg_tracker* t, const void* frame_dev, int
  * x: (n, ldx) matrix in time order, a device pointer or (x_on_host != 0) a host pointer that is
  * copied to the device first.  Host outputs: evals (n_nodes, d), evecs
  * (n_nodes, d, d) column-major per node (column i = eigenvector i), mean (n_nodes, d);
- * timings_ms[2] (optional): statistics kernels, solve. */
+ * timings_ms[2] (optional): statistics kernels, solve.
+ * Refusals: HG_ERR_ARG for n < 3, d outside 1..128, an unknown dtype, a null pointer, a column outside [0, ldx);
+ * HG_ERR_STATE naming the first node whose B is not positive definite (a constant column; a column listed twice
+ * in one node, refused before the solve; for d <= 16 a NaN in the input) or whose Jacobi sweeps did not converge
+ * (info = 17 from the hand-written solver). */
 int hg_sfa_train_layer(const void* x, int x_on_host, int x_dtype, int64_t n, int64_t ldx, const int32_t* conn_host,
                        int32_t n_nodes, int32_t d, int device, double* evals_host, double* evecs_host,
                        double* mean_host, double* timings_ms);
 /* The PCA / whitening step of a node (mdp.nodes.PCANode / WhiteningNode train + stop_training): same statistics kernel, then the
- * eigen-decomposition of Cov(x) itself (the same solver on (Cov, I)): evals ascending, orthonormal eigenvectors. */
+ * eigen-decomposition of Cov(x) itself (the same solver on (Cov, I)): evals ascending, orthonormal eigenvectors.  A singular
+ * covariance (n <= d, a constant column, a column listed twice) is legal here; for d <= 16 a NaN in the input is HG_ERR_STATE (the sweeps cannot converge). */
 int hg_pca_train_layer(const void* x, int x_on_host, int x_dtype, int64_t n, int64_t ldx, const int32_t* conn_host,
                        int32_t n_nodes, int32_t d, int device, double* evals_host, double* evecs_host,
                        double* mean_host, double* timings_ms);

@@ -185,7 +185,9 @@ __global__ void k_sfa_finish(const double* __restrict__ partial, int n_nodes, in
 // with a decoupled diagonal block of huge eigenvalues (no rotation ever mixes it in; it sorts to the end).
 // rocSOLVER's batched dsygvj needs 8 ms for 1024 such 16 x 16 problems, dsygvd 31 ms; this takes < 0.2 ms.
 // A, B: [node][d*d] symmetric (row- or column-major alike).  evecs: column-major per node like LAPACK.
+// info[node]: 0, or j + 1 when the Cholesky pivot j is not positive, or kJ + 1 when the sweeps did not converge (a NaN never does).
 constexpr int kJ = 16, kJS = 17;   // padded size and LDS row stride (doubles)
+constexpr int kSweeps = 30;        // Jacobi sweeps at most; info = kJ + 1 when they did not suffice
 
 __global__ void __launch_bounds__(64) k_sygv16(const double* __restrict__ A, const double* __restrict__ B, int d, double* __restrict__ evals,
                                                double* __restrict__ evecs, int* __restrict__ info) {
@@ -253,7 +255,7 @@ __global__ void __launch_bounds__(64) k_sygv16(const double* __restrict__ A, con
     for (int e = tid; e < kJ * kJ; e += 64) Cm[(e >> 4) * kJS + (e & 15)] = X[(e >> 4) * kJS + (e & 15)];
     __syncthreads();
     // ---- cyclic Jacobi, round-robin pairs
-    for (int sweep = 0; sweep < 30; ++sweep) {
+    for (int sweep = 0; sweep <= kSweeps; ++sweep) {
         // convergence: off-diagonal mass of the real block against its diagonal
         double off = 0.0, dia = 0.0;
         for (int e = tid; e < kJ * kJ; e += 64) {
@@ -268,6 +270,12 @@ __global__ void __launch_bounds__(64) k_sygv16(const double* __restrict__ A, con
             dia += __shfl_xor(dia, m);
         }
         if (off <= 1e-30 * dia || off == 0.0) break;
+        if (sweep == kSweeps) {
+            // out of sweeps.  Rounding can hold the off-diagonal mass just above the stopping threshold of a matrix that is
+            // diagonal to working precision; anything above 1e-12 of the diagonal in norm (a NaN included) did not converge
+            if (tid == 0 && bad == 0 && !(off <= 1e-24 * dia)) bad = kJ + 1;
+            break;
+        }
         for (int step = 0; step < kJ - 1; ++step) {
             if (tid < 8) {
                 const int k = tid;
@@ -323,16 +331,18 @@ __global__ void __launch_bounds__(64) k_sygv16(const double* __restrict__ A, con
         }
 #pragma unroll
         for (int i = 0; i < kJ; ++i) X[i * kJS + c] = x[i];
-        lam[c] = Cm[c * kJS + c];
+        const double ev = Cm[c * kJS + c];
+        lam[c] = ev != ev ? __builtin_inf() : ev;   // ranking key: NaN as the largest value, so that the order below is total
     }
     __syncthreads();
     if (tid < kJ) {
+        // ties by index: with no NaN among the keys this is a total order, so ord[] is a permutation whatever the sweeps left
         int rank = 0;
         for (int j = 0; j < kJ; ++j) rank += (lam[j] < lam[tid] || (lam[j] == lam[tid] && j < tid)) ? 1 : 0;
         ord[rank] = tid;
     }
     __syncthreads();
-    if (tid < d) evals[(size_t)node * d + tid] = lam[ord[tid]];
+    if (tid < d) evals[(size_t)node * d + tid] = Cm[ord[tid] * kJS + ord[tid]];
     for (int e = tid; e < dd; e += 64) {
         const int col = e / d, row = e - col * d;
         evecs[(size_t)node * dd + e] = X[row * kJS + ord[col]];
@@ -407,6 +417,17 @@ int train_layer_impl(const void* x_in, int x_on_host, int x_dtype, int64_t n, in
         HG_HIP(hipSetDevice(device));
         for (int64_t i = 0; i < (int64_t)n_nodes * d; ++i)
             if (conn_host[i] < 0 || conn_host[i] >= ldx) hg::fail(HG_ERR_ARG, "connection %d out of range", conn_host[i]);
+        if (mode == 0) {
+            // a column listed twice in a node makes its covariance singular by construction; rounding decides whether the Cholesky
+            // factorisation notices (the last pivot is v - fl(v / fl(sqrt v))^2), so it is refused here (PCA takes it)
+            std::vector<int32_t> u(d);
+            for (int k = 0; k < n_nodes; ++k) {
+                std::copy(conn_host + (size_t)k * d, conn_host + (size_t)(k + 1) * d, u.begin());
+                std::sort(u.begin(), u.end());
+                const auto dup = std::adjacent_find(u.begin(), u.end());
+                if (dup != u.end()) hg::fail(HG_ERR_STATE, "node %d: input column %d listed twice (covariance not positive definite)", k, *dup);
+            }
+        }
         hg::DevBuf xbuf;
         const void* x_dev = x_in;
         if (x_on_host) {
@@ -455,10 +476,15 @@ int train_layer_impl(const void* x_in, int x_on_host, int x_dtype, int64_t n, in
         hg::DevBuf resid, sweeps;       // sygvj work outputs
         resid.alloc((size_t)n_nodes * 8);
         sweeps.alloc((size_t)n_nodes * 4);
-        hipEvent_t e0, e1, e2;
-        HG_HIP(hipEventCreate(&e0));
-        HG_HIP(hipEventCreate(&e1));
-        HG_HIP(hipEventCreate(&e2));
+        struct Events {      // released on every path out of this function, the failing ones included
+            hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+            ~Events() {
+                for (hipEvent_t ev : e)
+                    if (ev) (void)hipEventDestroy(ev);
+            }
+        } events;
+        for (hipEvent_t& ev : events.e) HG_HIP(hipEventCreate(&ev));
+        const hipEvent_t e0 = events.e[0], e1 = events.e[1], e2 = events.e[2];
         HG_HIP(hipEventRecord(e0, nullptr));
         const size_t lds = (size_t)(kTS + 1) * d * 8;
         const unsigned grid = (unsigned)(n_nodes * n_splits);
@@ -545,9 +571,6 @@ int train_layer_impl(const void* x_in, int x_on_host, int x_dtype, int64_t n, in
             timings_ms[0] = a;
             timings_ms[1] = b;
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        (void)hipEventDestroy(e2);
     });
 }
 
