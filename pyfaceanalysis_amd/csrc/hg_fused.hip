@@ -599,6 +599,7 @@ constexpr int kWeightLdsKiB = 64;       // target size of a node group's weights
 struct StageDev {
     DevBuf afrag, bias, kb1tab, chunks, runs, piece, koff, kmean, kcol, gcol, etab, pack_slot;
     DevBuf fold_frag, fold_bias;      // stage 1 of a plan with the link 0 -> 1 folded
+    DevBuf pair_kids, kb1tab_pre, bias_pre;      // a hoisted stage whose nodes have two children each (HostStage::pair_kids)
 };
 struct SubRunDev {
     DevBuf nodes[kMaxTail], tab[kMaxTail];
@@ -630,6 +631,8 @@ public:
     std::string stage_name(int i) const override {
         if (i == 1 && plan_->fuse01 && !plan_->opt.fold01)
             return plan_->stages[i].name + "  [link 0 -> 1 stays as it is: switched off (HIGSFA_NO_FOLD01)]";
+        if (i < (int)plan_->stages.size() && plan_->stages[i].sum_in && !plan_->opt.pair)
+            return plan_->stages[i].name + "; unpaired: switched off (HIGSFA_NO_PAIR)";
         if (i < (int)plan_->stages.size()) return plan_->stages[i].name;
         return plan_->tail_begin >= 0 ? std::string("row-major y written by the top-of-hierarchy launch (no unpack pass)")
                                       : std::string("fused unpack (fragment order -> row-major y)");
@@ -677,6 +680,11 @@ public:
             if (!s.gcol.empty()) d.gcol.upload(s.gcol.data(), s.gcol.size() * 4);
             if (!s.etab.empty()) d.etab.upload(s.etab.data(), s.etab.size() * 4);
             if (!s.pack_slot.empty()) d.pack_slot.upload(s.pack_slot.data(), s.pack_slot.size() * 4);
+            if (!s.pair_kids.empty()) {
+                d.pair_kids.upload(s.pair_kids.data(), s.pair_kids.size() * 4);
+                d.kb1tab_pre.upload(s.kb1tab_pre.data(), s.kb1tab_pre.size() * 4);
+                d.bias_pre.upload(s.bias_pre.data(), s.bias_pre.size() * 4);
+            }
             if (!s.chunks.empty()) {
                 d.chunks.upload(s.chunks.data(), s.chunks.size() * sizeof(DChunk));
                 d.runs.upload(s.runs.data(), s.runs.size() * sizeof(DRun));
@@ -754,7 +762,9 @@ public:
         record(1);
         f32x4* cur = (f32x4*)L.bufA.p;
         f32x4* nxt = (f32x4*)L.bufB.p;
+        bool in_summed = false;      // the stage about to run reads ONE tile set per node (the stage below stored the link summed)
         for (int si = 0; si < (int)plan_->stages.size(); ++si) {
+            if (in_summed && !on_sweep(si, n_tiles, sub_set)) fail(HG_ERR_STATE, "internal: stage %d was handed a summed link but does not run the node-group sweep", si);
             if (plan_->tail_begin >= 0 && si == plan_->tail_start(n_tiles)) {
                 launch_top(si, cur, n_tiles, y, y_dtype, y_cols, ldy, n, st);
                 record((int)plan_->stages.size() + 1 - si);      // this stage, the ones above and the unpack pass it replaces
@@ -786,8 +796,18 @@ public:
                 covered = launch_front(L, s, d, P, x, x_dtype, ldx, n, n_tiles, cur, st) ? 2 : 1;
             else if (s.kind == 3)
                 launch_prod(s, d, P, n_tiles, si, st);
-            else if (!launch_splitm(s, P, n_tiles, st))
-                launch_stage(s, P, n_tiles, si, st);
+            else if (!launch_splitm(s, P, n_tiles, st)) {
+                if (in_summed) {      // a hoisted stage of one child per node whose first bias adds nothing: (-0.0f) + x == x
+                    P.kb1tab = (const int2*)d.kb1tab_pre.p;
+                    P.bias = (const float*)d.bias_pre.p;
+                    P.kb1 = s.mt1;
+                    P.n_kids = 1;
+                    P.nb_in = s.n_nodes * s.mt1;
+                }
+                in_summed = link_summed(si, n_tiles, sub_set, in_summed);
+                if (in_summed) launch_stage_pair(s, plan_->stages[si + 1], dev_[si + 1], P, n_tiles, si, st);
+                else launch_stage(s, P, n_tiles, si, st);
+            }
             if (covered == 1) std::swap(cur, nxt);      // (fused front: layer 1 wrote `cur`, which stage 2 reads)
             record(covered);
             si += covered - 1;
@@ -1137,13 +1157,18 @@ private:
     // a k_stage workgroup first copies 27-52 KiB of weights into LDS (5 us), which small batches never earn back
     // (N = 16: 92 -> 70 us per call, N = 340: 137 -> 129, N = 1024: the same; grids of more than ~500 workgroups: k_stage wins).
     // Returns false where the layer does not qualify.
-    bool launch_splitm(const HostStage& s, const StageParams& P, int n_tiles, hipStream_t st) {
+    // (the qualifying test alone, which launches nothing: run_range asks it about the NEXT layer too)
+    bool splitm_takes(const HostStage& s, int n_tiles) const {
         const int T = n_tiles >= 2 * 256 / std::max(1, s.n_nodes) ? 2 : 1;
         const int groups = (n_tiles + T - 1) / T;
         const int64_t wgs = (int64_t)groups * s.n_nodes;
-        if (!(s.kind == 0 && (!s.rem4 || s.mt1 == s.mt2) && (s.rem4 || !s.pack_out) && s.mt1 * s.nf <= 8 &&
-              (s.n_nodes <= plan_->opt.splitm_max_nodes ? (int64_t)s.n_nodes * n_tiles <= 8192 : wgs <= plan_->opt.splitm_max_wgs)))
-            return false;
+        return s.kind == 0 && (!s.rem4 || s.mt1 == s.mt2) && (s.rem4 || !s.pack_out) && s.mt1 * s.nf <= 8 &&
+               (s.n_nodes <= plan_->opt.splitm_max_nodes ? (int64_t)s.n_nodes * n_tiles <= 8192 : wgs <= plan_->opt.splitm_max_wgs);
+    }
+    bool launch_splitm(const HostStage& s, const StageParams& P, int n_tiles, hipStream_t st) {
+        if (!splitm_takes(s, n_tiles)) return false;
+        const int T = n_tiles >= 2 * 256 / std::max(1, s.n_nodes) ? 2 : 1;
+        const int groups = (n_tiles + T - 1) / T;
         const int nwv = std::max(s.mt1, s.has_exp ? s.mt2 : 1);
         const size_t lds_bytes = (size_t)std::max(1, s.nf) * s.mt1 * T * 1024;
         const unsigned grid = (unsigned)(groups * s.n_nodes);
@@ -1199,6 +1224,67 @@ private:
 #ifdef HIGSFA_DIAG
         if (P.stamps) stage_stamps_report(si, blocks, nw, st);
 #endif
+    }
+
+    // ---- summed links ----
+    // Stage si reaches launch_stage in a call of n_tiles: run_range's dispatch, asked without launching anything
+    bool on_sweep(int si, int n_tiles, int sub_set) const {
+        if (si < 0 || si >= (int)plan_->stages.size()) return false;
+        if (plan_->tail_begin >= 0 && si >= plan_->tail_start(n_tiles)) return false;
+        for (const SubRun& r : plan_->sub_runs)
+            if (r.set == sub_set && r.begin <= si && si < r.begin + r.len && plan_->sub_run_pays(r, n_tiles)) return false;
+        const HostStage& s = plan_->stages[si];
+        return s.kind == 0 && !s.from_x && !splitm_takes(s, n_tiles);
+    }
+    // pairs whose fragments a workgroup keeps in LDS: HIGSFA_SUM_LDS KiB as for k_stage_sum's node groups, at least one pair, at most 144 KiB
+    int pair_group(const HostStage& s) const {
+        const int kib = 2 * std::max(1, s.node_blocks);
+        return std::max(1, std::min(plan_->opt.sum_lds_kib, 144) / kib);
+    }
+    static int pair_waves(int n_tiles) {
+        int nw = 8;
+        while (nw * kPairTiles > std::max(n_tiles, 1) && nw > 1) nw >>= 1;
+        return nw;
+    }
+    // The link si -> si + 1 is stored summed in this call: the plan has pairs for it, both stages run through launch_stage, the producer has
+    // the shape k_stage_sum_pair is built for (a hoisted stage itself, 4 x 4 tiles, compile-time expansion) and enough work in pair groups
+    // (sweep_shape's criterion on pair groups x tile groups; FusedOptions::pair_min_wgs)
+    bool link_summed(int si, int n_tiles, int sub_set, bool in_summed) const {
+        if (si + 1 >= (int)plan_->stages.size()) return false;
+        const HostStage& s = plan_->stages[si];
+        const HostStage& p = plan_->stages[si + 1];
+        if (p.pair_kids.empty() || !s.sum_in || s.n_nodes != 2 * p.n_nodes) return false;
+        if (!in_summed && (s.pair_kids.empty() || s.kb1 != 2 * s.mt1)) return false;      // the kernel's two input forms: one child per node, or two
+        const bool fs = s.has_exp && s.nf == 2 && s.funcs[0].kind == E_IDENTITY && s.funcs[1].kind == E_ABS_POW && !plan_->opt.no_fspec;
+        if (!fs || s.mt1 != 4 || s.mt2 != 4 || p.mt1 != 4 || s.mto != 4 || s.pack_out || s.rem4) return false;
+        if (!on_sweep(si, n_tiles, sub_set) || !on_sweep(si + 1, n_tiles, sub_set)) return false;
+        const int ppg = pair_group(s), nw = pair_waves(n_tiles);
+        const int64_t n_groups = (p.n_nodes + ppg - 1) / ppg, tile_groups = (n_tiles + nw * kPairTiles - 1) / (nw * kPairTiles);
+        return n_groups * tile_groups >= plan_->opt.pair_min_wgs;
+    }
+    // launch_stage for the producer of a summed link: pair groups in the place of node groups, one tile set stored per node of `parent`
+    void launch_stage_pair(const HostStage& s, const HostStage& parent, const StageDev& pd, StageParams& P, int n_tiles, int si, hipStream_t st) {
+        const int ppg = std::min(pair_group(s), parent.n_nodes), nw = pair_waves(n_tiles), T = kPairTiles;
+        const int n_groups = (parent.n_nodes + ppg - 1) / ppg;
+        const int tile_groups = (n_tiles + nw * T - 1) / (nw * T);
+        const size_t lds_bytes = (size_t)2 * ppg * ((size_t)s.node_blocks * 1024 + (size_t)s.bias_floats * 4 + (size_t)P.kb1 * 8) + (size_t)ppg * 256;
+        StageFn fn = pick_stage_sum_pair(T);
+        if (!fn) fail(HG_ERR_STATE, "internal: no pair kernel of %d tiles per wave", T);
+        P.pair_kids = (const int2*)pd.pair_kids.p;
+        P.pair_bias = (const float*)pd.bias.p;      // the parent stage's own floats (not bias_pre)
+        P.pair_bias_floats = parent.bias_floats;
+        P.n_pairs = parent.n_nodes;
+        P.nb_out = parent.n_nodes * s.mto;
+        P.nodes_per_group = ppg;
+        P.nodes_per_wg = ppg;
+        P.n_chunks = n_groups;
+        P.tile_groups = tile_groups;
+        P.tile_parts = sweep_tile_parts(n_groups, tile_groups, resident_blocks(fn, nw * 64, lds_bytes));
+        const int64_t blocks = (int64_t)((n_groups + 7) / 8) * 8 * P.tile_parts;
+        if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
+        set_lds_limit(fn, lds_bytes);
+        if (plan_->opt.debug) fprintf(stderr, "[pair stage %d] pairs %d per group %d shape %dx%d lds %zu tile_groups %d parts %d kids in %d\n", si, parent.n_nodes, ppg, nw, T, lds_bytes, tile_groups, P.tile_parts, P.n_kids);
+        hipLaunchKernelGGL(fn, (unsigned)blocks, nw * 64, lds_bytes, st, P);
     }
 
     // fragment order -> the caller's row-major y (where no top-of-hierarchy launch wrote it)
@@ -1433,6 +1519,7 @@ std::unique_ptr<Executor> make_fused_executor(const TNode& root, std::string* wh
     fused::FusedOptions opt = fused::FusedOptions::from_env();
     opt.hoist = getenv("HIGSFA_NO_HOIST") == nullptr;      // (an executor's switch, not the planner's: DESIGN.md §9)
     opt.fold01 = getenv("HIGSFA_NO_FOLD01") == nullptr;    // likewise
+    opt.pair = opt.hoist && getenv("HIGSFA_NO_PAIR") == nullptr;      // summed links ride on the hoisted ones
     auto plan = fused::build_fused_plan(root, opt, why_not);
     if (!plan) return nullptr;
     return std::make_unique<FusedExecutor>(std::move(plan));

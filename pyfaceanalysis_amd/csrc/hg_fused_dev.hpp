@@ -83,6 +83,13 @@ struct StageParams {
     // blocks alone (node_blocks = 8, no first-affine blocks in front of them).
     const f32x4* fold_frag;
     const float* fold_bias;
+    // Summed link, producer side (k_stage_sum_pair, hg_fused_sum.hip): the nodes of this stage taken two by two, pair j = the children of node j of
+    // the stage above in the order that stage adds them; the output holds ONE tile set per pair, (pair_bias[j] + y of .x) + y of .y, at blocks
+    // j * mto .. (nb_out = n_pairs x mto).  pair_bias: the stage above's own bias array (pair_bias_floats per node, the first bias in front).
+    // The consumer side needs nothing new: a hoisted stage of one child per node (kb1 = mt1, n_kids = 1) whose first bias is -0.0f.
+    const int2* pair_kids;
+    const float* pair_bias;
+    int32_t n_pairs, pair_bias_floats;
 };
 
 __device__ __forceinline__ unsigned long long stamp_now() {
@@ -465,6 +472,8 @@ StageFn pick_igsfa(int ms, int mo, int T, int kb1);                   // hg_fuse
 StageFn pick_igfold(int mo, int T, bool fs = false);
 StageFn pick_prod(int mt1, int mt2, int T);                           // hg_fused_prod.hip
 StageFn pick_stage_sum(int mt1, int mt2, int T, bool fs);             // hg_fused_sum.hip: k_stage for a layer whose first affine was hoisted
+StageFn pick_stage_sum_pair(int T);                                        // ... storing its nodes' tiles summed per node of the layer above (4 x 4 tiles, compile-time expansion)
+constexpr int kPairTiles = 1;                                         // batch tiles per wave of k_stage_sum_pair (two do not fit 128 registers)
 void launch_igfold_split(const StageParams& P, int mo, int n_tiles, hipStream_t st);                                                          // hg_fused_igsfa.hip
 void launch_im2frag(const void* x, int x_dtype, int64_t ldx, int64_t n_rows, int n_tiles, int nb, const int32_t* gcol, f32x4* out,
                     int vec4, hipStream_t st);

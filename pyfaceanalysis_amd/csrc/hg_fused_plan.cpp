@@ -768,6 +768,7 @@ struct Planner : FusedPlan {
                << ", " << hs.mfma_per_tile << " MFMA/tile (issued: " << hs.mfma16_tile << " x 16x16x4 + " << hs.mfma4_tile << " x 4x4x1), " << hs.afrag.size() * 4 / 1024
                << " KiB weights, out " << hs.nb_out << " blocks/tile";
             hs.name = os.str();
+            if (st.sum_in && opt.pair) plan_pairs(st, hs);
         }
         plan_slot_major();
         fuse01 = can_fuse01();
@@ -788,6 +789,37 @@ struct Planner : FusedPlan {
         plan_subtree();
         for (auto& hs : stages)      // the front kernels read piece_col as int2 pairs: never an empty table
             if (!hs.chunks.empty()) hs.piece_col.resize(std::max<size_t>(hs.piece_col.size(), 2));
+    }
+
+    // Summed links (HostStage::pair_kids).  A hoisted stage whose nodes ALL have exactly two children gets what the layer
+    // below needs to store one tile set per node — each node's children in first-read order — and what this stage needs to read it: a
+    // K-block table of one child per node and a bias array whose first bias is -0.0f.  Whether a call uses them is the executor's business
+    // (both layers on the node-group sweep, the preset shape, enough work); every other kernel family keeps reading kb1tab and bias.
+    void plan_pairs(const FStage& st, HostStage& hs) {
+        size_t lo = ~(size_t)0, hi = 0;
+        for (auto& nd : st.nodes) {
+            lo = std::min(lo, nd.kids.size());
+            hi = std::max(hi, nd.kids.size());
+        }
+        if (lo != 2 || hi != 2) {
+            hs.name += lo == hi ? "; unpaired: " + std::to_string(lo) + " children per node" : "; unpaired: " + std::to_string(lo) + " to " + std::to_string(hi) + " children per node";
+            return;
+        }
+        const int n = hs.n_nodes;
+        hs.pair_kids.reserve((size_t)n * 2);
+        for (auto& nd : st.nodes) {
+            hs.pair_kids.push_back(nd.kids[0]);
+            hs.pair_kids.push_back(nd.kids[1]);
+        }
+        hs.kb1tab_pre.assign(((size_t)n * hs.mt1 + 8) * 2, 0);
+        for (int ni = 0; ni < n; ++ni)
+            for (int mt = 0; mt < hs.mt1; ++mt) {
+                hs.kb1tab_pre[((size_t)ni * hs.mt1 + mt) * 2] = ni * hs.mt1 + mt;
+                hs.kb1tab_pre[((size_t)ni * hs.mt1 + mt) * 2 + 1] = 1;
+            }
+        hs.bias_pre = hs.bias;
+        for (int ni = 0; ni < n; ++ni) std::fill_n(hs.bias_pre.begin() + (size_t)ni * hs.bias_floats, hs.mt1 * 16, -0.0f);
+        hs.name += "; paired: the layer below may store (bias + child 0) + child 1 once per node where both layers run the node-group sweep";
     }
 
     // Stage 0: group consecutive nodes into chunks whose distinct input columns fit the LDS tile,

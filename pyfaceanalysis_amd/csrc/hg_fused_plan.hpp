@@ -50,6 +50,10 @@ struct FusedOptions {
                                   // not an environment switch of the planner: the executor turns it on unless HIGSFA_NO_HOIST is set
     bool fold01 = false;          // fold layer 0's second affine into layer 1's first inside the front kernels (Planner::plan_fold01); like hoist,
                                   // the executor's switch: on unless HIGSFA_NO_FOLD01 is set
+    bool pair = false;            // record, for hoisted stages whose parents all have two children, what the layer below needs to store
+                                  // (bias + child 0) + child 1 once per parent (Planner::plan_pairs); rides on hoist, and like it
+                                  // the executor's switch: on unless HIGSFA_NO_PAIR is set
+    int pair_min_wgs = 512;       // HIGSFA_PAIR_WGS: a link is stored summed in a call while pair groups x tile groups of its producer reach this
     static FusedOptions from_env() {
         FusedOptions o;
         o.no_rem4 = getenv("HIGSFA_NO_REM4") != nullptr;
@@ -68,6 +72,7 @@ struct FusedOptions {
         if (const char* e = getenv("HIGSFA_SUBTREE")) o.subtree_max_tiles = std::max(0, atoi(e));
         if (const char* e = getenv("HIGSFA_SUBTREE_WGS")) o.subtree_max_wgs = std::max(0, atoi(e));
         if (const char* e = getenv("HIGSFA_SUM_LDS")) o.sum_lds_kib = std::max(1, atoi(e));
+        if (const char* e = getenv("HIGSFA_PAIR_WGS")) o.pair_min_wgs = std::max(0, atoi(e));
         if (const char* e = getenv("HIGSFA_TAIL")) o.tail_max = std::max(0, std::min(atoi(e), kMaxTail));
         return o;
     }
@@ -125,6 +130,12 @@ struct HostStage {
     // fold_frag [node][child 0..1][function 0..1][tile: 0 = 16x16 form, 1 = 4x4 form][lane][4]: A fragments of F_c = A2_c A1[rows of c, :]
     // (k = z0 feature 4 r + lane group of child c, per function; rows = z1 features), fold_bias [node][2 x 16]: z1's ONE bias vector.
     std::vector<float> fold_frag, fold_bias;
+    // Summed link (FusedOptions::pair; hoisted stages whose nodes all have exactly two children).  The layer below may then store ONE tile set
+    // per node of this stage, (bias + child 0's tiles) + child 1's tiles, in place of its own two (k_stage_sum_pair); this stage reads it as a
+    // hoisted stage of one child per node whose first bias adds nothing.  Empty where the stage has no pairs.
+    std::vector<int32_t> pair_kids;    // int2 per node: its two children in FNode::kids order (first read; neither ascending nor adjacent)
+    std::vector<int32_t> kb1tab_pre;   // int2 [node][mt1] = {node * mt1 + mt, 1}, and the eight spare entries every table carries
+    std::vector<float> bias_pre;       // `bias` with the first mt1 x 16 floats of every node = -0.0f: (-0.0f) + x is x, bit for bit, for every x
 };
 
 struct FusedPlan {
