@@ -133,6 +133,18 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
         if (tile[0] >= P.n_tiles) continue;
 #pragma unroll
         for (int t = 0; t < T; ++t) trow[t] = (uint32_t)(tile[t] < P.n_tiles ? tile[t] : tile[0]) * (uint32_t)P.nb_in;
+        // HG_VISIT_WAITS, packed remainder output: pack_slot[node] is read a visit ahead, in front of the visit's block requests — read in
+        // node_tail it is a load waited for between two runs of stores
+        // (a stage that does not pack has no such table: it reads a word of its K-block table instead, unconditionally — a load behind a
+        // branch makes the compiler drain the counter where the two paths meet)
+        constexpr bool SLOT = REM && HG_VISIT_WAITS != 0;
+        const int32_t* const slots = P.pack_base > 0 ? P.pack_slot : (const int32_t*)P.kb1tab;
+        const int slot_on = P.pack_base > 0 ? 1 : 0;
+        int slot_q = 0;
+        if constexpr (SLOT) {
+            slot_q = slots[g0 * slot_on];
+            asm volatile("" : "+v"(slot_q));
+        }
         if constexpr (KBF > 0) {
             f32x4 bq[KBF][T];
 #pragma unroll
@@ -145,6 +157,7 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
                     for (int t = 0; t < T; ++t) bq[kbi][t] = P.in[(size_t)(trow[t] + sb0) * 64 + lane];
                 }
             }
+            if constexpr (HG_VISIT_WAITS != 0) arrived(bq);
             for (int grp = part; grp < P.tile_groups; grp += P.tile_parts) {
                 const int tn0 = ((grp + P.tile_parts) * nw + wave) * T;
                 const bool has_next = grp + P.tile_parts < P.tile_groups && tn0 < P.n_tiles;
@@ -180,9 +193,11 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
 #pragma unroll
                         for (int t = 0; t < T; ++t) add_rem4(z[MT1 - 1][t], d4[t]);
                     }
+                    const int slot = __builtin_amdgcn_readfirstlane(slot_q);
                     {   // next visit's blocks: next node of this group on the same tiles, or the group's first node on the next tiles
                         const bool in_group = ln + 1 < gn;
                         const int2* ktn = in_group ? kt + KBF : stab;
+                        if constexpr (SLOT) slot_q = slots[(in_group ? g0 + ln + 1 : g0) * slot_on];
                         uint32_t rw[T];
 #pragma unroll
                         for (int t = 0; t < T; ++t) rw[t] = in_group ? trow[t] : trow_nx[t];
@@ -198,7 +213,7 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
                         }
                     }
                     if (STAMP) ts1 = stamp_now();
-                    node_tail<MT1, MT2, T, REM, FS>(P, wA2, b1 + MT1 * 16, g0 + ln, z, tile, lane);
+                    node_tail<MT1, MT2, T, REM, FS, false, HG_VISIT_WAITS != 0>(P, wA2, b1 + MT1 * 16, g0 + ln, z, tile, lane, nullptr, slot);
                     if (STAMP) {
                         unsigned long long ts2 = stamp_now();
                         t_g1 += ts1 - ts0;
@@ -227,6 +242,7 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
                 for (int t = 0; t < T; ++t) bf[t] = P.in[(size_t)(trow[t] + sb0) * 64 + lane];
             }
         }
+        if constexpr (HG_VISIT_WAITS != 0) arrived(bf);
         for (int grp = part; grp < P.tile_groups; grp += P.tile_parts) {
             // rows of the tile group after this one (or this one again when it is the last)
             const int tn0 = ((grp + P.tile_parts) * nw + wave) * T;
@@ -278,38 +294,52 @@ __global__ void __launch_bounds__(512, 4) k_stage(StageParams P) {
                         for (int t = 0; t < T; ++t) bf[t] = bfn[t];
                         nk = nkn;
                     };
+                    if constexpr (HG_VISIT_WAITS != 0) {
+                        // the visit's first block on its own: it was requested before the previous visit's stores, the blocks in the loop
+                        // after them — one wait in a shared loop header would have to cover both, and retire the stores
+                        kstep(0, a0, a1);
+                        for (int kbi = 1; kbi < P.kb1; kbi += 2) {
+                            kstep(kbi, a1, a0);
+                            if (kbi + 1 < P.kb1) kstep(kbi + 1, a0, a1);
+                        }
+                    } else
                     for (int kbi = 0; kbi < P.kb1; kbi += 2) {
                         kstep(kbi, a0, a1);
                         if (kbi + 1 < P.kb1) kstep(kbi + 1, a1, a0);
                     }
-                } else
-                for (int kbi = 0; kbi < P.kb1; ++kbi) {
-                    const bool in_node = kbi + 1 < P.kb1;
-                    const bool in_group = in_node || ln + 1 < gn;
-                    const int2 kbn = in_node ? kt[kbi + 1] : (ln + 1 < gn ? kt[P.kb1] : stab[0]);
-                    const int sbn = HG_HOT(__builtin_amdgcn_readfirstlane(kbn.x));
-                    const int nkn = __builtin_amdgcn_readfirstlane(kbn.y);
-                    if constexpr (REM) {      // (only remainder-tile stages can have slot-major packed input: plan_slot_major)
-                        uint32_t rw[T];
+                } else {
+                    auto kstep1 = [&](int kbi) {
+                        const bool in_node = kbi + 1 < P.kb1;
+                        const bool in_group = in_node || ln + 1 < gn;
+                        const int2 kbn = in_node ? kt[kbi + 1] : (ln + 1 < gn ? kt[P.kb1] : stab[0]);
+                        const int sbn = HG_HOT(__builtin_amdgcn_readfirstlane(kbn.x));
+                        const int nkn = __builtin_amdgcn_readfirstlane(kbn.y);
+                        if constexpr (REM) {      // (only remainder-tile stages can have slot-major packed input: plan_slot_major)
+                            uint32_t rw[T];
 #pragma unroll
-                        for (int t = 0; t < T; ++t) rw[t] = in_group ? trow[t] : trow_nx[t];
-                        load_kblock<T>(P, rw, sbn, nkn, lane, bfn);
-                    } else {
+                            for (int t = 0; t < T; ++t) rw[t] = in_group ? trow[t] : trow_nx[t];
+                            load_kblock<T>(P, rw, sbn, nkn, lane, bfn);
+                        } else {
 #pragma unroll
-                        for (int t = 0; t < T; ++t) bfn[t] = P.in[(size_t)((in_group ? trow[t] : trow_nx[t]) + sbn) * 64 + lane];
-                    }
-                    if constexpr (REM) gemm_block_rem<MT1, T>(wA1 + kbi * MT1 * 64, bf, z, d4, nk & 255, (nk >> 8) & 255);
-                    else gemm_block<MT1, T, FS>(wA1 + kbi * MT1 * 64, bf, z, nk & 255, (nk >> 8) & 255);
+                            for (int t = 0; t < T; ++t) bfn[t] = P.in[(size_t)((in_group ? trow[t] : trow_nx[t]) + sbn) * 64 + lane];
+                        }
+                        if constexpr (REM) gemm_block_rem<MT1, T>(wA1 + kbi * MT1 * 64, bf, z, d4, nk & 255, (nk >> 8) & 255);
+                        else gemm_block<MT1, T, FS>(wA1 + kbi * MT1 * 64, bf, z, nk & 255, (nk >> 8) & 255);
 #pragma unroll
-                    for (int t = 0; t < T; ++t) bf[t] = bfn[t];
-                    nk = nkn;
+                        for (int t = 0; t < T; ++t) bf[t] = bfn[t];
+                        nk = nkn;
+                    };
+                    if constexpr (HG_VISIT_WAITS != 0) kstep1(0);      // on its own, as above
+                    for (int kbi = HG_VISIT_WAITS ? 1 : 0; kbi < P.kb1; ++kbi) kstep1(kbi);
                 }
                 if constexpr (REM) {
 #pragma unroll
                     for (int t = 0; t < T; ++t) add_rem4(z[MT1 - 1][t], d4[t]);
                 }
                 if (STAMP) ts1 = stamp_now();
-                node_tail<MT1, MT2, T, REM, FS>(P, wA2, b1 + MT1 * 16, g0 + ln, z, tile, lane);
+                const int slot = __builtin_amdgcn_readfirstlane(slot_q);
+                if constexpr (SLOT) slot_q = slots[(ln + 1 < gn ? g0 + ln + 1 : g0) * slot_on];
+                node_tail<MT1, MT2, T, REM, FS, false, HG_VISIT_WAITS != 0>(P, wA2, b1 + MT1 * 16, g0 + ln, z, tile, lane, nullptr, slot);
                 if (STAMP) {
                     unsigned long long ts2 = stamp_now();
                     t_g1 += ts1 - ts0;

@@ -144,6 +144,9 @@ __device__ __forceinline__ f32x4 apply_func_uniform(int func, float expo, f32x4 
     return e;
 }
 
+#ifndef HG_VISIT_WAITS
+#define HG_VISIT_WAITS 1      // (A/B switch: HIGSFA_CXXFLAGS=-DHG_VISIT_WAITS=0) k_stage's node-group sweep: see node_tail's DUP and arrived(), DESIGN.md §6.11
+#endif
 #ifndef HG_POW_PREFETCH
 #define HG_POW_PREFETCH 1      // (A/B switch: HIGSFA_CXXFLAGS=-DHG_POW_PREFETCH=0)
 #endif
@@ -305,28 +308,52 @@ __device__ __forceinline__ float* packed_slot_ptr(const StageParams& P, int tile
     return P.pack_soa ? blk + (slot & 3) * 64 + lane : blk + lane * 4 + (slot & 3);
 }
 
+// k_stage's entry into its visit loop (HG_VISIT_WAITS): the blocks requested in front of the loop are made to arrive there (the
+// compiler waits for a register an asm statement reads), so that the loop header's two predecessors agree — nothing younger than the
+// prefetched blocks is awaited — and the back edge's counted wait survives the merge.  The first visit waited for these blocks anyway.
+template <int A, int B>
+__device__ __forceinline__ void arrived(f32x4 (&v)[A][B]) {
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int b = 0; b < B; ++b) asm volatile("" : "+v"(v[a][b]));
+}
+template <int B>
+__device__ __forceinline__ void arrived(f32x4 (&v)[B]) {
+#pragma unroll
+    for (int b = 0; b < B; ++b) asm volatile("" : "+v"(v[b]));
+}
+
 // Second half of a node: expansion of the z accumulators in registers, second affine, store.
 // wA2 / b2 point at this node's A2 fragments (+lane) and bias-2 fragment; address space (LDS or
 // global) is resolved after inlining.
 // FS: the expansion is (identity, |x|^p) and known at compile time (as in the front kernel): no function loop, no kind branches.
 // LEAN (with FS): m-tile-outer GEMMs and no fragment prefetch — 28 registers fewer, for callers that hold prefetched input blocks across this
 // call (k_stage_sum); the same MFMAs in the same order per accumulator.
-template <int MT1, int MT2, int T, bool REM = false, bool FS = false, bool LEAN = false, typename WP, typename BP>
+// DUP (k_stage under HG_VISIT_WAITS; the caller's tile[0] exists): a wave whose tile t does not exist computed on tile[0]'s blocks
+// (the callers' trow) and stores that duplicate to tile[0]'s own blocks and slots as well — the same wave, the same bits, twice — so that
+// the stores stand in straight-line code and the compiler can count them: the next visit's first wait then covers its prefetched
+// blocks alone and not the acknowledgement of these stores.  Such a caller also passes the node's packed slot (slot_in).
+template <int MT1, int MT2, int T, bool REM = false, bool FS = false, bool LEAN = false, bool DUP = false, typename WP, typename BP>
 __device__ __forceinline__ void node_tail(const StageParams& P, WP wA2, BP b2, int node, f32x4 (&z)[MT1][T],
-                                          const int (&tile)[T], int lane, float* rscr = nullptr) {      // rscr: this wave's 256 floats for rem4_total_lds (REM)
+                                          const int (&tile_in)[T], int lane, float* rscr = nullptr, int slot_in = 0) {      // rscr: this wave's 256 floats for rem4_total_lds (REM)
     const int g = lane >> 4;
     const int out_blk = node * P.mto;
+    int tile[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) tile[t] = DUP && tile_in[t] >= P.n_tiles ? tile_in[0] : tile_in[t];
 #ifdef HIGSFA_DIAG
     const bool no_store = (P.whatif & 2) != 0;
 #else
     constexpr bool no_store = false;
 #endif
-    if (!P.has_exp) {
+    if (!(FS && DUP) && !P.has_exp) {      // (FS: every caller picks such an instantiation for a stage with an expansion only — and a second
+                                           // store path that no launch takes is still one the compiler has to count with)
 #pragma unroll
         for (int mt = 0; mt < MT1; ++mt)
 #pragma unroll
             for (int t = 0; t < T; ++t)
-                if (tile[t] < P.n_tiles) P.out[((size_t)tile[t] * P.nb_out + out_blk + mt) * 64 + lane] = z[mt][t];
+                if (DUP || tile[t] < P.n_tiles) P.out[((size_t)tile[t] * P.nb_out + out_blk + mt) * 64 + lane] = z[mt][t];
         return;
     }
     f32x4 y[MT2][T];
@@ -402,7 +429,28 @@ __device__ __forceinline__ void node_tail(const StageParams& P, WP wA2, BP b2, i
             if (rscr) y[MT2 - 1][t][0] += rem4_total_lds(d4[t], rscr, lane);
             else add_rem4(y[MT2 - 1][t], d4[t]);
         }
-        if (P.pack_base > 0) {      // full tiles as blocks; the remainder rows into this node's register of the shared block
+        if constexpr (DUP) {
+            // the full tiles in one run for both layouts, then T stores on either side of ONE branch: every path of this function issues
+            // MT2 x T stores, and the compiler counts them.  The slot comes from the caller, who read pack_slot[node] a visit ahead: read
+            // here, between the block stores and the slot stores, it was a load waited for with the block stores in front of it.
+            const bool packed = P.pack_base > 0;
+            const int blk0 = packed ? node * (MT2 - 1) : out_blk;
+#pragma unroll
+            for (int mt = 0; mt < MT2 - 1; ++mt)
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    if (!no_store) P.out[((size_t)tile[t] * P.nb_out + blk0 + mt) * 64 + lane] = y[mt][t];
+            if (packed) {
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    if (!no_store) *packed_slot_ptr(P, tile[t], slot_in, lane) = y[MT2 - 1][t][0];
+            } else {
+#pragma unroll
+                for (int t = 0; t < T; ++t)
+                    if (!no_store) P.out[((size_t)tile[t] * P.nb_out + out_blk + MT2 - 1) * 64 + lane] = y[MT2 - 1][t];
+            }
+            return;
+        } else if (P.pack_base > 0) {      // full tiles as blocks; the remainder rows into this node's register of the shared block
 #pragma unroll
             for (int mt = 0; mt < MT2 - 1; ++mt)
 #pragma unroll
@@ -420,7 +468,7 @@ __device__ __forceinline__ void node_tail(const StageParams& P, WP wA2, BP b2, i
     for (int mt = 0; mt < MT2; ++mt)
 #pragma unroll
         for (int t = 0; t < T; ++t)
-            if (tile[t] < P.n_tiles && !no_store) P.out[((size_t)tile[t] * P.nb_out + out_blk + mt) * 64 + lane] = y[mt][t];
+            if ((DUP || tile[t] < P.n_tiles) && !no_store) P.out[((size_t)tile[t] * P.nb_out + out_blk + mt) * 64 + lane] = y[mt][t];
 }
 
 
