@@ -73,7 +73,7 @@ k_gauss_regression(const T* __restrict__ x, int64_t ldx, int64_t n, int K, int d
         lmax = fmax(lmax, v);
     }
     for (int o = 32; o > 0; o >>= 1) lmax = fmax(lmax, __shfl_xor(lmax, o));
-    double sw = 0, swa = 0, swa2 = 0;
+    double sw = 0, swa = 0;
 #pragma unroll
     for (int s = 0; s < kMaxClasses / 64; ++s) {
         int c = lane + 64 * s;
@@ -81,19 +81,15 @@ k_gauss_regression(const T* __restrict__ x, int64_t ldx, int64_t n, int K, int d
             double w = exp(lp[s] - lmax), a = avg[c];
             sw += w;
             swa += w * a;
-            swa2 += w * a * a;
         }
     }
     for (int o = 32; o > 0; o >>= 1) {
         sw += __shfl_xor(sw, o);
         swa += __shfl_xor(swa, o);
-        swa2 += __shfl_xor(swa2, o);
     }
-    if (lane == 0) {
-        double reg = swa / sw;
-        out_reg[row] = reg;
-        if (out_std) out_std[row] = sqrt(fmax(swa2 / sw - reg * reg, 0.0));
-    }
+    const double reg = swa / sw;
+    if (lane == 0) out_reg[row] = reg;
+    if (out_std) hg::out_std_two_pass(lp, lmax, lane, K, avg, reg, sw, out_std + row);
 }
 
 // The workgroup form (round 4): hg_gauss_dev.hpp, shared with the cascade's stage kernel.
@@ -144,6 +140,7 @@ void launch(hg_gauss* g, const void* x, int x_dtype, int64_t n, int64_t ldx, dou
     if (n > 0x7fffffffll) hg::fail(HG_ERR_ARG, "too many rows");
     if (x_dtype != HG_F32 && x_dtype != HG_F64) hg::fail(HG_ERR_ARG, "feature dtype must be HG_F32 or HG_F64");
     const bool no_wg = getenv("HIGSFA_GAUSS_WAVE") != nullptr;      // tests: the one-wave-per-row kernel only (read per call)
+    const bool debug = getenv("HIGSFA_DEBUG") != nullptr;           // one line per launch, like the fused stages (read per call)
     if ((int64_t)g->K * g->d <= 4096 && !no_wg) {
         // four rows per workgroup from 256 rows on (fewer: one row per workgroup keeps more of the chip busy), while the LDS image fits
         const bool r4 = n >= 256 && (int64_t)g->K * g->d <= 1536;
@@ -151,6 +148,7 @@ void launch(hg_gauss* g, const void* x, int x_dtype, int64_t n, int64_t ldx, dou
         const size_t lds = (size_t)R * (64 + g->K * g->d) * 8;
         const unsigned grid = (unsigned)((n + R - 1) / R);
         const hg::GaussParams G = hg::gauss_params(g);
+        if (debug) fprintf(stderr, "[gauss] form wg R %d grid %ux1 lds %zu classes %d features %d rows %lld\n", R, grid, lds, g->K, g->d, (long long)n);
 #define HG_GAUSS_WG(TT, RR) hipLaunchKernelGGL((k_gauss_regression_wg<TT, RR>), grid, 256, lds, st, (const TT*)x, ldx, n, G, reg, sd)
         if (x_dtype == HG_F32) {
             if (r4) HG_GAUSS_WG(float, 4);
@@ -163,6 +161,7 @@ void launch(hg_gauss* g, const void* x, int x_dtype, int64_t n, int64_t ldx, dou
         HG_HIP(hipGetLastError());
         return;
     }
+    if (debug) fprintf(stderr, "[gauss] form wave R 1 grid %ux1 lds %zu classes %d features %d rows %lld\n", (unsigned)n, sizeof(double) * 64, g->K, g->d, (long long)n);
     if (x_dtype == HG_F32)
         hipLaunchKernelGGL(k_gauss_regression<float>, (unsigned)n, 64, 0, st, (const float*)x, ldx, n, g->K, g->d,
                            (const double*)g->means.p, (const double*)g->inv_covs.p, (const double*)g->logw.p,
@@ -192,6 +191,11 @@ int hg_gauss_create(int32_t n_classes, int32_t dim, const double* means, const d
         if (!means || !inv_covs || !sqrt_det_covs || !priors || !avg_labels) hg::fail(HG_ERR_ARG, "null parameter array");
         if (n_classes < 1 || n_classes > kMaxClasses) hg::fail(HG_ERR_ARG, "n_classes must be 1..%d", kMaxClasses);
         if (dim < 1 || dim > 64) hg::fail(HG_ERR_ARG, "dim must be 1..64");
+        std::vector<double> lw(n_classes);      // every argument check comes before the device is looked for
+        for (int c = 0; c < n_classes; ++c) {
+            if (!(sqrt_det_covs[c] > 0) || !(priors[c] >= 0)) hg::fail(HG_ERR_ARG, "class %d: non-positive sqrt-det or negative prior", c);
+            lw[c] = std::log(priors[c]) - std::log(sqrt_det_covs[c]);
+        }
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
             hg::fail(HG_ERR_DEVICE, "no HIP device available (this library has no CPU execution path)");
@@ -201,11 +205,6 @@ int hg_gauss_create(int32_t n_classes, int32_t dim, const double* means, const d
         g->K = n_classes;
         g->d = dim;
         g->device = device;
-        std::vector<double> lw(n_classes);
-        for (int c = 0; c < n_classes; ++c) {
-            if (!(sqrt_det_covs[c] > 0) || !(priors[c] >= 0)) hg::fail(HG_ERR_ARG, "class %d: non-positive sqrt-det or negative prior", c);
-            lw[c] = std::log(priors[c]) - std::log(sqrt_det_covs[c]);
-        }
         g->means.upload(means, sizeof(double) * n_classes * dim);
         g->inv_covs.upload(inv_covs, sizeof(double) * n_classes * dim * dim);
         g->logw.upload(lw.data(), sizeof(double) * n_classes);
@@ -271,6 +270,8 @@ int hg_gauss_regression_multi_device(hg_gauss* const* gs, int m, const void* x, 
         const size_t lds = (size_t)R * (64 + kd_max) * 8;
         const dim3 grid((unsigned)((n + R - 1) / R), (unsigned)m);
         hipStream_t st = (hipStream_t)stream;
+        if (getenv("HIGSFA_DEBUG") != nullptr)
+            fprintf(stderr, "[gauss] form multi R %d grid %ux%u lds %zu classifiers %d rows %lld\n", R, grid.x, grid.y, lds, m, (long long)n);
         if (x_dtype == HG_F32) {
             if (r4) hipLaunchKernelGGL((k_gauss_regression_wg_multi<float, 4>), grid, dim3(256), lds, st, (const float*)x, ldx, n, M, out_reg, out_stride);
             else hipLaunchKernelGGL((k_gauss_regression_wg_multi<float, 1>), grid, dim3(256), lds, st, (const float*)x, ldx, n, M, out_reg, out_stride);

@@ -17,7 +17,25 @@ struct GaussParams {
     const double *means = nullptr, *inv_covs = nullptr, *logw = nullptr, *avg = nullptr;
 };
 
-// The regression with the quadratic forms spread over a workgroup (round 4).  In the one-wave form (hg_gauss.hip), lane c walks the d x d matrix of its
+// std(x) = sqrt(sum_c post_c (avg_c - reg)^2) by a second pass over a wave's log-weights, for both kernel forms (wave-uniform: every
+// lane of the wave calls it, with reg and sw as the butterflies left them).  The one-pass form sqrt(sum w a^2 / sw - reg^2) cancels:
+// off by 2.2e-7 on the shipped age classifier, exactly 0 for small true values, 1e-3 of the label spread for labels near 1e6.
+__device__ __forceinline__ void out_std_two_pass(const double (&lp)[kGaussMaxClasses / 64], double lmax, int lane, int K, const double* __restrict__ avg,
+                                                 double reg, double sw, double* __restrict__ out) {
+    double sv = 0;
+#pragma unroll
+    for (int s = 0; s < kGaussMaxClasses / 64; ++s) {
+        const int c = lane + 64 * s;
+        if (c < K) {
+            const double w = exp(lp[s] - lmax), e = avg[c] - reg;
+            sv += w * (e * e);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) sv += __shfl_xor(sv, o);
+    if (lane == 0) *out = sqrt(sv / sw);
+}
+
+// The regression with the quadratic forms spread over a workgroup (round 4). In the one-wave form (hg_gauss.hip), lane c walks the d x d matrix of its
 // class alone — 400 dependent steps for the pose regressors (50 classes, 20 features), with every lane of a load on another
 // cache line: 25-32 us for a call on a handful of rows, nine times per frame.  Here thread (c, i) of four waves computes
 // t_i = sum_j S_c[i][j] (x_j - m_c[j]) from one contiguous matrix row and leaves it in LDS; wave 0 then forms
@@ -80,7 +98,7 @@ __device__ __forceinline__ void gauss_rows_wg(const T* __restrict__ x, int64_t l
             lmax = fmax(lmax, v);
         }
         for (int o = 32; o > 0; o >>= 1) lmax = fmax(lmax, __shfl_xor(lmax, o));
-        double sw = 0, swa = 0, swa2 = 0;
+        double sw = 0, swa = 0;
 #pragma unroll
         for (int s = 0; s < kGaussMaxClasses / 64; ++s) {
             const int c = lane + 64 * s;
@@ -88,19 +106,15 @@ __device__ __forceinline__ void gauss_rows_wg(const T* __restrict__ x, int64_t l
                 const double w = exp(lp[s] - lmax), a = avg[c];
                 sw += w;
                 swa += w * a;
-                swa2 += w * a * a;
             }
         }
         for (int o = 32; o > 0; o >>= 1) {
             sw += __shfl_xor(sw, o);
             swa += __shfl_xor(swa, o);
-            swa2 += __shfl_xor(swa2, o);
         }
-        if (lane == 0) {
-            const double reg = swa / sw;
-            out_reg[row0 + rr] = reg;
-            if (out_std) out_std[row0 + rr] = sqrt(fmax(swa2 / sw - reg * reg, 0.0));
-        }
+        const double reg = swa / sw;      // every lane holds the sums after the butterflies
+        if (lane == 0) out_reg[row0 + rr] = reg;
+        if (out_std) out_std_two_pass(lp, lmax, lane, K, avg, reg, sw, out_std + row0 + rr);
     }
 }
 
