@@ -805,6 +805,36 @@ int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* fram
                                  const hg_norm_geom* geoms_host, int64_t n, double* out_dev, int64_t out_stride, float* patches_dev,
                                  float* features_dev, void* stream);
 
+/* --- Pose normalisation and estimation over a stack of same-size frames (the rows of hg_cascade_detect_faces_frames_device) ----------
+ * Every step of the chain above is independent per face, so each result below is DEFINED as what the single-frame entry returns for
+ * that face on its own frame, bit for bit (tests/test_estimate_frames_gpu.py).
+ *
+ * hg_patcher_normalize_device for n faces spread over a stack: face i is cut from frame face_frame_host[i] (host, int32, consumed before
+ * the call returns) of n_frames grey uint8 frames, all frame_h x frame_w with row stride ld, frame f starting frame_stride BYTES behind
+ * frame f - 1 — any value >= (frame_h - 1) ld + frame_w, not necessarily a multiple of ld, as for hg_patcher_extract_frames_device.
+ * The geoms are those of hg_normalize_geometry_host for the one frame size.  A pixel of the virtual crop is
+ * frames_dev[index * frame_stride + fy * ld + fx] inside that frame and 0 outside it, all offsets 64-bit.  A face whose index lies
+ * outside [0, n_frames) is treated like a refused face — an all-zero image, no address formed from the index — and is NOT an error.
+ * Staged and tap by tap as above (the same flags, the same bytes); the face records and the scratch are the patcher's, sized from the
+ * host geoms alone.  The single-frame entry runs its own kernel instantiations with the records it has always had.
+ * HG_ERR_ARG before the device is touched and without reading anything behind frames_dev / out_dev: everything the single-frame entry
+ * refuses, n_frames < 1 or > HG_MAX_STACK_FRAMES, frame_stride below the bound, a null face_frame_host with n > 0.  n == 0: HG_OK,
+ * nothing launched. */
+int hg_patcher_normalize_frames_device(hg_patcher* p, int flags, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                                       int frame_w, int64_t ld, const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n,
+                                       int out_w, int out_h, uint8_t* out_dev, int64_t ldo, void* stream);
+/* hg_estimator_estimate_device on the pooled faces of a stack: ONE normalise (the entry above) into the estimator's crop scratch, one
+ * patch step, one hg_flow_execute_device on n rows, the regressions on n rows, the finishing kernel.  out_dev, patches_dev,
+ * features_dev, flags, the scratch and the one-stream rule as there.  A face whose frame index lies outside [0, n_frames) has NaN in all
+ * four rows, as a refused face has; no other face's bits depend on it.  Refusals (HG_ERR_ARG, nothing launched; all but the fused
+ * kernel's pixel cap are decided without reading the handle): those of the entry above about the stack, the geoms and face_frame_host,
+ * out_stride < n, a null out_dev with n > 0, n above 2^20, bad flags.  n == 0: HG_OK, nothing launched.
+ * The prescaled grey stack these coordinates refer to is composed in Python (DeviceCascade.prescale_frames: the per-frame prescale
+ * into the slices of one tensor); there is no C entry for it. */
+int hg_estimator_estimate_frames_device(hg_estimator* e, int flags, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                                        int frame_w, int64_t ld, const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n,
+                                        double* out_dev, int64_t out_stride, float* patches_dev, float* features_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

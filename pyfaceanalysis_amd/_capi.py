@@ -29,6 +29,7 @@ _ENTRIES_SINCE_RESIZE = ("hg_frame_resize_host", "hg_patcher_resize_device", "hg
 _ENTRIES_SINCE_NORMALIZE = ("hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device")
 _ENTRIES_SINCE_ESTIMATION = ("hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device")
 _ENTRIES_SINCE_FRAME_STACKS = ("hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device")
+_ENTRIES_SINCE_ESTIMATE_FRAMES = ("hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device")
 _lib = None
 
 
@@ -170,6 +171,8 @@ def lib():
         "hg_estimator_free": (None, [vp]),
         "hg_estimator_patches_device": (C.c_int, [vp, i32, vp, i64, i64, vp, i64, vp]),
         "hg_estimator_estimate_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "hg_patcher_normalize_frames_device": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, i64, vp, vp, i64, i32, i32, vp, i64, vp]),
+        "hg_estimator_estimate_frames_device": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_gather_rows_device": (C.c_int, [i32, vp, vp, i64, vp, vp, i64, vp]),
@@ -212,7 +215,8 @@ def lib():
             # an A/B run on the library of an older commit (HIGSFA_LIB, tools/build_ref_lib.sh) may lack the newest entries, and only
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
-                        _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS +
+                        _ENTRIES_SINCE_ESTIMATE_FRAMES) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -242,6 +246,7 @@ EXPORTED_SYMBOLS = (
     "hg_normalize_geometry_host", "hg_normalize_faces_host", "hg_patcher_normalize_device",
     "hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device",
     "hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device",
+    "hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

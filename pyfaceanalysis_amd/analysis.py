@@ -204,8 +204,10 @@ class FaceAnalyzer(object):
             _capi.check(_capi.lib().hg_estimator_estimate_device(
                 self._handle(), int(flags), frame.data_ptr(), h, w, frame.stride(0) if h > 1 else w, g.ctypes.data_as(C.c_void_p), n, out.data_ptr(), n,
                 None if pt is None else pt.data_ptr(), None if ft is None else ft.data_ptr(), t.cuda.current_stream(frame.device).cuda_stream))
-        block = out.cpu().numpy()
-        status = g["status"].astype(np.int32)
+        return self._result(out.cpu().numpy(), g["status"].astype(np.int32), pt, ft)
+
+    def _result(self, block, status, pt, ft):
+        """The dict of ``estimate`` from the (4, n) host block, the status per face and the intermediates (device tensors or None)."""
         ok = status == 0
         res = dict(status=status)
         if self.age is not None:
@@ -218,9 +220,61 @@ class FaceAnalyzer(object):
             res[key + "_confidence"] = conf(v)
             names = iter(strings(v[ok]))
             res[key + "_label"] = [next(names) if o else None for o in ok]
-        if return_intermediates:
-            res["patches"], res["features"] = pt.cpu().numpy(), ft.cpu().numpy()
+        if pt is not None:
+            res["patches"], res["features"] = (a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in (pt, ft))
         return res
+
+    def estimate_frames(self, stack, eyes=None, face_frame=None, geoms=None, return_intermediates=False, flags=0):
+        """``estimate`` for faces spread over a stack of B same-size frames as ONE pooled chain (hg_estimator_estimate_frames_device: one
+        normalise, one patch step, one network call and the regressions on all n rows).  ``stack``: a (B, H, W) grey uint8 device tensor
+        (``normalize.check_grey_stack``) — for the rows of ``detect_faces_frames`` the prescaled stack the cascade read,
+        ``DeviceCascade.prescale_frames(stack)``; ``eyes`` (n, 4) in each face's own frame (or ``geoms``); ``face_frame`` (n,) integers,
+        the frame of every face, in any order.  Returns the dict of ``estimate`` over all n faces — face i's values are, bit for bit,
+        those of ``estimate(stack[face_frame[i]], eyes[i:i + 1])`` — with one device-to-host copy of the (4, n) block, the call's only
+        wait.  A face whose frame index is outside [0, B) has status ``normalize.STATUS_FRAME_RANGE``, NaN values and ``None`` labels, like
+        a refused face.  An empty stack or n = 0 touches no library entry."""
+        import torch as t
+        stack = _normalize.check_grey_stack(t, stack, None, "estimate_frames")      # layout first, then the faces, then the device
+        if geoms is not None:
+            g = _normalize._check_geoms(geoms)
+        else:
+            e = _normalize._eyes(eyes)
+            g = (self._norm.geometry(e, (int(stack.shape[2]), int(stack.shape[1]))) if stack is not None and len(e)
+                 else np.zeros(len(e), dtype=_capi.NORM_GEOM_DTYPE))
+        n = int(g.shape[0])
+        ff = _normalize.check_face_frame(face_frame, n)
+        _normalize.check_stack_device(stack, self.device, "estimate_frames")
+        b = 0 if stack is None else int(stack.shape[0])
+        status = np.where((ff < 0) | (ff >= b), _normalize.STATUS_FRAME_RANGE, g["status"]).astype(np.int32)
+        npix = self.patch_size[0] * self.patch_size[1]
+        if n == 0 or b == 0:
+            inter = (np.zeros((n, npix), dtype=np.float32), np.zeros((n, self.k), dtype=np.float32)) if return_intermediates else (None, None)
+            return self._result(np.full((4, n), np.nan), status, *inter)
+        out = t.empty((4, n), dtype=t.float64, device=stack.device)
+        pt = t.empty((n, npix), dtype=t.float32, device=stack.device) if return_intermediates else None
+        ft = t.empty((n, self.k), dtype=t.float32, device=stack.device) if return_intermediates else None
+        b, h, w, ld, stride = _normalize.stack_layout(stack)
+        _capi.check(_capi.lib().hg_estimator_estimate_frames_device(
+            self._handle(), int(flags), stack.data_ptr(), b, stride, h, w, ld, g.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), n, out.data_ptr(), n,
+            None if pt is None else pt.data_ptr(), None if ft is None else ft.data_ptr(), t.cuda.current_stream(stack.device).cuda_stream))
+        return self._result(out.cpu().numpy(), status, pt, ft)
+
+    def estimate_faces_frames(self, stack, faces, **kw):
+        """The list of B (m_b, 10) arrays ``DeviceCascade.detect_faces_frames`` returns, on the stack the cascade read
+        (``DeviceCascade.prescale_frames(stack)``), through ONE ``estimate_frames``.  Returns a list of B dicts, each, key for key, what
+        ``estimate_faces(stack[b], faces[b])`` returns; a frame without faces gets the dict of ``estimate`` with n = 0.  A list whose
+        length is not B raises ValueError."""
+        import torch as t
+        stack = _normalize.check_grey_stack(t, stack, None, "estimate_faces_frames")
+        b = 0 if stack is None else int(stack.shape[0])
+        if isinstance(faces, np.ndarray) or not hasattr(faces, "__len__") or len(faces) != b:
+            raise ValueError("faces must be the list of %d (m, 10) arrays detect_faces_frames returns, one per frame" % b)
+        rows = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in faces]
+        first = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        eyes = np.concatenate([r[:, 5:9] for r in rows]) if rows else np.zeros((0, 4))
+        face_frame = np.repeat(np.arange(b, dtype=np.int32), [len(r) for r in rows]) if rows else np.zeros(0, dtype=np.int32)
+        res = self.estimate_frames([] if stack is None else stack, eyes, face_frame, **kw)
+        return [{k: v[int(first[f]):int(first[f + 1])] for k, v in res.items()} for f in range(b)]
 
     def estimate_faces(self, frame, faces, **kw):
         """The (n, 10) rows of ``detect_faces`` / ``FaceTracker`` (x0, y0, x1, y1, angle, eyeL_x, eyeL_y, eyeR_x, eyeR_y, confidence) on

@@ -214,6 +214,11 @@ class DeviceCascade(object):
             self._prescale[key] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
                                    t.empty((ph, pw), dtype=t.uint8, device=self.dev))
         whole, small = self._prescale[key]
+        return self._shrink_into(frame, fw, fh, pw, ph, whole, small, stream)
+
+    def _shrink_into(self, frame, fw, fh, pw, ph, whole, small, stream):
+        """The shrinking part of ``prescale``: ``frame`` (fw x fh, checked) -> ``small``, a dense (ph, pw) grey uint8 tensor, by the configured
+        filter; ``whole``: the box of the whole frame on the device."""
         if self.prescale_filter != _capi.HG_RESAMPLE_NEAREST:      # PIL's antialiased resize of the grey frame (frames.resize)
             return frames.resize(frame, (pw, ph), self.prescale_filter, self.frame_format, out=small, patcher=self.patcher)
         if self.frame_format == _capi.HG_FRAME_L:
@@ -223,6 +228,37 @@ class DeviceCascade(object):
             _capi.check(_capi.lib().hg_patcher_extract_format_device(
                 self.patcher._handle(), self.frame_format, frame.data_ptr(), fh, fw, frame.stride(0), whole.data_ptr(), 1, pw, ph, small.data_ptr(),
                 _capi.HG_U8, pw * ph, stream))
+        return small
+
+    def prescale_frames(self, stack, prescale_size=grid.PRESCALE_SIZE):
+        """``prescale`` for a stack of B same-size frames (``_check_stack``): the (B, ph, pw) grey uint8 stack the rows of
+        ``detect_frames`` / ``detect_faces_frames`` refer to — what ``normalize.FaceNormalizer.normalize_frames`` and
+        ``analysis.FaceAnalyzer.estimate_faces_frames`` take beside those rows.  Composed here from the per-frame calls: frame f is
+        written by the code ``prescale(stack[f])`` runs (the configured filter, grey and colour formats) into slice f of one tensor, so
+        its bytes are that call's; B launches, no host wait.  A grey stack that needs no shrinking is returned as it is.  Otherwise the
+        tensor is cascade-owned per (B, frame size, prescaled size), with ``prescale``'s lifetime rule: valid until the next
+        ``prescale_frames`` with the same key, which writes into it again.  An empty stack returns an empty (0, 0, 0) tensor without
+        touching the library."""
+        t = self.torch
+        stack = self._check_stack(stack)
+        if stack is None:
+            return t.empty((0, 0, 0), dtype=t.uint8)
+        b, fh, fw = int(stack.shape[0]), int(stack.shape[1]), int(stack.shape[2])
+        pw, ph = grid.prescaled_size(fw, fh, prescale_size)
+        grey = self.frame_format == _capi.HG_FRAME_L
+        if (pw, ph) == (fw, fh) and grey:
+            return stack
+        key = ("stack", b, fw, fh, pw, ph)
+        if key not in self._prescale:
+            self._prescale[key] = (t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev),
+                                   t.empty((b, ph, pw), dtype=t.uint8, device=self.dev))
+        whole, small = self._prescale[key]
+        stream = t.cuda.current_stream(self.dev).cuda_stream
+        for f in range(b):
+            if (pw, ph) == (fw, fh):
+                frames.to_gray(stack[f], self.frame_format, out=small[f])
+            else:
+                self._shrink_into(stack[f], fw, fh, pw, ph, whole, small[f], stream)
         return small
 
     def detect(self, frame, smallest_face=0.2, windows=None):

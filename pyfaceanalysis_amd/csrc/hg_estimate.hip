@@ -25,6 +25,7 @@
 
 #include "hg_common.hpp"
 #include "hg_gauss_dev.hpp"
+#include "hg_normalize.hpp"
 
 #ifndef HG_EST_THREADS
 #define HG_EST_THREADS 1024
@@ -361,24 +362,26 @@ int hg_estimator_patches_device(hg_estimator* e, int flags, const uint8_t* crops
     });
 }
 
-int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* frame_dev, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms_host,
-                                 int64_t n, double* out_dev, int64_t out_stride, float* patches_dev, float* features_dev, void* stream) {
-    return guarded([&] {
-        if (!e) hg::fail(HG_ERR_ARG, "null estimator handle");
-        const bool fused = use_fused(e, flags, n);
-        if (n < 0 || n > kMaxFaces) hg::fail(HG_ERR_ARG, "bad face count");
-        if (frame_h <= 0 || frame_w <= 0 || ld < frame_w) hg::fail(HG_ERR_ARG, "bad frame shape");
-        if (out_stride < n) hg::fail(HG_ERR_ARG, "output rows %lld apart hold %lld faces", (long long)out_stride, (long long)n);
-        if (n > 0 && (!frame_dev || !geoms_host || !out_dev)) hg::fail(HG_ERR_ARG, "null data pointer");
-        if (n == 0) return;
+}  // extern "C"
+
+namespace {
+
+// The chain of both estimate entries behind their argument checks, n > 0.  frames_dev / n_frames / frame_stride / face_frame_host: the
+// stack's (face_frame_host == nullptr: the single frame at frames_dev).  A face whose frame index lies outside the stack counts as refused.
+void run_estimate(hg_estimator* e, bool fused, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                  const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n, double* out_dev, int64_t out_stride, float* patches_dev,
+                  float* features_dev, void* stream) {
         set_dev(e->device);
         hipStream_t st = (hipStream_t)stream;
         const hg_estimator_consts& c = e->c;
         e->reserve(n, st);
         // 1. the crops (a refused face: all zero)
         const int64_t crop_bytes = (int64_t)c.crop_w * c.crop_h;
-        if (hg_patcher_normalize_device(e->patcher, 0, frame_dev, frame_h, frame_w, ld, geoms_host, n, c.crop_w, c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st) != HG_OK)
-            hg::fail(HG_ERR_ARG, "%s", hg_last_error());      // (its refusals are all argument errors; the message is its own)
+        const int rc = face_frame_host
+            ? hg_patcher_normalize_frames_device(e->patcher, 0, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n, c.crop_w,
+                                                 c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st)
+            : hg_patcher_normalize_device(e->patcher, 0, frames_dev, frame_h, frame_w, ld, geoms_host, n, c.crop_w, c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st);
+        if (rc != HG_OK) hg::fail(HG_ERR_ARG, "%s", hg_last_error());      // (its refusals are all argument errors; the message is its own)
         // the refused flags, through the ring
         hg_estimator::Slot& slot = e->slot[e->next];
         e->next = (e->next + 1) % kSlots;
@@ -395,7 +398,8 @@ int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* fram
             HG_HIP(hipHostMalloc((void**)&slot.host, cap, hipHostMallocDefault));
             slot.cap = cap;
         }
-        for (int64_t i = 0; i < n; ++i) slot.host[i] = geoms_host[i].status != 0 ? 1 : 0;
+        for (int64_t i = 0; i < n; ++i)
+            slot.host[i] = (geoms_host[i].status != 0 || (face_frame_host && (face_frame_host[i] < 0 || face_frame_host[i] >= n_frames))) ? 1 : 0;
         HG_HIP(hipMemcpyAsync(e->refused.p, slot.host, (size_t)n, hipMemcpyHostToDevice, st));
         HG_HIP(hipEventRecord(slot.copied, st));
         slot.pending = true;
@@ -421,6 +425,42 @@ int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* fram
         hipLaunchKernelGGL(k_estimate_finish, (unsigned)((n + 255) / 256), 256, 0, st, n, (const uint8_t*)e->refused.p, out_dev, out_stride, e->age ? 1 : 0, e->race ? 1 : 0,
                            e->gender ? 1 : 0);
         HG_HIP(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int hg_estimator_estimate_device(hg_estimator* e, int flags, const uint8_t* frame_dev, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms_host,
+                                 int64_t n, double* out_dev, int64_t out_stride, float* patches_dev, float* features_dev, void* stream) {
+    return guarded([&] {
+        if (!e) hg::fail(HG_ERR_ARG, "null estimator handle");
+        const bool fused = use_fused(e, flags, n);
+        if (n < 0 || n > kMaxFaces) hg::fail(HG_ERR_ARG, "bad face count");
+        if (frame_h <= 0 || frame_w <= 0 || ld < frame_w) hg::fail(HG_ERR_ARG, "bad frame shape");
+        if (out_stride < n) hg::fail(HG_ERR_ARG, "output rows %lld apart hold %lld faces", (long long)out_stride, (long long)n);
+        if (n > 0 && (!frame_dev || !geoms_host || !out_dev)) hg::fail(HG_ERR_ARG, "null data pointer");
+        if (n == 0) return;
+        run_estimate(e, fused, frame_dev, 1, 0, frame_h, frame_w, ld, geoms_host, nullptr, n, out_dev, out_stride, patches_dev, features_dev, stream);
+    });
+}
+
+int hg_estimator_estimate_frames_device(hg_estimator* e, int flags, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
+                                        int64_t ld, const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n, double* out_dev,
+                                        int64_t out_stride, float* patches_dev, float* features_dev, void* stream) {
+    return guarded([&] {
+        // what a host can tell comes first and reads nothing behind the handle: a zeroed block in its place is refused, or told HG_OK at n == 0, like a live one
+        if (!e) hg::fail(HG_ERR_ARG, "null estimator handle");
+        if ((flags & ~3) || flags == 3) hg::fail(HG_ERR_ARG, "estimator: bad flags %d (1: composed patch path, 2: fused patch kernel)", flags);
+        if (n > kMaxFaces) hg::fail(HG_ERR_ARG, "bad face count");
+        if (const char* why = hg::normalize_stack_check(frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n))
+            hg::fail(HG_ERR_ARG, "%s", why);
+        if (out_stride < n) hg::fail(HG_ERR_ARG, "output rows %lld apart hold %lld faces", (long long)out_stride, (long long)n);
+        if (n > 0 && !out_dev) hg::fail(HG_ERR_ARG, "null data pointer");
+        const bool fused = use_fused(e, flags, n);
+        if (n == 0) return;
+        run_estimate(e, fused, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n, out_dev, out_stride, patches_dev, features_dev,
+                     stream);
     });
 }
 

@@ -242,6 +242,43 @@ const char* normalize_check(const void* frame, int frame_h, int frame_w, int64_t
     return nullptr;
 }
 
+namespace {
+
+// the shape of a stack: n, the frame size and ld as normalize_check reads them, then the stack's own two numbers
+const char* stack_shape_check(int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, int64_t n) {
+    if (n < 0) return "normalize: n < 0";
+    if (frame_h <= 0 || frame_w <= 0 || frame_w > (1 << 24) || frame_h > (1 << 24)) return "normalize: bad frame size";
+    if (ld < frame_w) return "normalize: ld < frame_w";
+    if (n_frames < 1 || n_frames > HG_MAX_STACK_FRAMES) return "normalize: n_frames must be 1 .. HG_MAX_STACK_FRAMES";
+    // frame_stride >= (frame_h - 1) ld + frame_w, without forming the product (ld is any int64)
+    if (frame_stride < frame_w || (frame_h > 1 && (frame_stride - frame_w) / (frame_h - 1) < ld)) return "normalize: frame_stride < (frame_h - 1) ld + frame_w";
+    return nullptr;
+}
+
+const char* geoms_check(const hg_norm_geom* geoms, int64_t n, int frame_w, int frame_h) {
+    for (int64_t f = 0; f < n; ++f)
+        if (const char* why = geom_check(geoms[f], frame_w, frame_h)) return why;
+    return nullptr;
+}
+
+}  // namespace
+
+const char* normalize_stack_check(const void* frames, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms,
+                                  const int32_t* face_frame, int64_t n) {
+    if (const char* why = stack_shape_check(n_frames, frame_stride, frame_h, frame_w, ld, n)) return why;
+    if (n > 0 && (!frames || !geoms || !face_frame)) return "normalize: null data pointer";
+    return geoms_check(geoms, n, frame_w, frame_h);
+}
+
+const char* normalize_frames_check(const void* frames, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms,
+                                   const int32_t* face_frame, int64_t n, int out_w, int out_h, const void* out, int64_t ldo) {
+    if (const char* why = stack_shape_check(n_frames, frame_stride, frame_h, frame_w, ld, n)) return why;
+    if (out_w < 1 || out_h < 1 || out_w > 4096 || out_h > 4096) return "normalize: out_w / out_h must be 1 .. 4096";
+    if (ldo < (int64_t)out_w * out_h) return "normalize: ldo < out_w * out_h";
+    if (n > 0 && (!frames || !geoms || !face_frame || !out)) return "normalize: null data pointer";
+    return geoms_check(geoms, n, frame_w, frame_h);
+}
+
 const char* normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,
                                  uint8_t* out, int64_t ldo) {
     if (const char* why = normalize_check(frame, frame_h, frame_w, ld, geoms, n, out_w, out_h, out, ldo)) return why;

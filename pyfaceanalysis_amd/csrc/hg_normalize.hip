@@ -20,6 +20,8 @@
 // each, sixteen threads computing the same one), staged grows with the rectangle and has a thread per rotated pixel.  The bound stays
 // where it is: beyond it the scratch per face would no longer be bounded by the output's size, and a batch of such faces is 0.02 ms apart.
 // Every grid and scratch size comes from the host's geoms; no launch is sized by anything read on the device.
+// The faces of a STACK of same-size frames (hg_patcher_normalize_frames_device) run the same bodies: k_norm_rect_frames and
+// k_norm_cut<…, StackRef, StackFace>, each face reading its own frame; the single frame keeps k_norm_rect and k_norm_cut<…, FrameRef, NormFace>.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,10 +48,36 @@ struct NormFace {
 };
 
 struct FrameRef {
+    static constexpr bool kStack = false;
     const uint8_t* p;
     int64_t ld;
     int w, h;
 };
+
+// A STACK of same-size frames (hg_patcher_normalize_frames_device): the face record carries the index of its frame, the reference the
+// stack's frame_stride in bytes — any value >= (h - 1) ld + w, not necessarily a multiple of ld.  The kernels below are instantiated
+// once for (FrameRef, NormFace), the single frame with the records and the code it has always had, and once for (StackRef, StackFace).
+struct StackFace {
+    NormFace f;
+    int32_t frame, pad;
+};
+
+struct StackRef {
+    static constexpr bool kStack = true;
+    const uint8_t* p;              // frame 0
+    int64_t ld, frame_stride;
+    int w, h, n_frames;
+};
+
+__device__ __forceinline__ const NormFace& rec(const NormFace& f) { return f; }
+__device__ __forceinline__ const NormFace& rec(const StackFace& s) { return s.f; }
+__device__ __forceinline__ FrameRef frame_of(const FrameRef& fr, const NormFace&) { return fr; }
+// the face's own frame; p == nullptr for an index outside [0, n_frames): no address is formed from such an index (the host has made
+// such a face kModeZero already; the kernels do not rely on it)
+__device__ __forceinline__ FrameRef frame_of(const StackRef& sr, const StackFace& s) {
+    const bool in = s.frame >= 0 && s.frame < sr.n_frames;
+    return FrameRef{in ? sr.p + (int64_t)s.frame * sr.frame_stride : nullptr, sr.ld, sr.w, sr.h};
+}
 
 // pixel (xc, yc) of the virtual crop
 __device__ __forceinline__ double crop_px(const FrameRef& fr, const NormFace& f, int xc, int yc) {
@@ -76,10 +104,15 @@ __device__ __forceinline__ FiltEnt cut_entry(double lo, double hi, int n, int i,
 
 // Pass A: a thread per pixel of a staged face's rectangle; blockIdx.y walks the faces, blockIdx.x the rectangle in chunks of 256 pixels
 // (the grid covers the largest rectangle of the call: the workgroups beyond a smaller face's rectangle leave at once).
-__global__ void __launch_bounds__(256) k_norm_rect(FrameRef fr, const NormFace* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
+template <typename Ref, typename Face>
+__device__ __forceinline__ void norm_rect(const Ref& ref, const Face* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const NormFace f = faces[b];
+        const Face F = faces[b];
+        const NormFace& f = rec(F);
         if (f.mode != kModeStaged) continue;
+        const FrameRef fr = frame_of(ref, F);
+        if constexpr (Ref::kStack)
+            if (!fr.p) continue;
         const int64_t np = (int64_t)f.rw * f.rh;
         for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < np; idx += (int64_t)gridDim.x * 256) {
             const int py = (int)(idx / f.rw), px = (int)(idx - (int64_t)py * f.rw);
@@ -87,21 +120,31 @@ __global__ void __launch_bounds__(256) k_norm_rect(FrameRef fr, const NormFace* 
         }
     }
 }
+__global__ void __launch_bounds__(256) k_norm_rect(FrameRef fr, const NormFace* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
+    norm_rect(fr, faces, n, scratch);
+}
+__global__ void __launch_bounds__(256) k_norm_rect_frames(StackRef sr, const StackFace* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
+    norm_rect(sr, faces, n, scratch);
+}
 
 // Pass B: the EXTENT / BICUBIC cut, a 16 x 16 tile of output pixels per workgroup.  MODE kModeStaged also writes the all-zero image of
 // a refused face (kModeZero); MODE kModeTaps takes the faces left to it.  A face of the other mode costs a workgroup one record read.
 constexpr int kTile = 16;
-template <int MODE>
-__global__ void __launch_bounds__(256) k_norm_cut(FrameRef fr, const NormFace* __restrict__ faces, int64_t n, const uint8_t* __restrict__ scratch, int out_w,
+template <int MODE, typename Ref, typename Face>
+__global__ void __launch_bounds__(256) k_norm_cut(Ref ref, const Face* __restrict__ faces, int64_t n, const uint8_t* __restrict__ scratch, int out_w,
                                                   int out_h, uint8_t* __restrict__ out, int64_t ldo, int tiles_x) {
     const int tx = threadIdx.x & (kTile - 1), ty = threadIdx.x / kTile;
     const int ox = (int)(blockIdx.x % tiles_x) * kTile + tx, oy = (int)(blockIdx.x / tiles_x) * kTile + ty;
     if (ox >= out_w || oy >= out_h) return;
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
-        const NormFace f = faces[b];
+        const Face F = faces[b];
+        const NormFace& f = rec(F);
         if (MODE == kModeStaged ? f.mode == kModeTaps : f.mode != kModeTaps) continue;
+        const FrameRef fr = frame_of(ref, F);
+        bool zero = f.mode == kModeZero;
+        if constexpr (Ref::kStack) zero = zero || !fr.p;      // a face whose frame lies outside the stack: the all-zero image
         uint8_t v = 0;
-        if (f.mode != kModeZero) {
+        if (!zero) {
             const FiltEnt ex = cut_entry(f.box[0], f.box[2], out_w, ox, f.W), ey = cut_entry(f.box[1], f.box[3], out_h, oy, f.H);
             if (ex.i != kFiltOutside && ey.i != kFiltOutside) {
                 if constexpr (MODE == kModeStaged) {
@@ -127,8 +170,8 @@ __global__ void __launch_bounds__(256) k_norm_cut(FrameRef fr, const NormFace* _
 constexpr int kSlots = 4;
 struct NormState {
     struct Slot {
-        NormFace* host = nullptr;
-        size_t cap = 0;
+        void* host = nullptr;      // NormFace or StackFace records
+        size_t cap = 0;            // bytes
         hipEvent_t copied = nullptr;
         bool pending = false;
     } slot[kSlots];
@@ -171,6 +214,109 @@ namespace hg {
 void normalize_state_free(void* state) { delete (NormState*)state; }
 }  // namespace hg
 
+
+namespace {
+
+inline void set_frame(NormFace&, int32_t) {}
+inline void set_frame(StackFace& s, int32_t frame) { s.frame = frame; }
+inline NormFace& rec_host(NormFace& f) { return f; }
+inline NormFace& rec_host(StackFace& s) { return s.f; }
+
+// Both entries behind their argument checks, n > 0.  face_frame / n_frames: the stack's (nullptr / 0 for the single frame); a face whose
+// frame index lies outside [0, n_frames) is a refused face here already — kModeZero, no scratch, no part in any grid size.
+template <typename Ref, typename Face>
+void normalize_run(hg_patcher* p, int flags, const Ref& ref, const hg_norm_geom* geoms_host, const int32_t* face_frame, int n_frames, int64_t n, int out_w, int out_h,
+                   uint8_t* out_dev, int64_t ldo, void* stream) {
+    if (n > (1 << 24)) hg::fail(HG_ERR_ARG, "normalize: more than 2^24 faces in one call");
+    auto live = [&](int64_t i) {
+        const hg_norm_geom& g = geoms_host[i];
+        return g.status == 0 && g.rect[2] > 0 && (!face_frame || (face_frame[i] >= 0 && face_frame[i] < n_frames));
+    };
+    // the path of every face and the scratch it needs, from the geoms alone
+    const int64_t limit = hg::normalize_stage_limit(out_w, out_h);
+    int64_t scratch_bytes = 0, max_rect = 0, n_taps = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!live(i)) continue;
+        const hg_norm_geom& g = geoms_host[i];
+        const int64_t np = (int64_t)g.rect[2] * g.rect[3];
+        const bool staged = (flags & 1) ? true : (flags & 2) ? false : np <= limit;
+        if (!staged) {
+            ++n_taps;
+            continue;
+        }
+        if ((flags & 1) && np > kForcedStageLimit) hg::fail(HG_ERR_ARG, "normalize: forced staging of a rectangle of %lld pixels (at most 2^26)", (long long)np);
+        scratch_bytes += (np + 15) & ~(int64_t)15;
+        max_rect = std::max(max_rect, np);
+    }
+    HG_HIP(hipSetDevice(hg::patcher_device(p)));
+    hipStream_t st = (hipStream_t)stream;
+    NormState* S = state_of(p);
+    NormState::Slot& slot = S->slot[S->next];
+    S->next = (S->next + 1) % kSlots;
+    if (slot.pending) {
+        HG_HIP(hipEventSynchronize(slot.copied));      // the upload of four calls ago
+        slot.pending = false;
+    }
+    if (!slot.copied) HG_HIP(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
+    const size_t bytes = (size_t)n * sizeof(Face);
+    if (bytes > slot.cap) {
+        if (slot.host) HG_HIP(hipHostFree(slot.host));
+        slot.host = nullptr;
+        slot.cap = 0;
+        const size_t cap = std::max<size_t>((size_t)n, 64) * sizeof(Face);
+        HG_HIP(hipHostMalloc(&slot.host, cap, hipHostMallocDefault));
+        slot.cap = cap;
+    }
+    Face* host = (Face*)slot.host;
+    int64_t off = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const hg_norm_geom& g = geoms_host[i];
+        Face F{};
+        NormFace& f = rec_host(F);
+        if (live(i)) {
+            for (int k = 0; k < 6; ++k) f.m[k] = g.m[k];
+            for (int k = 0; k < 4; ++k) f.box[k] = g.box[k];
+            f.crop_x0 = g.crop_x0; f.crop_y0 = g.crop_y0; f.W = g.W; f.H = g.H;
+            f.rotated = g.rotated ? 1 : 0;
+            f.rx0 = g.rect[0]; f.ry0 = g.rect[1]; f.rw = g.rect[2]; f.rh = g.rect[3];
+            const int64_t np = (int64_t)f.rw * f.rh;
+            const bool staged = (flags & 1) ? true : (flags & 2) ? false : np <= limit;
+            f.mode = staged ? kModeStaged : kModeTaps;
+            if (staged) {
+                f.scratch_off = off;
+                off += (np + 15) & ~(int64_t)15;
+            }
+            if (face_frame) set_frame(F, face_frame[i]);
+        } else if (face_frame) {
+            set_frame(F, -1);
+        }      // kModeZero — a refused face, one none of whose output pixels is inside rot, or one whose frame is outside the stack
+        host[i] = F;
+    }
+    if (S->faces.p && bytes > S->faces.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
+    S->faces.alloc(std::max<size_t>((size_t)n, 64) * sizeof(Face));
+    if (S->scratch.p && (size_t)scratch_bytes > S->scratch.bytes) HG_HIP(hipStreamSynchronize(st));
+    S->scratch.alloc((size_t)scratch_bytes);
+    HG_HIP(hipMemcpyAsync(S->faces.p, host, bytes, hipMemcpyHostToDevice, st));
+    HG_HIP(hipEventRecord(slot.copied, st));
+    slot.pending = true;
+    const Face* faces = (const Face*)S->faces.p;
+    const unsigned ny = (unsigned)std::min<int64_t>(n, 65535);
+    if (max_rect > 0) {
+        const dim3 grid((unsigned)((max_rect + 255) / 256), ny);      // <= 2^20 chunks (16 * 4096 * 4096 pixels; forced: kForcedStageLimit)
+        if constexpr (Ref::kStack) hipLaunchKernelGGL(k_norm_rect_frames, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
+        else hipLaunchKernelGGL(k_norm_rect, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
+    }
+    const int tiles_x = (out_w + kTile - 1) / kTile, tiles_y = (out_h + kTile - 1) / kTile;      // <= 256 each
+    const dim3 grid((unsigned)(tiles_x * tiles_y), ny);
+    if (n_taps < n)
+        hipLaunchKernelGGL((k_norm_cut<kModeStaged, Ref, Face>), grid, 256, 0, st, ref, faces, n, (const uint8_t*)S->scratch.p, out_w, out_h, out_dev, ldo, tiles_x);
+    if (n_taps > 0)
+        hipLaunchKernelGGL((k_norm_cut<kModeTaps, Ref, Face>), grid, 256, 0, st, ref, faces, n, (const uint8_t*)nullptr, out_w, out_h, out_dev, ldo, tiles_x);
+    HG_HIP(hipGetLastError());
+}
+
+}  // namespace
+
 extern "C" {
 
 int hg_patcher_normalize_device(hg_patcher* p, int flags, const uint8_t* frame_dev, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms_host,
@@ -180,82 +326,21 @@ int hg_patcher_normalize_device(hg_patcher* p, int flags, const uint8_t* frame_d
         if ((flags & ~3) || flags == 3) hg::fail(HG_ERR_ARG, "normalize: bad flags %d (1: staged, 2: tap by tap)", flags);
         if (const char* why = hg::normalize_check(frame_dev, frame_h, frame_w, ld, geoms_host, n, out_w, out_h, out_dev, ldo)) hg::fail(HG_ERR_ARG, "%s", why);
         if (n == 0) return;
-        if (n > (1 << 24)) hg::fail(HG_ERR_ARG, "normalize: more than 2^24 faces in one call");
-        // the path of every face and the scratch it needs, from the geoms alone
-        const int64_t limit = hg::normalize_stage_limit(out_w, out_h);
-        int64_t scratch_bytes = 0, max_rect = 0, n_taps = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const hg_norm_geom& g = geoms_host[i];
-            if (g.status != 0 || g.rect[2] == 0) continue;
-            const int64_t np = (int64_t)g.rect[2] * g.rect[3];
-            const bool staged = (flags & 1) ? true : (flags & 2) ? false : np <= limit;
-            if (!staged) {
-                ++n_taps;
-                continue;
-            }
-            if ((flags & 1) && np > kForcedStageLimit) hg::fail(HG_ERR_ARG, "normalize: forced staging of a rectangle of %lld pixels (at most 2^26)", (long long)np);
-            scratch_bytes += (np + 15) & ~(int64_t)15;
-            max_rect = std::max(max_rect, np);
-        }
-        HG_HIP(hipSetDevice(hg::patcher_device(p)));
-        hipStream_t st = (hipStream_t)stream;
-        NormState* S = state_of(p);
-        NormState::Slot& slot = S->slot[S->next];
-        S->next = (S->next + 1) % kSlots;
-        if (slot.pending) {
-            HG_HIP(hipEventSynchronize(slot.copied));      // the upload of four calls ago
-            slot.pending = false;
-        }
-        if (!slot.copied) HG_HIP(hipEventCreateWithFlags(&slot.copied, hipEventDisableTiming));
-        if ((size_t)n > slot.cap) {
-            if (slot.host) HG_HIP(hipHostFree(slot.host));
-            slot.host = nullptr;
-            slot.cap = 0;
-            const size_t cap = std::max<size_t>((size_t)n, 64);
-            HG_HIP(hipHostMalloc((void**)&slot.host, cap * sizeof(NormFace), hipHostMallocDefault));
-            slot.cap = cap;
-        }
-        int64_t off = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            const hg_norm_geom& g = geoms_host[i];
-            NormFace f{};
-            if (g.status == 0 && g.rect[2] > 0) {
-                for (int k = 0; k < 6; ++k) f.m[k] = g.m[k];
-                for (int k = 0; k < 4; ++k) f.box[k] = g.box[k];
-                f.crop_x0 = g.crop_x0; f.crop_y0 = g.crop_y0; f.W = g.W; f.H = g.H;
-                f.rotated = g.rotated ? 1 : 0;
-                f.rx0 = g.rect[0]; f.ry0 = g.rect[1]; f.rw = g.rect[2]; f.rh = g.rect[3];
-                const int64_t np = (int64_t)f.rw * f.rh;
-                const bool staged = (flags & 1) ? true : (flags & 2) ? false : np <= limit;
-                f.mode = staged ? kModeStaged : kModeTaps;
-                if (staged) {
-                    f.scratch_off = off;
-                    off += (np + 15) & ~(int64_t)15;
-                }
-            }      // else: kModeZero — a refused face, or one none of whose output pixels is inside rot
-            slot.host[i] = f;
-        }
-        if (S->faces.p && (size_t)n * sizeof(NormFace) > S->faces.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
-        S->faces.alloc(std::max<size_t>((size_t)n, 64) * sizeof(NormFace));
-        if (S->scratch.p && (size_t)scratch_bytes > S->scratch.bytes) HG_HIP(hipStreamSynchronize(st));
-        S->scratch.alloc((size_t)scratch_bytes);
-        HG_HIP(hipMemcpyAsync(S->faces.p, slot.host, (size_t)n * sizeof(NormFace), hipMemcpyHostToDevice, st));
-        HG_HIP(hipEventRecord(slot.copied, st));
-        slot.pending = true;
-        const FrameRef fr{frame_dev, ld, frame_w, frame_h};
-        const NormFace* faces = (const NormFace*)S->faces.p;
-        const unsigned ny = (unsigned)std::min<int64_t>(n, 65535);
-        if (max_rect > 0) {
-            const dim3 grid((unsigned)((max_rect + 255) / 256), ny);      // <= 2^20 chunks (16 * 4096 * 4096 pixels; forced: kForcedStageLimit)
-            hipLaunchKernelGGL(k_norm_rect, grid, 256, 0, st, fr, faces, n, (uint8_t*)S->scratch.p);
-        }
-        const int tiles_x = (out_w + kTile - 1) / kTile, tiles_y = (out_h + kTile - 1) / kTile;      // <= 256 each
-        const dim3 grid((unsigned)(tiles_x * tiles_y), ny);
-        if (n_taps < n)
-            hipLaunchKernelGGL((k_norm_cut<kModeStaged>), grid, 256, 0, st, fr, faces, n, (const uint8_t*)S->scratch.p, out_w, out_h, out_dev, ldo, tiles_x);
-        if (n_taps > 0)
-            hipLaunchKernelGGL((k_norm_cut<kModeTaps>), grid, 256, 0, st, fr, faces, n, (const uint8_t*)nullptr, out_w, out_h, out_dev, ldo, tiles_x);
-        HG_HIP(hipGetLastError());
+        normalize_run<FrameRef, NormFace>(p, flags, FrameRef{frame_dev, ld, frame_w, frame_h}, geoms_host, nullptr, 0, n, out_w, out_h, out_dev, ldo, stream);
+    });
+}
+
+int hg_patcher_normalize_frames_device(hg_patcher* p, int flags, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                                       const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n, int out_w, int out_h, uint8_t* out_dev, int64_t ldo,
+                                       void* stream) {
+    return guarded([&] {
+        if (!p) hg::fail(HG_ERR_ARG, "null patcher handle");
+        if ((flags & ~3) || flags == 3) hg::fail(HG_ERR_ARG, "normalize: bad flags %d (1: staged, 2: tap by tap)", flags);
+        if (const char* why = hg::normalize_frames_check(frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n, out_w, out_h, out_dev, ldo))
+            hg::fail(HG_ERR_ARG, "%s", why);
+        if (n == 0) return;
+        normalize_run<StackRef, StackFace>(p, flags, StackRef{frames_dev, ld, frame_stride, frame_w, frame_h, n_frames}, geoms_host, face_frame_host, n_frames, n, out_w,
+                                           out_h, out_dev, ldo, stream);
     });
 }
 

@@ -18,6 +18,15 @@ const char* normalize_geometry_host(const double* eyes, int64_t n, int frame_w, 
 const char* normalize_check(const void* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,
                             const void* out, int64_t ldo);
 
+// The same for the faces of a STACK of same-size frames (hg_patcher_normalize_frames_device, hg_estimator_estimate_frames_device): what
+// normalize_check refuses, n_frames outside 1 .. HG_MAX_STACK_FRAMES, a frame_stride below (frame_h - 1) ld + frame_w, a null face_frame
+// with n > 0.  Reads the geoms (host memory) and nothing behind frames / face_frame / out: an index outside the stack is no error.
+// normalize_stack_check is the part about the stack and the faces alone (the estimator has no caller's images).
+const char* normalize_stack_check(const void* frames, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms,
+                                  const int32_t* face_frame, int64_t n);
+const char* normalize_frames_check(const void* frames, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms,
+                                   const int32_t* face_frame, int64_t n, int out_w, int out_h, const void* out, int64_t ldo);
+
 // hg_normalize_faces_host
 const char* normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,
                                  uint8_t* out, int64_t ldo);

@@ -33,6 +33,10 @@ ROTATION_MODES = {"EyeLineRotation": True, "noRotation": False}
 # the two callers of the reference: (out_size, normalization_method), face_analysis.py:1172-1179 and :986-995
 PRESETS = {"age": ((256, 260), "eyes_inferred-mouth_areaZ"), "pose": ((256, 192), "eyes_inferred-mouth_area")}
 STATUS = {0: "ok", 1: "left eye right of the right eye", 2: "a coordinate is not finite", 3: "the eyes coincide", 4: "the centre is beyond 2^20"}
+# the stack calls' own status (``normalize_frames``, ``FaceAnalyzer.estimate_frames``): the face's frame index lies outside the stack.  It
+# is Python's: the geometry knows no frames, hg_norm_geom.status stays 0 for such a face and the library treats it like a refused one.
+STATUS_FRAME_RANGE = 5
+STATUS[STATUS_FRAME_RANGE] = "the frame index is outside the stack"
 
 
 def check_configuration(normalization_method="eyes_inferred-mouth_area", centering_mode="mid_eyes_inferred-mouth", rotation_mode="EyeLineRotation",
@@ -135,6 +139,72 @@ def approximate_eye_coords(boxes, angles=None):
     return np.stack([eye_left_x, eye_left_y, eye_right_x, eye_right_y], axis=1)
 
 
+def check_grey_stack(t, stack, device, what):
+    """A stack of same-size grey frames for ``what`` ("normalize_frames", "estimate_frames") as one tensor, or ValueError; None for an
+    empty stack.  The rules of ``DeviceCascade._check_stack`` for grey frames: (B, H, W) uint8, rows contiguous, ``stride(1) >= W`` (a
+    broadcast view is refused), ``stride(0) >= (H - 1) stride(1) + W`` — every second frame of a larger stack or crops of larger frames
+    are fine — at most ``HG_MAX_STACK_FRAMES`` frames; a list or tuple of same-shaped tensors is stacked.  Shape, dtype and strides are
+    checked before the device.  ``device``: the index the stack must live on."""
+    if isinstance(stack, (list, tuple)):
+        if len(stack) == 0:
+            return None
+        if any(not isinstance(f, t.Tensor) or f.shape != stack[0].shape or f.dtype != stack[0].dtype or f.device != stack[0].device for f in stack):
+            raise ValueError("a list of frames must hold tensors of one shape, dtype and device (frames of different sizes do not share a call)")
+        stack = t.stack(list(stack))
+    if not isinstance(stack, t.Tensor):
+        raise ValueError("%s takes a device tensor" % what)
+    if stack.dtype != t.uint8 or stack.dim() != 3:
+        raise ValueError("the stack must be (B, H, W) grey uint8 (a float stack is not offered; a colour stack goes through DeviceCascade.prescale_frames first)")
+    b, h, w = (int(v) for v in stack.shape)
+    if b == 0:
+        return None
+    if h == 0 or w == 0:
+        raise ValueError("a stack of empty frames")
+    if b > _capi.HG_MAX_STACK_FRAMES:
+        raise ValueError("%d frames in a stack, at most %d" % (b, _capi.HG_MAX_STACK_FRAMES))
+    if stack.stride(2) != 1:
+        raise ValueError("the frames of a stack must have contiguous rows, got strides %s" % (tuple(stack.stride()),))
+    if h > 1 and stack.stride(1) < w:
+        raise ValueError("rows %d bytes apart hold %d bytes: a broadcast or overlapping view is not a frame" % (stack.stride(1), w))
+    ld = stack.stride(1) if h > 1 else w
+    if b > 1 and stack.stride(0) < (h - 1) * ld + w:
+        raise ValueError("frames %d bytes apart reach over %d bytes: a broadcast or overlapping view is not a stack" % (stack.stride(0), (h - 1) * ld + w))
+    if device is not None:
+        check_stack_device(stack, device, what)
+    return stack
+
+
+def check_stack_device(stack, device, what):
+    """The last refusal before the library: the stack (None: an empty one) lives on device ``device``."""
+    if stack is None:
+        return
+    if not stack.is_cuda:
+        raise ValueError("%s takes a device tensor" % what)
+    if (stack.device.index or 0) != device:
+        raise ValueError("the stack is on %s, not on device %d" % (stack.device, device))
+
+
+def stack_layout(stack):
+    """(B, H, W, ld, frame_stride) of a checked stack, as the stack entries take them (bytes; one frame: the bound itself)."""
+    b, h, w = (int(v) for v in stack.shape)
+    ld = stack.stride(1) if h > 1 else w
+    return b, h, w, ld, (stack.stride(0) if b > 1 else (h - 1) * ld + w)
+
+
+def check_face_frame(face_frame, n):
+    """``face_frame`` as the (n,) int32 array the stack entries read: one frame index per face, an integer dtype.  An index the stack does
+    not hold is no error here (the face gets ``STATUS_FRAME_RANGE``); one beyond int32 becomes -1."""
+    if face_frame is None:
+        raise ValueError("face_frame is required: one frame index per face")
+    f = np.asarray(face_frame)
+    if f.size == 0:
+        f = f.astype(np.int64)
+    if f.dtype.kind not in "iu" or f.ndim != 1 or f.shape[0] != n:
+        raise ValueError("face_frame must be (n,) integers, one frame index per face (n = %d), got dtype %s, shape %s" % (n, f.dtype, f.shape))
+    f = (np.minimum(f, np.uint64(1 << 31)) if f.dtype == np.uint64 else f).astype(np.int64)
+    return np.ascontiguousarray(np.where((f < -(1 << 31)) | (f >= (1 << 31)), -1, f).astype(np.int32))
+
+
 class FaceNormalizer(object):
     """``normalize_image`` for the faces of one frame, on the device.  ``preset``: "age" — (256, 260), areaZ, the crops
     ``estimate_age_race_gender`` makes (face_analysis.py:1172-1179) — or "pose" — (256, 192), area, those of
@@ -189,6 +259,44 @@ class FaceNormalizer(object):
                 self._patcher._handle(), int(flags), frame.data_ptr(), h, w, frame.stride(0) if h > 1 else w, g.ctypes.data_as(C.c_void_p), n, ow, oh,
                 out.data_ptr(), out.stride(0) if n > 1 else ow * oh, t.cuda.current_stream(frame.device).cuda_stream))
         return out, g["status"].astype(np.int32)
+
+    def normalize_frames(self, stack, eyes=None, face_frame=None, geoms=None, out=None, flags=0):
+        """``normalize`` for faces spread over a stack of B same-size frames, ONE call (hg_patcher_normalize_frames_device): ``stack`` a
+        (B, H, W) grey uint8 device tensor (``check_grey_stack``; the prescaled stack the rows of ``detect_faces_frames`` refer to is
+        ``DeviceCascade.prescale_frames(stack)``), ``eyes`` (n, 4) in the coordinates of each face's own frame (or ``geoms`` from
+        ``geometry`` for the frame size), ``face_frame`` (n,) integers: the frame of every face, in any order.  Returns (images, status) as
+        ``normalize`` does; face i's image is, byte for byte, ``normalize(stack[face_frame[i]], eyes[i:i + 1])``'s.  A face whose frame
+        index is outside [0, B) gets an all-zero image and status ``STATUS_FRAME_RANGE``; it is no error.  An empty stack or n = 0
+        touches no library entry."""
+        import torch as t
+        dev = stack.device if isinstance(stack, t.Tensor) else t.device("cuda", self.device)      # (an empty stack's images live where it does)
+        stack = check_grey_stack(t, stack, None, "normalize_frames")      # layout first, then the faces, then the device
+        ow, oh = self.out_size
+        if geoms is not None:
+            g = _check_geoms(geoms)
+        else:
+            e = _eyes(eyes)
+            g = self.geometry(e, (int(stack.shape[2]), int(stack.shape[1]))) if stack is not None and len(e) else np.zeros(len(e), dtype=_capi.NORM_GEOM_DTYPE)
+        n = int(g.shape[0])
+        ff = check_face_frame(face_frame, n)
+        check_stack_device(stack, self.device, "normalize_frames")
+        b = 0 if stack is None else int(stack.shape[0])
+        status = np.where((ff < 0) | (ff >= b), STATUS_FRAME_RANGE, g["status"]).astype(np.int32)
+        if stack is not None:
+            dev = stack.device
+        if out is None:
+            out = t.empty((n, oh, ow), dtype=t.uint8, device=dev) if b else t.zeros((n, oh, ow), dtype=t.uint8, device=dev)
+        elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or out.device != dev or tuple(out.shape) != (n, oh, ow)
+              or (ow > 1 and out.stride(2) != 1) or (oh > 1 and out.stride(1) != ow) or (n > 1 and out.stride(0) < ow * oh)):
+            raise ValueError("out must be a (%d, %d, %d) uint8 tensor on %s whose images are contiguous" % (n, oh, ow, dev))
+        elif not b:
+            out.zero_()
+        if n and b:
+            b, h, w, ld, stride = stack_layout(stack)
+            _capi.check(_capi.lib().hg_patcher_normalize_frames_device(
+                self._patcher._handle(), int(flags), stack.data_ptr(), b, stride, h, w, ld, g.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), n,
+                ow, oh, out.data_ptr(), out.stride(0) if n > 1 else ow * oh, t.cuda.current_stream(stack.device).cuda_stream))
+        return out, status
 
     def close(self):
         """Frees the patcher it owns; the caller makes sure the device has finished with it (as for ``Patcher.close``)."""
