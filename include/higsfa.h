@@ -722,6 +722,59 @@ int hg_tracker_step_frame_multi_device(hg_tracker* t, const void* frame_dev, int
                                        int64_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, int* used_tracked_grid,
                                        int32_t* slots, int* n_held, void* stream);
 
+/* --- Tracking faces on a SET of frame streams in one pooled step ----------------------------------------------------------------
+ * hg_stream_tracker: n_streams trackers in one handle.  Stream s behaves exactly as an hg_tracker_create_multi(c, e, consts, max_faces,
+ * rescan_every) of its own that is fed frame s of every stack, step after step: the same boxes in the same carried order, the same
+ * path rule (FULL GRID when the stream holds nothing or, with rescan_every = R > 0, after R tracked steps in a row, counted per stream;
+ * TRACKED otherwise), the same hand-over rule, and a change of the prescaled size drops the boxes of EVERY stream.
+ * hg_stream_tracker_create: HG_ERR_ARG, the numbers before any handle is looked at, for n_streams outside 1..HG_MAX_STACK_FRAMES,
+ * max_faces outside 1..64, 9 n_streams max_faces above HG_MAX_STREAM_WINDOWS, rescan_every < 0; then as hg_tracker_create_multi.
+ *   HG_MAX_STREAM_WINDOWS = 8192: the tracked pass runs under a bound and relies on the filler rows the stage loop's single-workgroup
+ *   glue kernel writes between the live count and the bound; above 8192 candidates the stage loop takes its chunked two-launch glue,
+ *   which writes none.
+ * hg_stream_tracker_reset(t, s): stream s forgets its faces (its next step uses the full grid); s = -1: every stream.  HG_ERR_ARG for
+ * another s.  Synchronous.
+ * hg_stream_tracker_step_frames_device: one frame per stream.  The frame arguments are hg_cascade_detect_faces_frames_device's
+ * (frame 0, n_frames, frame_stride, frame_h, frame_w, ld in the cascade's frame format, the prescale size, the levels of the full
+ * grid, which are checked on every step).  With T = the streams on the tracked path and G = the others:
+ *   1. the tracked pass, enqueued whole: one kernel builds the nine windows of every held face of every stream of T from the state on
+ *      the device (hg_cascade_tracked_grid_streams_device is that kernel alone); the stage loop runs under the bound 9 * (faces held in
+ *      T), known on the host, every extraction cutting a row from its own stream's frame; the eye step runs on all survivors as one
+ *      batch (18 * ... rows), the purge per stream; a hand-over kernel, one workgroup per stream, writes the stream's carried boxes and
+ *      count into the state and its kept rows, counts and slots to pinned memory; a sequence word follows behind it.  No count is read
+ *      back.
+ *   2. the full-grid pass: what hg_cascade_detect_faces_frames_device runs on the frames of G (copied together unless they are all
+ *      the frames, one frame, or prescaled / converted anyway), then the hand-over of every stream's first rows.
+ *   3. the one wait of the tracked pass.
+ * A pass without streams launches nothing.  Outputs (host; all but stream_first nullable): out_rows, the kept rows ordered by stream,
+ * stream s's at stream_first[s] .. stream_first[s + 1] (n_streams + 1 entries); slots (out_cap entries), per row as
+ * hg_tracker_step_frame_multi_device's, relative to the stream's carried order, -1 on a full-grid step; per stream n_before_purge,
+ * used_tracked_grid (0 / 1) and n_held; *rows_executed, the rows of both passes (9 * faces held in T per network-owning stage, plus
+ * the full-grid pass's).  Per-stage survivor counts are not offered: the pooled passes do not have them per stream.
+ * HG_ERR_ARG before anything is launched or written — the numbers before the handle: n_frames outside 1..HG_MAX_STACK_FRAMES, a bad
+ * frame geometry, frame_stride below (frame_h - 1) ld + frame_w bytes-per-pixel, out_cap < 0; then a null handle or stream_first,
+ * n_frames != n_streams, and hg_cascade_detect_faces_frames_device's other refusals.  HG_ERR_ARG, writing no row and no slot
+ * (stream_first all 0), when out_cap is below the kept total: the hand-overs have happened by then and n_held is valid.  After any
+ * other failure every stream holds nothing.  One stream per handle, as above: a step must not run while another step of the set, or any
+ * call on its cascade or eye handle, is in flight.  Synchronous. */
+#define HG_MAX_STREAM_WINDOWS 8192
+typedef struct hg_stream_tracker hg_stream_tracker;
+int hg_stream_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int n_streams, int max_faces, int rescan_every,
+                             hg_stream_tracker** out);
+void hg_stream_tracker_free(hg_stream_tracker* t);
+int hg_stream_tracker_reset(hg_stream_tracker* t, int stream_index);
+int hg_stream_tracker_step_frames_device(hg_stream_tracker* t, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
+                                         int frame_w, int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels,
+                                         int n_levels, double* out_rows, int64_t out_cap, int32_t* stream_first, int32_t* n_before_purge,
+                                         int32_t* used_tracked_grid, int32_t* n_held, int32_t* slots, int64_t* rows_executed, void* stream);
+/* The grid kernel of the tracked pass alone, for inspection: faces_dev (n_streams, max_faces, 4) float64 and held_dev (n_streams) int32
+ * ON THE DEVICE -> boxes_dev (9 n_streams max_faces, 4) and level_dev (.., 3): window s * 9 max_faces + 9 j + i is window i of held
+ * face j < held[s] of stream s, the bits hg_cascade_tracked_grid_multi_device writes for that face; the rows of faces not held are
+ * not written.  A count outside 0..max_faces is read as the nearer end.  HG_ERR_ARG for n_streams outside 1..HG_MAX_STACK_FRAMES,
+ * max_faces outside 1..64, a null pointer, constants that are not positive and finite.  Enqueued on `stream`. */
+int hg_cascade_tracked_grid_streams_device(int device, const hg_tracked_consts* consts, const double* faces_dev, const int32_t* held_dev,
+                                           int n_streams, int max_faces, double* boxes_dev, double* level_dev, void* stream);
+
 /* --- SFA training step for one layer of nodes (BASELINE.json configs[4]) -----
  * Not on the reference's path (it never trains, face_analysis.py:451-479); restates
  * mdp.nodes.SFANode train/stop_training per node k over input columns conn[k*d .. (k+1)*d):

@@ -16,10 +16,11 @@ HG_FILTER_NEAREST, HG_FILTER_BILINEAR, HG_FILTER_BICUBIC = 0, 2, 3      # enum h
 HG_RESAMPLE_NEAREST, HG_RESAMPLE_LANCZOS, HG_RESAMPLE_BILINEAR, HG_RESAMPLE_BICUBIC, HG_RESAMPLE_BOX, HG_RESAMPLE_HAMMING = 0, 1, 2, 3, 4, 5
 HG_FRAME_L, HG_FRAME_RGB, HG_FRAME_BGR, HG_FRAME_RGBA, HG_FRAME_BGRA = 0, 1, 2, 3, 4      # frame formats (pyfaceanalysis_amd/frames.py)
 HG_MAX_STACK_FRAMES = 1024      # frames in one call of the stack entries (include/higsfa.h)
+HG_MAX_STREAM_WINDOWS = 8192    # 9 * n_streams * max_faces of a stream set (include/higsfa.h)
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks, the stream set
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
@@ -30,6 +31,8 @@ _ENTRIES_SINCE_NORMALIZE = ("hg_normalize_geometry_host", "hg_normalize_faces_ho
 _ENTRIES_SINCE_ESTIMATION = ("hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device")
 _ENTRIES_SINCE_FRAME_STACKS = ("hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device")
 _ENTRIES_SINCE_ESTIMATE_FRAMES = ("hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device")
+_ENTRIES_SINCE_STREAM_SET = ("hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
+                             "hg_cascade_tracked_grid_streams_device")
 _lib = None
 
 
@@ -204,6 +207,12 @@ def lib():
         "hg_tracker_create_multi": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), i32, i32, C.POINTER(vp)]),
         "hg_tracker_step_frame_multi_device": (C.c_int, [vp, vp, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, C.POINTER(i64),
                                                          C.POINTER(i64), vp, C.POINTER(i64), C.POINTER(C.c_int), vp, C.POINTER(C.c_int), vp]),
+        "hg_stream_tracker_create": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), i32, i32, i32, C.POINTER(vp)]),
+        "hg_stream_tracker_free": (None, [vp]),
+        "hg_stream_tracker_reset": (C.c_int, [vp, i32]),
+        "hg_stream_tracker_step_frames_device": (C.c_int, [vp, vp, i32, i64, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, vp, vp, vp, vp, vp,
+                                                           C.POINTER(i64), vp]),
+        "hg_cascade_tracked_grid_streams_device": (C.c_int, [i32, C.POINTER(HgTrackedConsts), vp, vp, i32, i32, vp, vp, vp]),
         "hg_sfa_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_pca_train_layer": (C.c_int, [vp, i32, i32, i64, i64, vp, C.c_int32, C.c_int32, i32, vp, vp, vp, vp]),
         "hg_train_apply_device": (C.c_int, [vp, i32, i64, i64, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, i64, i32]),
@@ -216,7 +225,7 @@ def lib():
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
                         _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS +
-                        _ENTRIES_SINCE_ESTIMATE_FRAMES) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_ESTIMATE_FRAMES + _ENTRIES_SINCE_STREAM_SET) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -247,6 +256,8 @@ EXPORTED_SYMBOLS = (
     "hg_estimator_create", "hg_estimator_free", "hg_estimator_patches_device", "hg_estimator_estimate_device",
     "hg_patcher_extract_frames_device", "hg_cascade_detect_frames_device", "hg_cascade_detect_faces_frames_device",
     "hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device",
+    "hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
+    "hg_cascade_tracked_grid_streams_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

@@ -30,6 +30,11 @@ void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** 
 void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const double* boxes,
                       const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n, double* out_rows, int64_t out_cap,
                       int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
+void eyes_frames_tail_bounded(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                              const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n_bound,
+                              const int32_t* n_dev, const double** purged, const int32_t** seg_first, const int32_t** seg_kept, const int32_t** row_src,
+                              const int32_t** kept_idx, hipStream_t st);
+void eyes_frames_buffers(const hg_eyes* e, int n_frames, const double** purged, const int32_t** seg_first, const int32_t** seg_kept);
 int eyes_device(const hg_eyes* e);
 }
 
@@ -379,6 +384,112 @@ __global__ void __launch_bounds__(128) k_tracker_handover(const double* __restri
         __threadfence_system();
         __hip_atomic_store(R.words + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+// ---- a SET of streams tracked in one pooled pass (hg_stream_tracker) ------------------------------------------------------------------
+// The start of the tracked pass: the nine windows of every held face of every stream, from the set's device state — faces
+// (n_streams, max_faces, 4) and held (n_streams) counts, clamped to 0 .. max_faces.  Original window o = s * 9 * max_faces + 9 j + i is
+// window i of held face j of stream s: orig_coords / orig_level are indexed by o with a fixed period per stream, so a row's stream is
+// o / (9 max_faces) wherever it travels — the divisor the stack machinery divides by already (FrameStack::n0, FrameSel::div,
+// k_eye_row_frames, k_frame_segments) — and its slot (o % (9 max_faces)) / 9.  The entries of faces not held are holes: never written,
+// never read.  The candidate arrays (coords .. oidx, nullable as everywhere) get the live rows COMPACTED, in order of o, with
+// oidx = o, and *count their number, 9 * sum of held: exactly the host's bound, no filler row at the first stage.  Every window comes
+// from tracked_window(): the bits k_cascade_init_tracked_multi writes for that face.  One workgroup of 1024 threads (n_streams <= 1024:
+// one thread per stream scans the counts; the windows are walked in steps of the workgroup's size).
+__global__ void __launch_bounds__(1024) k_cascade_init_tracked_streams(hg_tracked_consts t, const double* __restrict__ faces, const int32_t* __restrict__ held,
+                                                                       int n_streams, int max_faces, double* orig_coords, double* orig_level,
+                                                                       double* __restrict__ coords, double* __restrict__ angles, double* __restrict__ neg,
+                                                                       double* __restrict__ conf, int32_t* __restrict__ oidx, int32_t* __restrict__ count) {
+    __shared__ int first[1025];      // first[s]: held faces of the streams before s; first[n_streams]: all
+    __shared__ int wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int h = 0;
+    if (tid < n_streams) {
+        h = held[tid];
+        h = h < 0 ? 0 : (h > max_faces ? max_faces : h);
+    }
+    int incl = h;
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    if (tid < n_streams) first[tid] = off + incl - h;
+    if (tid == n_streams - 1) first[n_streams] = off + incl;
+    __syncthreads();
+    if (tid == 0 && count) *count = kTracked * first[n_streams];
+    const int per = kTracked * max_faces;
+    const int64_t n = (int64_t)per * n_streams;
+    for (int64_t o = tid; o < n; o += blockDim.x) {
+        const int s = (int)(o / per), r = (int)(o - (int64_t)s * per), j = r / kTracked, i = r - j * kTracked;
+        if (j >= first[s + 1] - first[s]) continue;
+        tracked_window(t, faces + ((size_t)s * max_faces + j) * 4, i, (int)o, orig_coords, orig_level, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (coords) {
+            const size_t p = (size_t)kTracked * (first[s] + j) + i;
+            for (int q = 0; q < 4; ++q) coords[p * 4 + q] = orig_coords[(size_t)o * 4 + q];
+            angles[p] = 0.0;
+            neg[p] = 0.0;
+            conf[p] = 0.0;
+            oidx[p] = (int32_t)o;
+        }
+    }
+}
+
+// The hand-over of a stream set, one workgroup per segment f of a per-frame purge (k_purge_frames / k_purge_frames_kept: segment f's kept
+// rows start at row seg_first[f] + f of `purged`, seg_kept[f] of them, from seg_first[f + 1] - seg_first[f] assembled rows).  The
+// segment belongs to stream stream_of[f] (null: f) and k_tracker_handover's rule runs on it: the first min(kept, max_faces) rows with
+// a finite box are carried, in order, into that stream's boxes of the state, their count beside them.  With R.words (the tracked pass)
+// everything the host needs goes to the stream's part of pinned memory: words {kept, before the purge, carried, 0}, the kept rows
+// (R.cap per stream) and a slot per kept row, kept row -> assembled row (S.kept_idx, relative to the segment) -> cascade survivor
+// (S.row_src) -> original window (S.oidx), whose position within its stream's period of `per` windows / 9 is the held face.
+// The sequence word is NOT written here: k_publish_seq behind this kernel, in stream order, publishes all workgroups' stores at once.
+__global__ void __launch_bounds__(128) k_stream_handover(const double* __restrict__ purged, const int32_t* __restrict__ seg_first,
+                                                         const int32_t* __restrict__ seg_kept, const int32_t* __restrict__ stream_of,
+                                                         double* __restrict__ boxes, int32_t* __restrict__ held, int max_faces, SlotChain S, int per,
+                                                         TrackerResults R) {
+    __shared__ int carried_s;
+    const int tid = threadIdx.x, f = blockIdx.x;
+    const int s = stream_of ? stream_of[f] : f;
+    const int lo = seg_first[f], kept = seg_kept[f], before = seg_first[f + 1] - lo;
+    const double* rows = purged + (size_t)(lo + f) * 10;
+    const int ncand = kept < max_faces ? kept : max_faces;
+    if (tid < 64) {      // the first wave: max_faces <= 64
+        bool ok = tid < ncand;
+        if (ok)
+            for (int q = 0; q < 4; ++q) ok = ok && isfinite(rows[(size_t)tid * 10 + q]);
+        const unsigned long long m = __ballot(ok ? 1 : 0);
+        if (ok) {
+            const int pos = __popcll(m & ((1ull << tid) - 1ull));
+            for (int q = 0; q < 4; ++q) boxes[((size_t)s * max_faces + pos) * 4 + q] = rows[(size_t)tid * 10 + q];
+        }
+        if (tid == 0) {
+            carried_s = __popcll(m);
+            held[s] = carried_s;
+        }
+    }
+    if (!R.words) return;
+    const int nrow = kept < R.cap ? kept : R.cap;
+    double* out = R.rows + (size_t)s * R.cap * 10;
+    int32_t* slots = R.slots + (size_t)s * R.cap;
+    for (int q = tid; q < nrow * 10; q += blockDim.x) out[q] = rows[q];
+    for (int j = tid; j < nrow; j += blockDim.x) slots[j] = (S.oidx[S.row_src[lo + S.kept_idx[lo + f + j]]] % per) / kTracked;
+    __syncthreads();
+    if (tid == 0) {
+        R.words[s * 4] = kept;
+        R.words[s * 4 + 1] = before;
+        R.words[s * 4 + 2] = carried_s;
+    }
+    __threadfence_system();
+}
+
+// One thread behind k_stream_handover in stream order: every workgroup's pinned stores are complete when this kernel starts; the
+// sequence number the host polls goes out last, at system scope (as k_tracker_handover's).
+__global__ void k_publish_seq(int32_t* word, int seq) {
+    __threadfence_system();
+    __hip_atomic_store(word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // A GROUP of stages (round 5): a stage that owns a network and the stages behind it whose network is None read the SAME sl
@@ -834,6 +945,11 @@ struct Bounded {
     int n_faces;
     hg_tracked_consts tc;
     const int32_t* final_count;      // out
+    // a SET of streams (hg_stream_tracker; n_streams = 0: the one stream above): the faces are (n_streams, max_faces, 4), held_dev holds
+    // n_streams counts, n_faces is their sum over the streams — the host's mirror — and the call comes with a FrameStack of n_streams
+    // frames whose n0 is the period 9 * max_faces of the original windows (k_cascade_init_tracked_streams)
+    const int32_t* held_dev = nullptr;
+    int n_streams = 0, max_faces = 0;
 };
 
 // A STACK of frames (`FS`, hg_cascade_detect_frames_device): frame_dev is frame 0 of n_frames grey frames of one size, `stride` bytes
@@ -862,8 +978,14 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
     // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
     if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
     // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
-    if (FS && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
-    if (B && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
+    const bool SB = B && B->n_streams > 0;      // the tracked pass of a stream set: Bounded and FrameStack together
+    if (FS && !SB && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
+    if (B && !SB && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
+    // the bound 9 * sum of held lies under the windows of the whole set, and those inside k_cascade_group's single-workgroup path (pad_to)
+    if (SB && (T || !FS || FS->n_frames != B->n_streams || B->max_faces < 1 || B->max_faces > kMaxFaces || FS->n0 != (int64_t)kTracked * B->max_faces ||
+               FS->n0 * FS->n_frames > 2 * kChunk || B->n_faces < 1 || n0 != (int64_t)kTracked * B->n_faces || n0 > FS->n0 * FS->n_frames || !B->face_dev ||
+               !B->held_dev))
+        hg::fail(HG_ERR_ARG, "bad tracked stream set");
     set_dev(c->device);
     hipStream_t st = (hipStream_t)stream;
     const int ns = (int)c->stages.size();
@@ -873,8 +995,12 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         for (int k = 0; k < ns && stage_counts; ++k) stage_counts[k] = 0;
         return;
     }
-    c->reserve(n0);
-    if (B) {
+    c->reserve(SB ? FS->n0 * FS->n_frames : n0);      // (a stream set: orig_coords / orig_level are indexed over the whole set's period)
+    if (SB) {
+        hipLaunchKernelGGL(k_cascade_init_tracked_streams, 1, 1024, 0, st, B->tc, B->face_dev, B->held_dev, B->n_streams, B->max_faces, (double*)c->orig_coords.p,
+                           (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p,
+                           (int32_t*)c->oidx[0].p, (int32_t*)c->count.p);
+    } else if (B) {
         hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)((n0 + 63) / 64), 64, 0, st, B->tc, B->face_dev, B->n_faces, (double*)c->orig_coords.p,
                            (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
                            (int32_t*)c->count.p);
@@ -1520,6 +1646,346 @@ int hg_tracker_step_frame_multi_device(hg_tracker* t, const void* frame_dev, int
     return guarded([&] {
         tracker_step(t, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_rows, out_cap, n_out, n_before_purge, stage_counts,
                      rows_executed, used_tracked_grid, slots, n_held, stream);
+    });
+}
+
+}  // extern "C"
+
+// ---- tracking faces on a SET of frame streams in one pooled step (include/higsfa.h) ----------------------------------------------------
+// Stream s behaves as an hg_tracker of its own fed frame s of every stack.  The streams that hold faces and are not due for a rescan
+// (T) share ONE tracked pass — k_cascade_init_tracked_streams, the bounded stage loop over a frame stack, the eye step as one batch, the
+// purge per stream, k_stream_handover — enqueued whole; the others (G) share one full-grid pass, what
+// hg_cascade_detect_faces_frames_device runs on their frames; the tracked pass's one wait comes last.
+struct hg_stream_tracker {
+    hg_cascade* c = nullptr;
+    hg_eyes* e = nullptr;
+    hg_tracked_consts tc{};
+    int n_streams = 0, max_faces = 1, rescan_every = 0;
+    hg::DevBuf state;                   // device: the held boxes (n_streams x max_faces x 4 doubles), then the carried counts (n_streams int32)
+    std::vector<int> held, run;         // per stream: host mirror of the carried count; consecutive tracked steps since the last full-grid step
+    int w = 0, h = 0;                   // prescaled frame size the boxes belong to
+    // pinned: the sequence word at 0; from 64 on the rows (n_streams x rows_cap x 10 doubles), the words (n_streams x {kept, before the
+    // purge, carried, 0}), the slots (n_streams x rows_cap) and the streams of the full-grid pass's segments (n_streams)
+    char* host_res = nullptr;
+    int32_t seq = 0;
+    int rows_cap() const { return kTracked * max_faces + 1; }      // the purge may keep n + 1 rows of a stream
+    double* box_dev() const { return (double*)state.p; }
+    int32_t* held_dev() const { return (int32_t*)((char*)state.p + (size_t)n_streams * max_faces * 32); }
+    double* res_rows() const { return (double*)(host_res + 64); }
+    int32_t* res_words() const { return (int32_t*)(host_res + 64 + (size_t)n_streams * rows_cap() * 80); }
+    int32_t* res_slots() const { return res_words() + (size_t)n_streams * 4; }
+    int32_t* res_gmap() const { return res_slots() + (size_t)n_streams * rows_cap(); }
+    size_t res_bytes() const { return 64 + (size_t)n_streams * rows_cap() * 84 + (size_t)n_streams * 20; }
+    void forget() {      // after a failed step: nothing is held anywhere (the device counts go to 0 in stream order, best effort)
+        std::fill(held.begin(), held.end(), 0);
+        std::fill(run.begin(), run.end(), 0);
+        w = h = 0;
+        if (state.p) (void)hipMemset(held_dev(), 0, (size_t)n_streams * 4);
+    }
+};
+
+namespace {
+// the numbers of a stream set, refused before any handle is looked at
+void check_stream_set(int n_streams, int max_faces, int rescan_every) {
+    if (n_streams < 1 || n_streams > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "n_streams %d outside 1..%d", n_streams, HG_MAX_STACK_FRAMES);
+    if (max_faces < 1 || max_faces > kMaxFaces) hg::fail(HG_ERR_ARG, "max_faces %d outside 1..%d", max_faces, kMaxFaces);
+    // the bounded stage loop pads its filler rows on k_cascade_group's single-workgroup path only (pad_to); above 2 * kChunk
+    // candidates detect_impl takes the two-launch chunk path, which has no padding
+    if ((int64_t)kTracked * n_streams * max_faces > HG_MAX_STREAM_WINDOWS)
+        hg::fail(HG_ERR_ARG, "%d streams of %d faces: %lld tracked windows, at most %d", n_streams, max_faces, (long long)kTracked * n_streams * max_faces,
+                 HG_MAX_STREAM_WINDOWS);
+    if (rescan_every < 0) hg::fail(HG_ERR_ARG, "negative rescan_every %d", rescan_every);
+}
+static_assert(HG_MAX_STREAM_WINDOWS == 2 * kChunk, "the stream set's window bound is k_cascade_group's single-workgroup path");
+
+void stream_tracker_step(hg_stream_tracker* t, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, int prescale_w,
+                         int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap, int32_t* stream_first,
+                         int32_t* n_before_purge, int32_t* used_tracked_grid, int32_t* n_held, int32_t* slots, int64_t* rows_executed, void* stream) {
+    const int Bn = t->n_streams, K = t->max_faces;
+    hg_cascade* c = t->c;
+    hg_eyes* e = t->e;
+    hipStream_t st = (hipStream_t)stream;
+    const LevelTable T = check_frame_stack(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_cap,
+                                           stream_first);
+    set_dev(c->device);
+    const bool pre = prescale_w > 0 || prescale_h > 0, conv = pre || c->frame_format != HG_FRAME_L;
+    const int oh = pre ? prescale_h : frame_h, ow = pre ? prescale_w : frame_w;
+    const size_t slot = (size_t)oh * ow;
+    // a change of the prescaled size drops every stream's boxes: they mean nothing on another size
+    if (ow != t->w || oh != t->h) {
+        bool any = false;
+        for (int s = 0; s < Bn; ++s) any = any || t->held[(size_t)s];
+        if (any) HG_HIP(hipMemsetAsync(t->held_dev(), 0, (size_t)Bn * 4, st));
+        std::fill(t->held.begin(), t->held.end(), 0);
+    }
+    t->w = ow;
+    t->h = oh;
+    // the path rule per stream, on the host: nothing held, or rescan_every tracked steps in a row behind it
+    std::vector<int> in_g((size_t)Bn), gs;      // gs: the streams of the full-grid pass, in order
+    int64_t held_sum = 0;
+    for (int s = 0; s < Bn; ++s) {
+        in_g[(size_t)s] = !t->held[(size_t)s] || (t->rescan_every > 0 && t->run[(size_t)s] >= t->rescan_every);
+        if (in_g[(size_t)s]) gs.push_back(s);
+        else held_sum += t->held[(size_t)s];
+    }
+    const int nG = (int)gs.size(), nT = Bn - nG;
+    // the grey frames both passes read.  The tracked pass cuts row i from frame (its stream), so stream s's frame is frame s of its stack;
+    // the full-grid pass reads a dense stack of ITS streams' frames.  Prescaled / converted: every frame goes through prescale_frame once,
+    // a tracked stream's into slot s, a full-grid stream's into slot n_streams + its position.  Grey frames as they are: read in place,
+    // and the full-grid pass's copied together unless they are all the frames or one
+    const void *fr_t = frames_dev, *fr_g = frames_dev;
+    int64_t stride_t = frame_stride, stride_g = frame_stride, fld_t = ld, fld_g = ld;
+    if (conv) {
+        c->frame_stack.alloc(slot * 2 * Bn);
+        int g = 0, fh, fw;
+        int64_t fld;
+        for (int s = 0; s < Bn; ++s) {
+            const void* one;
+            const size_t at = in_g[(size_t)s] ? (size_t)Bn + g++ : (size_t)s;
+            prescale_frame(c, (const char*)frames_dev + (int64_t)s * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream, one, fh, fw, fld,
+                           (char*)c->frame_stack.p + slot * at);
+        }
+        fr_t = c->frame_stack.p;
+        fr_g = (const char*)c->frame_stack.p + slot * Bn;
+        stride_t = stride_g = (int64_t)slot;
+        fld_t = fld_g = ow;
+    } else if (nG == 1) {
+        fr_g = (const char*)frames_dev + (int64_t)gs[0] * frame_stride;
+    } else if (nG > 0 && nG < Bn) {
+        c->frame_stack.alloc(slot * Bn);
+        for (int g = 0; g < nG; ++g)
+            HG_HIP(hipMemcpy2DAsync((char*)c->frame_stack.p + slot * g, (size_t)ow, (const char*)frames_dev + (int64_t)gs[(size_t)g] * frame_stride, (size_t)ld,
+                                    (size_t)ow, (size_t)oh, hipMemcpyDeviceToDevice, st));
+        fr_g = c->frame_stack.p;
+        stride_g = (int64_t)slot;
+        fld_g = ow;
+    }
+    int64_t rows_t = 0, rows_g = 0;
+    const int cap = t->rows_cap();
+    int32_t seq = 0;
+    // 1. the tracked pass, enqueued whole: no count is read back, its one wait is the last thing this call does
+    if (nT) {
+        for (int s : gs)      // due for a rescan: its boxes take no part (the full-grid pass's hand-over writes the count again)
+            if (t->held[(size_t)s]) HG_HIP(hipMemsetAsync(t->held_dev() + s, 0, 4, st));
+        Bounded B{};
+        B.face_dev = t->box_dev();
+        B.n_faces = (int)held_sum;
+        B.tc = t->tc;
+        B.held_dev = t->held_dev();
+        B.n_streams = Bn;
+        B.max_faces = K;
+        const FrameStack FS{Bn, stride_t, (int64_t)kTracked * K};
+        const int64_t n0 = (int64_t)kTracked * held_sum;
+        int64_t n = 0;
+        int cur = 0;
+        detect_impl(c, fr_t, oh, ow, fld_t, nullptr, nullptr, nullptr, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, nullptr, &rows_t, stream, &cur, &B, &FS);
+        SlotChain S{};
+        const double* purged = nullptr;
+        const int32_t *seg_first = nullptr, *seg_kept = nullptr;
+        hg::eyes_frames_tail_bounded(e, fr_t, Bn, stride_t, oh, ow, fld_t, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
+                                     (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, FS.n0, n0, B.final_count, &purged, &seg_first, &seg_kept,
+                                     &S.row_src, &S.kept_idx, st);
+        S.oidx = (const int32_t*)c->oidx[cur].p;
+        TrackerResults R{};
+        R.words = t->res_words();
+        R.rows = t->res_rows();
+        R.slots = t->res_slots();
+        R.cap = cap;
+        seq = ++t->seq;
+        hipLaunchKernelGGL(k_stream_handover, (unsigned)Bn, 128, 0, st, purged, seg_first, seg_kept, (const int32_t*)nullptr, t->box_dev(), t->held_dev(), K, S,
+                           (int)FS.n0, R);
+        hipLaunchKernelGGL(k_publish_seq, 1, 1, 0, st, (int32_t*)t->host_res, seq);
+        HG_HIP(hipGetLastError());
+    }
+    // 2. the full-grid pass on the other streams' frames; its kernels follow the tracked pass's hand-over in stream order, so the
+    // workspaces of the two handles serve both
+    std::vector<double> g_rows;
+    std::vector<int32_t> g_first((size_t)nG + 1, 0), g_before((size_t)nG, 0);
+    if (nG) {
+        const int64_t n0 = T.first[T.n_levels], total = n0 * nG;
+        const FrameStack FS{nG, stride_g, n0};
+        int64_t n = 0;
+        int cur = 0;
+        detect_impl(c, fr_g, oh, ow, fld_g, nullptr, nullptr, &T, total, nullptr, nullptr, nullptr, nullptr, total, &n, nullptr, &rows_g, stream, &cur, nullptr, &FS);
+        g_rows.resize((size_t)(n + nG) * 10);
+        hg::eyes_frames_tail(e, fr_g, nG, stride_g, oh, ow, fld_g, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
+                             (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, n0, n, g_rows.data(), n + nG, g_first.data(), g_before.data(), st);
+        if (n > 0) {      // the first rows of every stream become its held faces: the purge's device rows into the state, in stream order
+            const double* purged = nullptr;
+            const int32_t *seg_first = nullptr, *seg_kept = nullptr;
+            hg::eyes_frames_buffers(e, nG, &purged, &seg_first, &seg_kept);
+            int32_t* gmap = t->res_gmap();      // (the tail above has synchronised the stream: no earlier kernel still reads it)
+            for (int g = 0; g < nG; ++g) gmap[g] = gs[(size_t)g];
+            hipLaunchKernelGGL(k_stream_handover, (unsigned)nG, 128, 0, st, purged, seg_first, seg_kept, (const int32_t*)gmap, t->box_dev(), t->held_dev(), K,
+                               SlotChain{}, kTracked * K, TrackerResults{});
+            HG_HIP(hipGetLastError());
+        } else if (nG == Bn) {
+            HG_HIP(hipMemsetAsync(t->held_dev(), 0, (size_t)Bn * 4, st));
+        } else {
+            for (int s : gs) HG_HIP(hipMemsetAsync(t->held_dev() + s, 0, 4, st));
+        }
+        for (int g = 0; g < nG; ++g) {      // the hand-over's rule, on the rows the host has already
+            const int s = gs[(size_t)g];
+            int carried = 0;
+            for (int64_t j = g_first[(size_t)g]; j < g_first[(size_t)g + 1] && j < g_first[(size_t)g] + K; ++j) {
+                bool ok = true;
+                for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(g_rows[(size_t)j * 10 + q]);
+                carried += ok ? 1 : 0;
+            }
+            t->held[(size_t)s] = carried;
+            t->run[(size_t)s] = 0;
+        }
+    }
+    // 3. the one wait of the tracked pass: the sequence word is polled (publish_count); a deadline guards against a device that never answers
+    if (nT) {
+        int32_t* word = (int32_t*)t->host_res;
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != seq; ++spins) {
+            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+                HG_HIP(hipStreamSynchronize(st));
+                if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) break;
+                hg::fail(HG_ERR_DEVICE, "tracked pass did not report its result");
+            }
+            __builtin_ia32_pause();
+        }
+        const int32_t* words = t->res_words();
+        for (int s = 0; s < Bn; ++s) {
+            if (in_g[(size_t)s]) continue;
+            const int32_t kept = words[s * 4], before = words[s * 4 + 1], carried = words[s * 4 + 2];
+            if (kept < 0 || kept > cap || before < 0 || carried < 0 || carried > K) hg::fail(HG_ERR_STATE, "stream %d: bad counts from the device", s);
+            t->held[(size_t)s] = carried;
+            ++t->run[(size_t)s];
+        }
+    }
+    // both hand-overs have happened: the state is valid whatever follows
+    int64_t total_kept = 0;
+    for (int s = 0, g = 0; s < Bn; ++s) {
+        if (n_held) n_held[s] = t->held[(size_t)s];
+        if (used_tracked_grid) used_tracked_grid[s] = in_g[(size_t)s] ? 0 : 1;
+        total_kept += in_g[(size_t)s] ? g_first[(size_t)g + 1] - g_first[(size_t)g] : t->res_words()[s * 4];
+        g += in_g[(size_t)s];
+    }
+    if (rows_executed) *rows_executed = rows_t + rows_g;
+    if (total_kept > out_cap) {
+        for (int s = 0; s <= Bn; ++s) stream_first[s] = 0;
+        hg::fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)total_kept, (long long)out_cap);
+    }
+    if (total_kept > 0 && !out_rows) hg::fail(HG_ERR_ARG, "null output rows");
+    int64_t at = 0;
+    for (int s = 0, g = 0; s < Bn; ++s) {
+        stream_first[s] = (int32_t)at;
+        if (in_g[(size_t)s]) {
+            const int64_t lo = g_first[(size_t)g], m = g_first[(size_t)g + 1] - lo;
+            if (m) memcpy(out_rows + at * 10, g_rows.data() + (size_t)lo * 10, (size_t)m * 80);
+            for (int64_t j = 0; slots && j < m; ++j) slots[at + j] = -1;      // no held face stands behind a row of the full grid
+            if (n_before_purge) n_before_purge[s] = g_before[(size_t)g];
+            at += m;
+            ++g;
+        } else {
+            const int64_t m = t->res_words()[s * 4];
+            if (m) memcpy(out_rows + at * 10, t->res_rows() + (size_t)s * cap * 10, (size_t)m * 80);
+            if (m && slots) memcpy(slots + at, t->res_slots() + (size_t)s * cap, (size_t)m * 4);
+            if (n_before_purge) n_before_purge[s] = t->res_words()[s * 4 + 1];
+            at += m;
+        }
+    }
+    stream_first[Bn] = (int32_t)at;
+}
+}  // namespace
+
+extern "C" {
+
+int hg_cascade_tracked_grid_streams_device(int device, const hg_tracked_consts* consts, const double* faces_dev, const int32_t* held_dev, int n_streams,
+                                           int max_faces, double* boxes_dev, double* level_dev, void* stream) {
+    return guarded([&] {
+        if (n_streams < 1 || n_streams > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "n_streams %d outside 1..%d", n_streams, HG_MAX_STACK_FRAMES);
+        if (max_faces < 1 || max_faces > kMaxFaces) hg::fail(HG_ERR_ARG, "max_faces %d outside 1..%d", max_faces, kMaxFaces);
+        if (!consts || !faces_dev || !held_dev || !boxes_dev || !level_dev) hg::fail(HG_ERR_ARG, "null argument");
+        check_finite_consts(*consts);
+        set_dev(device);
+        hipLaunchKernelGGL(k_cascade_init_tracked_streams, 1, 1024, 0, (hipStream_t)stream, *consts, faces_dev, held_dev, n_streams, max_faces, boxes_dev, level_dev,
+                           (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+        HG_HIP(hipGetLastError());
+    });
+}
+
+int hg_stream_tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int n_streams, int max_faces, int rescan_every,
+                             hg_stream_tracker** out) {
+    return guarded([&] {
+        if (!out) hg::fail(HG_ERR_ARG, "null output handle pointer");
+        *out = nullptr;
+        check_stream_set(n_streams, max_faces, rescan_every);
+        if (!c || !e || !consts) hg::fail(HG_ERR_ARG, "null argument");
+        check_finite_consts(*consts);
+        if (consts->subimage_width != (double)c->w || consts->subimage_height != (double)c->h)
+            hg::fail(HG_ERR_ARG, "tracked-grid sub-image %g x %g, the cascade's is %d x %d", consts->subimage_width, consts->subimage_height, c->w, c->h);
+        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+        set_dev(c->device);
+        auto t = std::make_unique<hg_stream_tracker>();
+        t->c = c;
+        t->e = e;
+        t->tc = *consts;
+        t->n_streams = n_streams;
+        t->max_faces = max_faces;
+        t->rescan_every = rescan_every;
+        t->held.assign((size_t)n_streams, 0);
+        t->run.assign((size_t)n_streams, 0);
+        const size_t state_bytes = (size_t)n_streams * max_faces * 32 + (size_t)n_streams * 4;
+        t->state.alloc(state_bytes);
+        HG_HIP(hipMemset(t->state.p, 0, state_bytes));
+        HG_HIP(hipHostMalloc((void**)&t->host_res, t->res_bytes(), hipHostMallocDefault));
+        memset(t->host_res, 0, t->res_bytes());
+        *out = t.release();
+    });
+}
+
+void hg_stream_tracker_free(hg_stream_tracker* t) {
+    if (!t) return;
+    if (hipSetDevice(t->c->device) == hipSuccess && t->host_res) (void)hipHostFree(t->host_res);
+    delete t;
+}
+
+int hg_stream_tracker_reset(hg_stream_tracker* t, int stream_index) {
+    return guarded([&] {
+        if (!t) hg::fail(HG_ERR_ARG, "null tracker handle");
+        if (stream_index < -1 || stream_index >= t->n_streams) hg::fail(HG_ERR_ARG, "stream %d of %d (-1: all)", stream_index, t->n_streams);
+        set_dev(t->c->device);
+        if (stream_index < 0) {      // steps are synchronous: nothing of this tracker is in flight
+            HG_HIP(hipMemset(t->held_dev(), 0, (size_t)t->n_streams * 4));
+            std::fill(t->held.begin(), t->held.end(), 0);
+            std::fill(t->run.begin(), t->run.end(), 0);
+            t->w = t->h = 0;
+        } else {
+            HG_HIP(hipMemset(t->held_dev() + stream_index, 0, 4));
+            t->held[(size_t)stream_index] = 0;
+            t->run[(size_t)stream_index] = 0;
+        }
+    });
+}
+
+int hg_stream_tracker_step_frames_device(hg_stream_tracker* t, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                                         int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows, int64_t out_cap,
+                                         int32_t* stream_first, int32_t* n_before_purge, int32_t* used_tracked_grid, int32_t* n_held, int32_t* slots,
+                                         int64_t* rows_executed, void* stream) {
+    return guarded([&] {
+        // the numbers first, then the handle
+        if (n_frames < 1 || n_frames > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "%d frames in a stack (1..%d)", n_frames, HG_MAX_STACK_FRAMES);
+        check_frame_geometry(frame_h, frame_w, ld);
+        if (frame_stride < (int64_t)(frame_h - 1) * ld + frame_w)
+            hg::fail(HG_ERR_ARG, "frames %lld bytes apart, a frame reaches over %lld", (long long)frame_stride, (long long)((int64_t)(frame_h - 1) * ld + frame_w));
+        if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+        if (!t || !stream_first) hg::fail(HG_ERR_ARG, "null argument");
+        if (n_frames != t->n_streams) hg::fail(HG_ERR_ARG, "%d frames for a set of %d streams", n_frames, t->n_streams);
+        try {
+            stream_tracker_step(t, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_rows, out_cap,
+                                stream_first, n_before_purge, used_tracked_grid, n_held, slots, rows_executed, stream);
+        } catch (const hg::Error& err) {
+            if (err.code != HG_ERR_ARG) t->forget();      // (a refused argument launched nothing, or came after both hand-overs)
+            throw;
+        } catch (...) {
+            t->forget();
+            throw;
+        }
     });
 }
 

@@ -391,6 +391,16 @@ __global__ void __launch_bounds__(1024) k_purge_frames(const double* __restrict_
     purge_rows(rows + lo * 10, n, n, out + (lo + f) * 10, seg_kept + f, scratch + (lo + f) * 16, nullptr);
 }
 
+// The same, and for every row frame f keeps its index within the frame's rows (purge_rows' kept_out), at entry seg_first[f] + f onwards
+// of kept_idx: what the slots of a stream set's tracked pass are composed of (hg_cascade.hip, k_stream_handover).  A kernel of its own,
+// so that k_purge_frames stays the code it was.
+__global__ void __launch_bounds__(1024) k_purge_frames_kept(const double* __restrict__ rows, const int32_t* __restrict__ seg_first, double* __restrict__ out,
+                                                            int32_t* __restrict__ seg_kept, char* __restrict__ scratch, int32_t* __restrict__ kept_idx) {
+    const int f = blockIdx.x;
+    const int64_t lo = seg_first[f], n = seg_first[f + 1] - lo;
+    purge_rows(rows + lo * 10, n, n, out + (lo + f) * 10, seg_kept + f, scratch + (lo + f) * 16, kept_idx + lo + f);
+}
+
 void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, double* out, int32_t* count, void* scratch, hipStream_t st,
                   int32_t* kept_out = nullptr) {
     hipLaunchKernelGGL(k_purge, 1, 1024, 0, st, rows, n_max, n_dev, out, count, (char*)scratch, kept_out);
@@ -543,6 +553,45 @@ void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t f
         at += kf;
     }
     frame_first[n_frames] = (int32_t)at;
+}
+
+// The stack tail for the TRACKED pass of a stream set (hg_stream_tracker_step_frames_device): eyes_frames_tail and eyes_frame_tail_bounded
+// combined.  The survivor count is the device word *n_dev, at most n_bound; survivor i belongs to frame orig_index[i] / n0 (the rows
+// between the live count and the bound carry index 0: frame 0, a window k_eye_boxes replaces anyway); the eye step runs on all n_bound
+// rows as one batch, the purge per frame with its kept indices, and NOTHING is read back.  *purged: frame f's kept rows from row
+// seg_first[f] + f on; *seg_first (n_frames + 1) / *seg_kept (n_frames): first assembled row and kept rows of every frame; *row_src /
+// *kept_idx: as eyes_frame_tail_bounded, kept_idx per frame from entry seg_first[f] + f on and relative to the frame's first row.
+void eyes_frames_tail_bounded(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
+                              const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n_bound,
+                              const int32_t* n_dev, const double** purged, const int32_t** seg_first, const int32_t** seg_kept, const int32_t** row_src,
+                              const int32_t** kept_idx, hipStream_t st) {
+    if (!e || !n_dev || n_bound < 1 || n_frames < 1 || n0 < 1) fail(HG_ERR_ARG, "bad bounded eye step");
+    e->reserve(n_bound + n_frames);      // before any workspace pointer is taken (see eyes_frame_tail); count + 1 rows per frame
+    e->row_frame.alloc((size_t)n_bound * 2 * 4);
+    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
+    int32_t* first = (int32_t*)e->seg.p;
+    int32_t* kept = first + n_frames + 1;
+    hipLaunchKernelGGL(k_eye_row_frames, (unsigned)((n_bound + 255) / 256), 256, 0, st, n_bound, orig_index, (int)n0, (int32_t*)e->row_frame.p);
+    HG_HIP(hipGetLastError());
+    const EyeFrames F{n_frames, frame_stride, (const int32_t*)e->row_frame.p};
+    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n_bound, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st,
+             n_dev, (int32_t*)e->row_src.p, &F);
+    hipLaunchKernelGGL(k_frame_segments, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, (int)n0, n_frames, first);
+    hipLaunchKernelGGL(k_purge_frames_kept, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)first, (double*)e->purged.p, kept,
+                       (char*)e->scratch.p, (int32_t*)e->kept_idx.p);
+    HG_HIP(hipGetLastError());
+    *purged = (const double*)e->purged.p;
+    *seg_first = first;
+    *seg_kept = kept;
+    *row_src = (const int32_t*)e->row_src.p;
+    *kept_idx = (const int32_t*)e->kept_idx.p;
+}
+
+// What a stream set's hand-over kernel reads after eyes_frames_tail with n > 0 of a stack of n_frames: the same buffers.
+void eyes_frames_buffers(const hg_eyes* e, int n_frames, const double** purged, const int32_t** seg_first, const int32_t** seg_kept) {
+    *purged = (const double*)e->purged.p;
+    *seg_first = (const int32_t*)e->seg.p;
+    *seg_kept = (const int32_t*)e->seg.p + n_frames + 1;
 }
 
 // What the tracker's hand-over kernel reads after an ordinary frame's tail (eyes_frame_tail with n > 0): the same two buffers.
