@@ -647,6 +647,59 @@ int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void*
                                           int n_levels, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge,
                                           int32_t* stage_counts, int64_t* rows_executed, void* stream);
 
+/* --- A LIST of frames of different sizes through one pooled pass (a folder of photographs, cameras of different resolutions) --------
+ * The stack entries above take frames of one size.  These take a list: every frame brings its own pointer, size and row stride, and —
+ * in the cascade — its own prescaled size and level table.  The candidates are the CONCATENATION of the frames' grids: with n0_f the
+ * windows of frame f's level table and first[f] = n0_0 + ... + n0_{f-1}, window first[f] + j is window j of frame f.  As for the stack,
+ * each result is DEFINED as what the per-frame entry returns for that frame, bit for bit (tests/test_frame_list_gpu.py).  Frames of
+ * ONE size stay the stack entries' case: those copy one grid and need no per-box descriptor.
+ *
+ * The descriptor arrays (hg_frame_ref, hg_cascade_frame, and the level tables they point to) are HOST memory, consumed before the call
+ * returns: the caller may reuse them at once.
+ *
+ * The patcher: hg_patcher_extract_frames_device with the frame of row i described by frames[row_frame_dev[i]] — grey uint8, frame_h x
+ * frame_w, rows ld bytes apart, anywhere in device memory.  Rule, tables and bytes are those of hg_patcher_extract_filter_device on that
+ * one frame; a row whose frame index lies outside [0, n_frames) is an all-zero window and forms no address from the index.
+ * HG_ERR_ARG, nothing launched and neither the handle nor a data pointer dereferenced: a null pointer (delta_angs_dev and stream may be
+ * null), n_frames < 1 or > HG_MAX_STACK_FRAMES, ANY frame with frame_h <= 0, frame_w <= 0, ld < frame_w or a null frame_dev — the
+ * message names the frame, and one bad frame refuses the whole call —, a rotated NEAREST call with a frame of 32768 pixels or more per
+ * side, n < 0, an unknown filter, a bad output size / dtype / ldo.  n == 0: HG_OK.  Enqueued on `stream`. */
+typedef struct hg_frame_ref {
+    const void* frame_dev;
+    int32_t frame_h, frame_w;
+    int64_t ld;
+} hg_frame_ref;
+typedef struct hg_cascade_frame {
+    const void* frame_dev;          /* in the cascade's frame format; ld in bytes */
+    int32_t frame_h, frame_w;
+    int64_t ld;
+    int32_t prescale_w, prescale_h; /* 0, 0: none */
+    const hg_cascade_level* levels; /* the grid of the (prescaled) frame */
+    int32_t n_levels;
+} hg_cascade_frame;
+int hg_patcher_extract_frame_list_device(hg_patcher* p, int filter, const hg_frame_ref* frames, int n_frames, const double* boxes_dev,
+                                         const double* delta_angs_dev, const int32_t* row_frame_dev, int64_t n, int out_w, int out_h,
+                                         void* out_dev, int out_dtype, int64_t ldo, void* stream);
+/* hg_cascade_detect_frames_device for a list.  Each frame is prescaled / converted by the code a single frame runs, to ITS prescaled
+ * size, into its own slot of one cascade-owned grey buffer; a grey frame without a prescale is read where it is.  One kernel lays out
+ * the concatenated grids from a device array of the DISTINCT level tables, with hg_cascade_grid_device's arithmetic.  The stage loop is
+ * the one loop on the sum of the n0_f candidates; every extraction takes the row's frame from a per-window frame array.  First-stage
+ * index tables: frames whose prescaled size and level table are equal share one set, all sets in one buffer that lives for the call.
+ * Outputs as for the stack: survivors ordered by frame, frame_first (n_frames + 1), out_orig_index within the frame's own grid,
+ * stage_counts / *rows_executed by the pooled rule.  HG_ERR_ARG before anything is launched or written: a null c / frames /
+ * frame_first, n_frames < 1 or > HG_MAX_STACK_FRAMES, out_cap < 0, and for ANY frame (the message names it) a bad geometry (frame_h <=
+ * 0, frame_w <= 0, ld < frame_w bytes-per-pixel), a null frame_dev, null levels, n_levels outside 1..32, a bad prescale size, 32768
+ * pixels or more per side under its grid where a later NEAREST stage (or the NEAREST eye step of the faces entry) cuts rotated windows
+ * from it; a total window count above 2^31 / 64.  HG_ERR_ARG when out_cap is below the survivors.  Synchronous. */
+int hg_cascade_detect_frame_list_device(hg_cascade* c, const hg_cascade_frame* frames, int n_frames, double* out_coords, double* out_angles,
+                                        int32_t* out_orig_index, double* out_confidence, int64_t out_cap, int32_t* frame_first,
+                                        int32_t* stage_counts, int64_t* rows_executed, void* stream);
+/* hg_cascade_detect_faces_frames_device for a list: the pooled stage loop above, the eye step on ALL survivors as one batch, every eye
+ * patch cut from its face's own prescaled frame, the purge per frame.  Outputs and refusals as there and as above.  Synchronous. */
+int hg_cascade_detect_faces_frame_list_device(hg_cascade* c, hg_eyes* e, const hg_cascade_frame* frames, int n_frames, double* out_rows,
+                                              int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, int32_t* stage_counts,
+                                              int64_t* rows_executed, void* stream);
+
 /* --- Tracking one face across a stream of frames (the reference's track_single_face mode) ---------------------------------
  * Once a frame has produced a face, its first purged detection is carried over (FaceDetectUpdated.py:1189-1195) and the next
  * frame searches NINE windows instead of the pyramid: one sampling value from the size of that box (face_analysis.py:576-585),

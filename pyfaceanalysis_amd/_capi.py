@@ -20,7 +20,7 @@ HG_MAX_STREAM_WINDOWS = 8192    # 9 * n_streams * max_faces of a stream set (inc
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks, the stream set
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks, the stream set, the frame lists
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
@@ -33,6 +33,7 @@ _ENTRIES_SINCE_FRAME_STACKS = ("hg_patcher_extract_frames_device", "hg_cascade_d
 _ENTRIES_SINCE_ESTIMATE_FRAMES = ("hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device")
 _ENTRIES_SINCE_STREAM_SET = ("hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
                              "hg_cascade_tracked_grid_streams_device")
+_ENTRIES_SINCE_FRAME_LISTS = ("hg_patcher_extract_frame_list_device", "hg_cascade_detect_frame_list_device", "hg_cascade_detect_faces_frame_list_device")
 _lib = None
 
 
@@ -51,6 +52,15 @@ class HgCascadeConsts(C.Structure):
 
 class HgCascadeLevel(C.Structure):      # hg_cascade_level: one pyramid level of the first-stage grid (face_analysis.py:630-652)
     _fields_ = [("nx", C.c_int32), ("ny", C.c_int32)] + [(n, C.c_double) for n in ("x_stop", "y_stop", "patch_w", "patch_h", "max_dx", "max_dy", "base_side")]
+
+
+class HgFrameRef(C.Structure):          # hg_frame_ref: one grey frame of a list (hg_patcher_extract_frame_list_device)
+    _fields_ = [("frame_dev", C.c_void_p), ("frame_h", C.c_int32), ("frame_w", C.c_int32), ("ld", C.c_int64)]
+
+
+class HgCascadeFrame(C.Structure):      # hg_cascade_frame: one frame of a list with its prescaled size and level table
+    _fields_ = [("frame_dev", C.c_void_p), ("frame_h", C.c_int32), ("frame_w", C.c_int32), ("ld", C.c_int64), ("prescale_w", C.c_int32),
+                ("prescale_h", C.c_int32), ("levels", C.POINTER(HgCascadeLevel)), ("n_levels", C.c_int32)]
 
 
 class HgCascadeStage(C.Structure):
@@ -197,6 +207,9 @@ def lib():
                                                       C.POINTER(i64), vp]),
         "hg_cascade_detect_faces_frames_device": (C.c_int, [vp, vp, vp, i32, i64, i32, i32, i64, i32, i32, C.POINTER(HgCascadeLevel), i32, vp, i64, vp, vp, vp,
                                                             C.POINTER(i64), vp]),
+        "hg_patcher_extract_frame_list_device": (C.c_int, [vp, i32, C.POINTER(HgFrameRef), i32, vp, vp, vp, i64, i32, i32, vp, i32, i64, vp]),
+        "hg_cascade_detect_frame_list_device": (C.c_int, [vp, C.POINTER(HgCascadeFrame), i32, vp, vp, vp, vp, i64, vp, vp, C.POINTER(i64), vp]),
+        "hg_cascade_detect_faces_frame_list_device": (C.c_int, [vp, vp, C.POINTER(HgCascadeFrame), i32, vp, i64, vp, vp, vp, C.POINTER(i64), vp]),
         "hg_cascade_tracked_grid_device": (C.c_int, [i32, C.POINTER(HgTrackedConsts), vp, vp, vp, vp]),
         "hg_tracker_create": (C.c_int, [vp, vp, C.POINTER(HgTrackedConsts), C.POINTER(vp)]),
         "hg_tracker_free": (None, [vp]),
@@ -225,7 +238,7 @@ def lib():
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
                         _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS +
-                        _ENTRIES_SINCE_ESTIMATE_FRAMES + _ENTRIES_SINCE_STREAM_SET) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_ESTIMATE_FRAMES + _ENTRIES_SINCE_STREAM_SET + _ENTRIES_SINCE_FRAME_LISTS) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -258,6 +271,7 @@ EXPORTED_SYMBOLS = (
     "hg_patcher_normalize_frames_device", "hg_estimator_estimate_frames_device",
     "hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
     "hg_cascade_tracked_grid_streams_device",
+    "hg_patcher_extract_frame_list_device", "hg_cascade_detect_frame_list_device", "hg_cascade_detect_faces_frame_list_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

@@ -123,6 +123,7 @@ class DeviceCascade(object):
         self._levels = {}        # (frame size, smallest_face) -> level table (frame_levels)
         self._prescale = {}      # (frame size, prescaled size) -> (box tensor, output tensor) of the prescale step
         self._frames = {}        # (frame size, smallest_face, prescale size) -> everything detect_frame needs per call
+        self._list_bufs = {}     # kind of list call -> (rows, output buffers): one set, grown on demand (_list_plan)
         for st in self.stages:
             if st.classifier.input_dim > self.k:
                 raise ValueError("stage %s: classifier reads %d features, cascade keeps %d" % (st.name, st.classifier.input_dim, self.k))
@@ -450,6 +451,115 @@ class DeviceCascade(object):
             vp(before), vp(counts), C.byref(n_rows), t.cuda.current_stream(self.dev).cuda_stream))
         return dict(faces=[rows[int(first[f]):int(first[f + 1])].copy() for f in range(b)], n_before_purge=before.tolist(), counts=counts.tolist(),
                     rows_executed=n_rows.value, n_windows=b * n0)
+
+    def _check_list(self, frame_list):
+        """A list (or tuple) of frames of ANY sizes, or ValueError; None for an empty list.  Every frame is checked as ``_check_frame``
+        checks one — (H, W) uint8, (H, W, C) for a colour ``frame_format``, packed pixels — and, as ``_check_stack`` does, refused when
+        it is empty or its rows are fewer bytes apart than they hold (a broadcast view).  Shapes, dtypes and strides are checked
+        before the device, which is checked before the library is touched."""
+        t = self.torch
+        if not isinstance(frame_list, (list, tuple)):
+            raise ValueError("a list of frames must be a list or tuple of tensors (a stack of same-size frames: detect_frames)")
+        if len(frame_list) == 0:
+            return None
+        if len(frame_list) > _capi.HG_MAX_STACK_FRAMES:
+            raise ValueError("%d frames in a list, at most %d" % (len(frame_list), _capi.HG_MAX_STACK_FRAMES))
+        c = frames.CHANNELS[self.frame_format]
+        for i, f in enumerate(frame_list):
+            if not isinstance(f, t.Tensor):
+                raise ValueError("frame %d of the list is not a tensor" % i)
+            try:
+                frames.check_color_frame(t, f, self.frame_format, f.device)
+            except ValueError as e:
+                raise ValueError("frame %d of the list: %s" % (i, e))
+            fh, fw = int(f.shape[0]), int(f.shape[1])
+            if fh == 0 or fw == 0:
+                raise ValueError("frame %d of the list is empty" % i)
+            if fh > 1 and f.stride(0) < fw * c:
+                raise ValueError("frame %d of the list: rows %d bytes apart hold %d bytes: a broadcast or overlapping view is not a frame" %
+                                 (i, f.stride(0), fw * c))
+        for i, f in enumerate(frame_list):
+            if f.device != self.dev:
+                raise ValueError("frame %d of the list must live on %s" % (i, self.dev))
+        return list(frame_list)
+
+    def _list_plan(self, what, frame_list, smallest_face, prescale_size):
+        """The descriptor array of this list (hg_cascade_frame, assembled per call), the window count of every frame, and output buffers.
+        What depends on a frame's size alone — prescaled size, level table — is kept per distinct size, as detect_frame's plans are."""
+        c = frames.CHANNELS[self.frame_format]
+        arr = (_capi.HgCascadeFrame * len(frame_list))()
+        n0s = []
+        for i, f in enumerate(frame_list):
+            fh, fw = int(f.shape[0]), int(f.shape[1])
+            key = ("list", fw, fh, float(smallest_face), int(prescale_size or 0))
+            plan = self._frames.get(key)
+            if plan is None:
+                pw, ph = grid.prescaled_size(fw, fh, prescale_size) if prescale_size else (fw, fh)
+                pre = (pw, ph) if (pw, ph) != (fw, fh) else (0, 0)
+                plan = self._frames[key] = (pre,) + tuple(frame_levels(pw, ph, smallest_face, self.pipeline, (self.w, self.h)))
+            pre, levels, n_levels, n0 = plan
+            a = arr[i]
+            a.frame_dev, a.frame_h, a.frame_w, a.ld = f.data_ptr(), fh, fw, (f.stride(0) if fh > 1 else fw * c)
+            a.prescale_w, a.prescale_h = pre
+            a.levels, a.n_levels = C.cast(levels, C.POINTER(_capi.HgCascadeLevel)), n_levels
+            n0s.append(n0)
+        b, total = len(frame_list), sum(n0s)
+        # ONE set of output buffers per kind of call, grown on demand (nearly every list of a folder of photographs has another length and
+        # window count: a set per (b, total) would stay with the cascade for ever)
+        rows, bufs = self._list_bufs.get(what, (0, None))
+        if bufs is None or rows < total + b or len(bufs[1]) < b + 1:
+            rows = max(total + b, 2 * rows)
+            nb = max(b, 2 * (len(bufs[1]) - 1) if bufs else 0)
+            first, counts = np.zeros(nb + 1, dtype=np.int32), np.zeros(len(self.stages), dtype=np.int32)
+            if what == "list bufs":
+                out = (np.empty((rows, 4)), np.empty(rows), np.empty(rows, dtype=np.int32), np.empty(rows))
+            else:
+                out = (np.empty((rows, 10)), np.zeros(nb, dtype=np.int32))      # the purge may keep n + 1 rows of every frame
+            bufs = (out, first, counts, C.c_int64())
+            self._list_bufs[what] = (rows, bufs)
+        return arr, total, bufs
+
+    def detect_frame_list(self, frame_list, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+        """``detect_frame`` for a list of frames of DIFFERENT sizes as ONE pooled pass (hg_cascade_detect_frame_list_device): every frame is
+        prescaled to its own size and has its own grid, and the concatenated grids are one batch of candidates through the stage loop.
+        frame_list: see ``_check_list`` (shapes and row strides may differ; frames of one size are ``detect_frames``'s case).  Returns
+        what ``detect_frames`` returns: ``frames``, a list of dicts — array for array what ``detect_frame`` returns for that frame — and
+        the pooled counts, rows_executed and n_windows (the sum over the frames).  An empty list returns an empty result without
+        touching the library."""
+        t = self.torch
+        frame_list = self._check_list(frame_list)
+        if frame_list is None:
+            return dict(frames=[], counts=[0] * len(self.stages), rows_executed=0, n_windows=0)
+        arr, total, ((coords, angles, oidx, conf), first, counts, rows) = self._list_plan("list bufs", frame_list, smallest_face, prescale_size)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _capi.check(_capi.lib().hg_cascade_detect_frame_list_device(
+            self._handle(), arr, len(frame_list), vp(coords), vp(angles), vp(oidx), vp(conf), total, vp(first), vp(counts), C.byref(rows),
+            t.cuda.current_stream(self.dev).cuda_stream))
+        out = []
+        for f in range(len(frame_list)):
+            lo, hi = int(first[f]), int(first[f + 1])
+            out.append(dict(coords=coords[lo:hi].copy(), angles=angles[lo:hi].copy(), orig_index=oidx[lo:hi].astype(np.int64),
+                            confidence=conf[lo:hi].copy()))
+        return dict(frames=out, counts=counts.tolist(), rows_executed=rows.value, n_windows=total)
+
+    def detect_faces_frame_list(self, frame_list, eyes, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
+        """``detect_faces`` for a list of frames of different sizes (hg_cascade_detect_faces_frame_list_device): the pooled stage loop, the
+        eye step on all survivors as one batch — every eye patch cut from its face's own prescaled frame — and the purge per frame.
+        Returns what ``detect_faces_frames`` returns: ``faces``, a list of (m_b, 10) arrays, ``n_before_purge``, a list, and the pooled
+        counts, rows_executed, n_windows."""
+        t = self.torch
+        if eyes.device != self.device:
+            raise ValueError("eye locator on device %d, cascade on device %d" % (eyes.device, self.device))
+        frame_list = self._check_list(frame_list)
+        if frame_list is None:
+            return dict(faces=[], n_before_purge=[], counts=[0] * len(self.stages), rows_executed=0, n_windows=0)
+        arr, total, ((rows, before), first, counts, n_rows) = self._list_plan("list faces bufs", frame_list, smallest_face, prescale_size)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        _capi.check(_capi.lib().hg_cascade_detect_faces_frame_list_device(
+            self._handle(), eyes._handle(), arr, len(frame_list), vp(rows), len(rows), vp(first), vp(before), vp(counts), C.byref(n_rows),
+            t.cuda.current_stream(self.dev).cuda_stream))
+        return dict(faces=[rows[int(first[f]):int(first[f + 1])].copy() for f in range(len(frame_list))], n_before_purge=before[:len(frame_list)].tolist(),
+                    counts=counts.tolist(), rows_executed=n_rows.value, n_windows=total)
 
     def close(self):
         if self._h is not None:

@@ -17,6 +17,7 @@
 
 #include "hg_common.hpp"
 #include "hg_frame_format.hpp"
+#include "hg_frame_list.hpp"
 #include "hg_gauss_dev.hpp"
 
 namespace hg {
@@ -35,7 +36,10 @@ void eyes_frames_tail_bounded(hg_eyes* e, const void* frame_dev, int n_frames, i
                               const int32_t* n_dev, const double** purged, const int32_t** seg_first, const int32_t** seg_kept, const int32_t** row_src,
                               const int32_t** kept_idx, hipStream_t st);
 void eyes_frames_buffers(const hg_eyes* e, int n_frames, const double** purged, const int32_t** seg_first, const int32_t** seg_kept);
+void eyes_frame_list_tail(hg_eyes* e, const FrameList& fl, const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n,
+                          double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
 int eyes_device(const hg_eyes* e);
+int eyes_filter(const hg_eyes* e);
 }
 
 // No contraction anywhere below (hg_gauss_dev.hpp, the regression, is included above and keeps the build's default): under hipcc's
@@ -223,13 +227,8 @@ struct LevelTable {
     hg_cascade_level lv[kMaxLevels];
 };
 
-__global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coords, double* __restrict__ orig_level, double* __restrict__ coords,
-                                    double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf, int32_t* __restrict__ oidx,
-                                    int32_t* __restrict__ count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = T.first[T.n_levels];
-    if (i == 0 && count) *count = n;
-    if (i >= n) return;
+// Window i of the grid of T: its box into b[0..4), and its level (shared by k_cascade_init_grid and k_cascade_init_list: one arithmetic)
+__device__ __forceinline__ const hg_cascade_level& grid_window(const LevelTable& T, int i, double* b) {
     int L = 0;
     while (L + 1 < T.n_levels && i >= T.first[L + 1]) ++L;
     const hg_cascade_level& V = T.lv[L];
@@ -240,7 +239,22 @@ __global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coor
         return d_mul((double)j, d_div(stop, (double)(num - 1)));
     };
     const double x0 = lin(ix, V.nx, V.x_stop), y0 = lin(iy, V.ny, V.y_stop);
-    const double b[4] = {x0, y0, d_sub(d_add(x0, V.patch_w), 1.0), d_sub(d_add(y0, V.patch_h), 1.0)};
+    b[0] = x0;
+    b[1] = y0;
+    b[2] = d_sub(d_add(x0, V.patch_w), 1.0);
+    b[3] = d_sub(d_add(y0, V.patch_h), 1.0);
+    return V;
+}
+
+__global__ void k_cascade_init_grid(LevelTable T, double* __restrict__ orig_coords, double* __restrict__ orig_level, double* __restrict__ coords,
+                                    double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf, int32_t* __restrict__ oidx,
+                                    int32_t* __restrict__ count) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = T.first[T.n_levels];
+    if (i == 0 && count) *count = n;
+    if (i >= n) return;
+    double b[4];
+    const hg_cascade_level& V = grid_window(T, i, b);
     for (int q = 0; q < 4; ++q) orig_coords[(size_t)i * 4 + q] = b[q];
     orig_level[(size_t)i * 3] = V.max_dx;
     orig_level[(size_t)i * 3 + 1] = V.max_dy;
@@ -274,6 +288,39 @@ __global__ void k_cascade_init_frames(int n0, int n, double* __restrict__ orig_c
     neg[i] = 0.0;
     conf[i] = 0.0;
     oidx[i] = i;
+}
+
+// The start of a LIST of frames of different sizes (hg_cascade_detect_frame_list_device): the candidates are the concatenation of the
+// frames' grids — window desc[f].first + j is window j of frame f, laid out by grid_window from frame f's level table, tables[grid_of[f]]
+// (one table per DISTINCT grid) — and win_frame[i] = f, the frame of original window i, which every later kernel that needs a row's frame
+// reads through the row's original index.  first[] ascends strictly (a grid has at least one window): a binary search per thread.
+__global__ void k_cascade_init_list(const LevelTable* __restrict__ tables, const hg::FrameDesc* __restrict__ desc, const int32_t* __restrict__ grid_of,
+                                    int n_frames, int n, double* __restrict__ orig_coords, double* __restrict__ orig_level, double* __restrict__ coords,
+                                    double* __restrict__ angles, double* __restrict__ neg, double* __restrict__ conf, int32_t* __restrict__ oidx,
+                                    int32_t* __restrict__ count, int32_t* __restrict__ win_frame) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) *count = n;
+    if (i >= n) return;
+    int lo = 0, hi = n_frames - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (desc[mid].first <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    double b[4];
+    const hg_cascade_level& V = grid_window(tables[grid_of[lo]], i - desc[lo].first, b);
+    for (int q = 0; q < 4; ++q) {
+        orig_coords[(size_t)i * 4 + q] = b[q];
+        coords[(size_t)i * 4 + q] = b[q];
+    }
+    orig_level[(size_t)i * 3] = V.max_dx;
+    orig_level[(size_t)i * 3 + 1] = V.max_dy;
+    orig_level[(size_t)i * 3 + 2] = V.base_side;
+    angles[i] = 0.0;
+    neg[i] = 0.0;
+    conf[i] = 0.0;
+    oidx[i] = i;
+    win_frame[i] = lo;
 }
 
 // The start of a TRACKED frame (the reference's track_single_face branch with a face found on the previous frame): nine windows from
@@ -802,6 +849,11 @@ struct hg_cascade {
     int frame_format = HG_FRAME_L;       // hg_cascade_set_frame_format: how frame_dev / ld of the detect entries are read
     hg::DevBuf gray_frame;               // a colour frame that is not prescaled, converted (grows on demand, like pre_frame)
     hg::DevBuf frame_stack;              // hg_cascade_detect_frames_device: the prescaled / converted grey frames of a stack, dense, one after the other
+    // hg_cascade_detect_frame_list_device: the grey slots of the frames that are prescaled / converted; the descriptor table; the frame of
+    // every original window; and what depends on the list's geometry alone, kept under the key of the whole list (hg_frame_list.hpp) —
+    // the distinct level tables, every frame's whole-frame box and grid number
+    hg::DevBuf list_gray, list_desc, list_win, list_meta;
+    uint64_t list_key = 0;
     int prescale_filter = HG_RESAMPLE_NEAREST;      // hg_cascade_set_prescale_filter (enum hg_resample)
     int32_t* host_count = nullptr;       // pinned, device-visible: {count, sequence number} (publish_count)
     int32_t seq = 0;                     // sequence number of the last read-back asked for
@@ -956,9 +1008,19 @@ struct Bounded {
 // apart; the candidates are n_frames copies of the grid of `T` (n0 = n_frames * FS->n0: k_cascade_init_frames) and every extraction
 // cuts row i from frame orig_index[i] / FS->n0 (hg::patcher_extract_frames).  Nothing else differs: rows are independent, the
 // compaction keeps their order, so the survivors come out by frame and, inside a frame, in the order the frame alone gives.
+// A LIST of frames of different sizes (`list`, hg_cascade_detect_frame_list_device): frame_dev / frame_h / frame_w / ld are frame 0's,
+// stride and n0 are unused; the candidates are the concatenated grids (k_cascade_init_list) and every extraction takes row i's frame
+// from win_frame[orig_index[i]] (hg::patcher_extract_frame_list).  The same loop, for the same reason.
+struct ListRun {
+    hg::FrameList fl;
+    const LevelTable* tables_dev;      // one per distinct grid
+    const int32_t* grid_of_dev;        // per frame
+    int32_t* win_frame_dev;
+};
 struct FrameStack {
     int n_frames;
     int64_t stride, n0;
+    const ListRun* list = nullptr;
 };
 
 // Every frame-reading entry of this file refuses a bad frame as a bad ARGUMENT, before it launches or writes anything: a row stride
@@ -974,12 +1036,15 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
                  Bounded* B = nullptr, const FrameStack* FS = nullptr) {
     if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
     if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
-    if (n0 > 0 && (!frame_dev || (!T && !B && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
+    const ListRun* LS = FS ? FS->list : nullptr;
+    if (n0 > 0 && (!frame_dev || (!T && !B && !LS && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
     // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
     if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
     // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
     const bool SB = B && B->n_streams > 0;      // the tracked pass of a stream set: Bounded and FrameStack together
-    if (FS && !SB && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
+    if (LS && (T || B || FS->n_frames < 1 || FS->n_frames != LS->fl.n_frames || n0 != LS->fl.n_windows || !LS->tables_dev || !LS->win_frame_dev))
+        hg::fail(HG_ERR_ARG, "bad frame list");
+    if (FS && !LS && !SB && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
     if (B && !SB && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
     // the bound 9 * sum of held lies under the windows of the whole set, and those inside k_cascade_group's single-workgroup path (pad_to)
     if (SB && (T || !FS || FS->n_frames != B->n_streams || B->max_faces < 1 || B->max_faces > kMaxFaces || FS->n0 != (int64_t)kTracked * B->max_faces ||
@@ -1004,6 +1069,10 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)((n0 + 63) / 64), 64, 0, st, B->tc, B->face_dev, B->n_faces, (double*)c->orig_coords.p,
                            (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
                            (int32_t*)c->count.p);
+    } else if (LS) {
+        hipLaunchKernelGGL(k_cascade_init_list, (unsigned)((n0 + 255) / 256), 256, 0, st, LS->tables_dev, LS->fl.dev, LS->grid_of_dev, LS->fl.n_frames, (int)n0,
+                           (double*)c->orig_coords.p, (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p,
+                           (double*)c->conf[0].p, (int32_t*)c->oidx[0].p, (int32_t*)c->count.p, LS->win_frame_dev);
     } else if (T) {
         hipLaunchKernelGGL(k_cascade_init_grid, (unsigned)((n0 + 255) / 256), 256, 0, st, *T, (double*)c->orig_coords.p, (double*)c->orig_level.p,
                            (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
@@ -1074,7 +1143,14 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
             // the stage's filter: interpolation_formats[network_serial] (FaceDetectUpdated.py:671, :686)
             const uint64_t key = k == 0 && T ? key_of(T, sizeof *T) : 0;
             const double* dang = k == 0 ? nullptr : (const double*)c->neg.p;
-            const int rc = FS ? hg::patcher_extract_frames(c->patcher, key, FS->n0, c->interp[S.serial], frame_dev, FS->n_frames, FS->stride, frame_h, frame_w, ld,
+            hg::FrameList fl{};
+            if (LS) {
+                fl = LS->fl;
+                if (k != 0) fl.key = 0;      // the concatenated grids are the first stage's boxes only
+            }
+            const int rc = LS ? hg::patcher_extract_frame_list(c->patcher, fl, c->interp[S.serial], (const double*)c->coords[cur].p, dang,
+                                                               (const int32_t*)c->oidx[cur].p, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
+                         : FS ? hg::patcher_extract_frames(c->patcher, key, FS->n0, c->interp[S.serial], frame_dev, FS->n_frames, FS->stride, frame_h, frame_w, ld,
                                                            (const double*)c->coords[cur].p, dang, (const int32_t*)c->oidx[cur].p, (int)FS->n0, n_bound, c->w,
                                                            c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
                               : hg::patcher_extract(c->patcher, key, c->interp[S.serial], frame_dev, HG_U8, frame_h, frame_w, ld,
@@ -1202,7 +1278,7 @@ void gray_frame_of(hg_cascade* c, const void* frame_dev, int frame_h, int frame_
 }
 
 void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
-                    const void*& fr, int& fh, int& fw, int64_t& fld, void* dst = nullptr) {
+                    const void*& fr, int& fh, int& fw, int64_t& fld, void* dst = nullptr, const double* box_dev = nullptr) {
     fr = frame_dev;
     fh = frame_h;
     fw = frame_w;
@@ -1211,7 +1287,7 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
         if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
         check_frame_geometry(frame_h, frame_w, ld, hg::frame_bpp(c->frame_format));
         set_dev(c->device);
-        if (c->pre_src_w != frame_w || c->pre_src_h != frame_h) {
+        if (!box_dev && (c->pre_src_w != frame_w || c->pre_src_h != frame_h)) {      // (box_dev: the whole-frame box of a list's frame, kept with the list)
             const double box[4] = {0.0, 0.0, (double)frame_w, (double)frame_h};
             c->pre_box.upload(box, sizeof box);
             c->pre_src_w = frame_w;
@@ -1233,7 +1309,7 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
         }
         const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
         if (hg::patcher_extract_format(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), c->frame_format, frame_dev, frame_h, frame_w, ld,
-                                       (const double*)c->pre_box.p, 1, prescale_w, prescale_h, dst, HG_U8, (int64_t)prescale_w * prescale_h,
+                                       box_dev ? box_dev : (const double*)c->pre_box.p, 1, prescale_w, prescale_h, dst, HG_U8, (int64_t)prescale_w * prescale_h,
                                        stream) != HG_OK)
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         fr = dst;
@@ -1295,6 +1371,89 @@ void split_by_frame(int32_t* orig_index, int64_t n, int64_t n0, int n_frames, in
         const int fi = (int)(orig_index[i] / n0);
         while (f < fi && f < n_frames) frame_first[++f] = (int32_t)i;
         orig_index[i] = (int32_t)(orig_index[i] - (int64_t)fi * n0);
+    }
+    while (f < n_frames) frame_first[++f] = (int32_t)n;
+}
+
+// ---- a list of frames of different sizes through one pooled pass (include/higsfa.h, hg_cascade_detect_frame_list_device) -----------
+// What both list entries refuse, before anything is launched or written, and the layout of the list (hg_frame_list.hpp)
+// e (nullable): the eye handle of the faces entry, whose patches are rotated windows too
+hg::ListLayout check_frame_list(const hg_cascade* c, const hg_eyes* e, const hg_cascade_frame* frames, int n_frames, int64_t out_cap, const int32_t* frame_first) {
+    if (!c || !frames || !frame_first) hg::fail(HG_ERR_ARG, "null argument");
+    if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
+    // a stage behind the first that extracts (detect_impl's skip_extract) with NEAREST, or a NEAREST eye step, cuts rotated NEAREST windows:
+    // a frame outside PIL's fixed-point range is refused here, not by the patcher in the middle of the stage loop
+    bool rotated_nearest = e && hg::eyes_filter(e) == HG_FILTER_NEAREST;
+    for (size_t k = 1; k < c->stages.size(); ++k)
+        if (c->stages[k].flow && c->stages[k - 1].type != HG_STAGE_DISC && c->interp[c->stages[k].serial] == HG_FILTER_NEAREST) rotated_nearest = true;
+    hg::ListLayout L;
+    const std::string why = hg::list_layout(frames, n_frames, hg::frame_bpp(c->frame_format), &L, rotated_nearest);
+    if (!why.empty()) hg::fail(HG_ERR_ARG, "%s", why.c_str());
+    return L;
+}
+
+// The grey frames the list's stage loop reads and everything it needs on the device.  Every frame goes through prescale_frame — the code
+// a single frame runs, one pass per frame, each to its own size — into its slot of list_gray (16-byte aligned); a grey frame that needs
+// no prescale is read where it is.  `desc` (the caller's, alive while R is used): the descriptors, sent to the device in stream order.
+void list_frames(hg_cascade* c, const hg_cascade_frame* frames, int n_frames, const hg::ListLayout& L, void* stream, std::vector<hg::FrameDesc>& desc,
+                 ListRun& R) {
+    set_dev(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t total = L.first[(size_t)n_frames];
+    const size_t n_grids = L.grid_frame.size();
+    const size_t off_box = n_grids * sizeof(LevelTable), off_grid = off_box + (size_t)n_frames * 32, meta_bytes = off_grid + (size_t)n_frames * 4;
+    if (c->list_key != L.key || c->list_meta.bytes < meta_bytes) {      // what depends on the list's geometry alone: once per list, not per call
+        std::vector<char> meta(meta_bytes);
+        for (size_t g = 0; g < n_grids; ++g) {
+            const hg_cascade_frame& F = frames[L.grid_frame[g]];
+            const LevelTable T = make_level_table(F.levels, F.n_levels);
+            memcpy(meta.data() + g * sizeof(LevelTable), &T, sizeof T);
+        }
+        for (int f = 0; f < n_frames; ++f) {
+            const double box[4] = {0.0, 0.0, (double)frames[f].frame_w, (double)frames[f].frame_h};
+            memcpy(meta.data() + off_box + (size_t)f * 32, box, 32);
+            memcpy(meta.data() + off_grid + (size_t)f * 4, &L.grid[(size_t)f], 4);
+        }
+        HG_HIP(hipStreamSynchronize(st));      // nothing of an earlier list may still read the buffer
+        c->list_key = 0;
+        c->list_meta.upload(meta.data(), meta_bytes);
+        c->list_key = L.key;
+    }
+    size_t gray = 0;
+    std::vector<size_t> slot((size_t)n_frames, 0);
+    for (int f = 0; f < n_frames; ++f) {
+        const bool pre = frames[f].prescale_w > 0;
+        if (!pre && c->frame_format == HG_FRAME_L) continue;
+        slot[(size_t)f] = gray;
+        gray += ((size_t)L.gw[(size_t)f] * L.gh[(size_t)f] + 15) & ~(size_t)15;
+    }
+    c->list_gray.alloc(gray);
+    c->list_desc.alloc((size_t)n_frames * sizeof(hg::FrameDesc));
+    c->list_win.alloc((size_t)total * 4);
+    desc.resize((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        const hg_cascade_frame& F = frames[f];
+        const void* one;
+        int fh, fw;
+        int64_t fld;
+        prescale_frame(c, F.frame_dev, F.frame_h, F.frame_w, F.ld, F.prescale_w, F.prescale_h, stream, one, fh, fw, fld, (char*)c->list_gray.p + slot[(size_t)f],
+                       (const double*)((const char*)c->list_meta.p + off_box) + (size_t)f * 4);
+        desc[(size_t)f] = hg::FrameDesc{(const uint8_t*)one, fld, fw, fh, L.first[(size_t)f], L.tab_row[(size_t)f]};
+    }
+    hg::put_frame_descs(desc.data(), n_frames, (hg::FrameDesc*)c->list_desc.p, st);
+    R.fl = hg::FrameList{desc.data(), (const hg::FrameDesc*)c->list_desc.p, n_frames, (const int32_t*)c->list_win.p, total, L.key, L.tab_rows};
+    R.tables_dev = (const LevelTable*)c->list_meta.p;
+    R.grid_of_dev = (const int32_t*)((const char*)c->list_meta.p + off_grid);
+    R.win_frame_dev = (int32_t*)c->list_win.p;
+}
+
+// detect_impl's survivors of a list, as the caller gets them (split_by_frame with first[] in place of f n0)
+void split_by_list(int32_t* orig_index, int64_t n, const std::vector<int32_t>& first, int n_frames, int32_t* frame_first) {
+    int f = 0;
+    frame_first[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        while (f + 1 < n_frames && orig_index[i] >= first[(size_t)f + 1]) frame_first[++f] = (int32_t)i;
+        orig_index[i] -= first[(size_t)f];
     }
     while (f < n_frames) frame_first[++f] = (int32_t)n;
 }
@@ -1411,6 +1570,50 @@ int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void*
         hg::eyes_frames_tail(e, fr, n_frames, FS.stride, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
                              (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, n0, n, out_rows, out_cap, frame_first, n_before_purge,
                              (hipStream_t)stream);
+    });
+}
+
+int hg_cascade_detect_frame_list_device(hg_cascade* c, const hg_cascade_frame* frames, int n_frames, double* out_coords, double* out_angles,
+                                        int32_t* out_orig_index, double* out_confidence, int64_t out_cap, int32_t* frame_first, int32_t* stage_counts,
+                                        int64_t* rows_executed, void* stream) {
+    return guarded([&] {
+        const hg::ListLayout L = check_frame_list(c, nullptr, frames, n_frames, out_cap, frame_first);
+        const int64_t total = L.first[(size_t)n_frames];
+        std::vector<hg::FrameDesc> desc;
+        ListRun R{};
+        list_frames(c, frames, n_frames, L, stream, desc, R);
+        const FrameStack FS{n_frames, 0, 0, &R};
+        std::vector<int32_t> own_index;      // the frame of a survivor is read off its index: fetched even if the caller does not want it
+        if (!out_orig_index) {
+            own_index.resize((size_t)std::min<int64_t>(out_cap, total));
+            out_orig_index = own_index.data();
+        }
+        int64_t n = 0;
+        detect_impl(c, desc[0].px, desc[0].h, desc[0].w, desc[0].ld, nullptr, nullptr, nullptr, total, out_coords, out_angles, out_orig_index, out_confidence,
+                    out_cap, &n, stage_counts, rows_executed, stream, nullptr, nullptr, &FS);
+        split_by_list(out_orig_index, n, L.first, n_frames, frame_first);
+    });
+}
+
+// the list's pooled stage loop, then the eye step on ALL survivors as one batch, every eye row cut from its face's own grey frame, and
+// the purge per frame (hg::eyes_frame_list_tail)
+int hg_cascade_detect_faces_frame_list_device(hg_cascade* c, hg_eyes* e, const hg_cascade_frame* frames, int n_frames, double* out_rows, int64_t out_cap,
+                                              int32_t* frame_first, int32_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
+    return guarded([&] {
+        if (!e) hg::fail(HG_ERR_ARG, "null argument");
+        const hg::ListLayout L = check_frame_list(c, e, frames, n_frames, out_cap, frame_first);
+        if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
+        const int64_t total = L.first[(size_t)n_frames];
+        std::vector<hg::FrameDesc> desc;
+        ListRun R{};
+        list_frames(c, frames, n_frames, L, stream, desc, R);
+        const FrameStack FS{n_frames, 0, 0, &R};
+        int64_t n = 0;
+        int cur = 0;
+        detect_impl(c, desc[0].px, desc[0].h, desc[0].w, desc[0].ld, nullptr, nullptr, nullptr, total, nullptr, nullptr, nullptr, nullptr, total, &n, stage_counts,
+                    rows_executed, stream, &cur, nullptr, &FS);
+        hg::eyes_frame_list_tail(e, R.fl, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p,
+                                 (const int32_t*)c->oidx[cur].p, n, out_rows, out_cap, frame_first, n_before_purge, (hipStream_t)stream);
     });
 }
 

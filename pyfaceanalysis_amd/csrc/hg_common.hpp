@@ -182,6 +182,31 @@ int patcher_extract(hg_patcher* p, uint64_t key, int filter, const void* frame_d
 int patcher_extract_frames(hg_patcher* p, uint64_t key, int64_t tab_n, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h,
                            int frame_w, int64_t ld, const double* boxes_dev, const double* delta_angs_dev, const int32_t* row_frame_dev, int row_div, int64_t n,
                            int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
+// hg_extract.hip: the same dispatch over a LIST of grey uint8 frames of DIFFERENT sizes (hg_patcher_extract_frame_list_device, and the
+// list pass of hg_cascade.hip / hg_eyes.hip).  One descriptor per frame, the same struct on the host and in the device table.
+struct FrameDesc {
+    const uint8_t* px;      // the frame's first pixel (device memory)
+    int64_t ld;             // row stride
+    int32_t w, h;
+    int32_t first;          // the frame's first original window in the concatenated grids (0 where the caller has none)
+    int32_t tab_row;        // the first row of the frame's grid in the list's shared first-stage tables
+};
+struct FrameList {
+    const FrameDesc* host;           // n_frames descriptors, read before the call returns
+    const FrameDesc* dev;            // the same table on the device, or nullptr: the call sends `host` itself, in stream order
+    int n_frames;
+    const int32_t* win_frame_dev;    // original window -> frame (n_windows entries): row_frame_dev then holds original-window indices;
+    int64_t n_windows;               //   nullptr: row_frame_dev holds the frame index of every row
+    // key != 0 (never with angles): boxes_dev holds the n_windows concatenated grids themselves, row i = original window i.  Their
+    // tables — tab_rows rows, frame f's from tab_row on, shared by frames of equal grids — are kept in ONE buffer for the whole call
+    // (not in the keyed ring, which has four slots and evicts) and across calls while the key, a key of the whole list, stays.
+    uint64_t key;
+    int64_t tab_rows;
+};
+// descriptors in host memory -> a device table, carried in kernel arguments (consumed at the launch, ordered on the stream)
+void put_frame_descs(const FrameDesc* host, int n_frames, FrameDesc* dev, hipStream_t st);
+int patcher_extract_frame_list(hg_patcher* p, const FrameList& fl, int filter, const double* boxes_dev, const double* delta_angs_dev,
+                               const int32_t* row_frame_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
 // hg_extract.hip: NEAREST, unrotated windows from a frame of format HG_FRAME_* (ld_bytes: row stride in bytes), the tables kept under
 // `key` as above.  What hg_patcher_extract_format_device (key = 0) and the cascade's prescale of a colour frame call.
 int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,

@@ -33,6 +33,7 @@
 
 #include "hg_common.hpp"
 #include "hg_frame_format.hpp"
+#include "hg_frame_list.hpp"
 
 struct hg_patcher {
     int device = -1;
@@ -49,6 +50,12 @@ struct hg_patcher {
     hg::DevBuf ftabs, frot;     // BILINEAR / BICUBIC: coordinate tables and rotation matrices of unkeyed calls
     Keyed keyed[4];
     int keyed_next = 0;
+    // a frame list (hg::patcher_extract_frame_list): the descriptor table of a call that brings its descriptors in host memory, and the
+    // shared first-stage tables of the whole list — one buffer that lives for the call, kept while the list's key and shape stay
+    hg::DevBuf list_desc, list_tabs;
+    uint64_t list_key = 0;
+    int64_t list_rows = 0;
+    int list_w = 0, list_h = 0, list_filtered = 0;
     void* resample = nullptr;   // hg_patcher_resize_device: the tables and the intermediate image (hg_resample.hip owns and frees it)
     void* normalize = nullptr;  // hg_patcher_normalize_device: face records and the staged rectangles (hg_normalize.hip owns and frees it)
     ~hg_patcher() {
@@ -149,11 +156,60 @@ __device__ __forceinline__ bool frame_of(int64_t b, P& frame, int64_t& tb, const
     return in_stack;
 }
 
+// Windows from a LIST of grey uint8 frames of different sizes (hg_patcher_extract_frame_list_device, hg_common.hpp): the third form of
+// the optional last argument.  The frame geometry is no longer the kernel's arguments but a device table of one descriptor per frame,
+// and per box (uniform per workgroup) frame_of() replaces the frame pointer and the table row, geo() the kernels' locals ld, fw and fh (one descriptor load, returned by value),
+// by the box's frame's.  Without a list geo() returns the kernel's own argument: the other instantiations stay the code they were.  The
+// kernel's own arguments are frame 0's: a box whose frame lies outside [0, n_frames) forms no address from its index, keeps frame 0's
+// geometry through the kernels' clamped addresses and is masked to 0, as in the stack form.
+// The frame of box b: row_frame[b] itself (win_frame == nullptr), or win_frame[row_frame[b]] where row_frame holds the cascade's
+// original-window indices (the array k_cascade_init_list writes, n_windows entries).  shared_tabs: the unrotated boxes are the
+// concatenated grids of the list and original window r of frame f reads table row tab_row[f] + (r - first[f]) of one call-long buffer,
+// which frames of equal grids share; otherwise a table per box.
+struct FrameListSel {
+    const hg::FrameDesc* desc;
+    const int32_t* row_frame;
+    const int32_t* win_frame;
+    int32_t n_frames, n_windows, shared_tabs, pad;
+};
+__device__ __forceinline__ int32_t list_frame_of(int64_t b, const FrameListSel& s, int32_t& r) {
+    r = s.row_frame[b];
+    if (!s.win_frame) return r;
+    return r >= 0 && r < s.n_windows ? s.win_frame[r] : -1;
+}
+template <typename P>
+__device__ __forceinline__ bool frame_of(int64_t b, P& frame, int64_t& tb, const FrameListSel& s) {
+    int32_t r;
+    const int32_t f = list_frame_of(b, s, r);
+    const bool in_list = f >= 0 && f < s.n_frames;
+    if (s.shared_tabs) tb = 0;      // (a box outside the list: frame 0's first table row, inside frame 0 whatever it holds)
+    if (in_list) {
+        const hg::FrameDesc d = s.desc[f];
+        frame = (P)d.px;
+        if (s.shared_tabs) tb = (int64_t)d.tab_row + (r - d.first);
+    }
+    return in_list;
+}
+// ld / fw / fh of box b's frame, by value: the kernel's own arguments `g`, or, under a list, ONE load of the box's descriptor
+struct BoxGeo {
+    int64_t ld;
+    int fw, fh;
+};
+__device__ __forceinline__ BoxGeo geo(int64_t, BoxGeo g) { return g; }
+__device__ __forceinline__ BoxGeo geo(int64_t, BoxGeo g, const FrameSel&) { return g; }
+__device__ __forceinline__ BoxGeo geo(int64_t b, BoxGeo g, const FrameListSel& s) {
+    int32_t r;
+    const int32_t f = list_frame_of(b, s, r);
+    if (!(f >= 0 && f < s.n_frames)) return g;
+    const hg::FrameDesc d = s.desc[f];
+    return BoxGeo{d.ld, d.w, d.h};
+}
+
 // One workgroup per (group of output rows, box): no index divisions, the row's source line and the column table are
 // read once; four output pixels per thread and one vector store when the output is uint8.  ld_bytes: the frame's row stride in
 // bytes (a colour frame's rows need not be a whole number of pixels apart).
 template <typename FT, typename OT, typename... SEL>
-__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame0, int64_t ld_bytes, const int32_t* __restrict__ tabs, int64_t n,
+__global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ frame0, int64_t ld_bytes0, const int32_t* __restrict__ tabs, int64_t n,
                                                         int w, int h, OT* __restrict__ out, int64_t ldo, SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;     // blockDim.y output rows per workgroup
     if (y >= h) return;
@@ -161,6 +217,7 @@ __global__ void __launch_bounds__(256) k_extent_gather(const FT* __restrict__ fr
         const FT* frame = frame0;
         int64_t tb = b;
         const bool in_stack = frame_of(b, frame, tb, sel...);
+        const int64_t ld_bytes = geo(b, BoxGeo{ld_bytes0, 0, 0}, sel...).ld;      // (the tables hold the frame's limits: this kernel reads its row stride only)
         const int32_t* t = tabs + tb * (w + h);
         const int ys = in_stack ? t[w + y] : -1;
         const FT* src = (const FT*)((const char*)frame + (int64_t)(ys >= 0 ? ys : 0) * ld_bytes);
@@ -246,7 +303,7 @@ __global__ void __launch_bounds__(256) k_frame_to_gray(const uint8_t* __restrict
 // four byte loads; one 16-byte store per row.  5 memory instructions per 16 pixels.  Same bytes: every pixel is still
 // frame[ytab[y]][xtab[x]] or 0.
 template <typename... SEL>
-__global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __restrict__ frame0, int64_t ld, int fw, const int32_t* __restrict__ tabs,
+__global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __restrict__ frame0, int64_t ld0, int fw0, const int32_t* __restrict__ tabs,
                                                              int64_t n, int w, int h, uint8_t* __restrict__ out, int64_t ldo, int rows_per_wg, SEL... sel) {
     const int tpr = w >> 4;                                   // threads per output row (a power of two, <= 256)
     const int tx = threadIdx.x & (tpr - 1), ty = threadIdx.x / tpr, rows_per_pass = 256 / tpr;
@@ -255,6 +312,9 @@ __global__ void __launch_bounds__(256) k_extent_gather_u8x16(const uint8_t* __re
         const uint8_t* frame = frame0;
         int64_t tb = b;
         const bool in_stack = frame_of(b, frame, tb, sel...);      // (a box outside the stack: every row below reads as "outside the frame")
+        const BoxGeo g = geo(b, BoxGeo{ld0, fw0, 0}, sel...);
+        const int64_t ld = g.ld;
+        const int fw = g.fw;
         const int32_t* t = tabs + tb * (w + h);
         int xs[16];
 #pragma unroll
@@ -484,7 +544,7 @@ __device__ __forceinline__ void gather_rot_row(const FT* __restrict__ frame, int
 // Rotated windows, tables from memory (k_extent_tables, k_rot_coefs): the frame (<= a few MB) sits in L2; the access pattern is a
 // rotated scan line.
 template <typename FT, typename OT, typename... SEL>
-__global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict__ frame0, int64_t ld, int fw, int fh, const int32_t* __restrict__ tabs,
+__global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict__ frame0, int64_t ld0, int fw0, int fh0, const int32_t* __restrict__ tabs,
                                                             const RotCoef* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo,
                                                             SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;
@@ -493,13 +553,14 @@ __global__ void __launch_bounds__(256) k_extent_gather_rot(const FT* __restrict_
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {
         if constexpr (sizeof...(SEL) == 0) {
             const RotCoef rc = rot[b];
-            gather_rot_row<FT, OT>(frame0, ld, fw, fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
+            gather_rot_row<FT, OT>(frame0, ld0, fw0, fh0, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
         } else {
             const FT* frame = frame0;
             int64_t tb = b;      // (rotated boxes: a table per box)
             RotCoef rc = rot[b];
             if (!frame_of(b, frame, tb, sel...)) rc.mode = 3;      // a box outside the stack: as outside the fixed-point range, the window stays 0
-            gather_rot_row<FT, OT>(frame, ld, fw, fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
+            const BoxGeo g = geo(b, BoxGeo{ld0, fw0, fh0}, sel...);
+            gather_rot_row<FT, OT>(frame, g.ld, g.fw, g.fh, tabs + b * (w + h), rc, y, w, out + b * ldo + (int64_t)y * w, packed, threadIdx.x, blockDim.x);
         }
     }
 }
@@ -537,6 +598,56 @@ __global__ void k_filter_tables(const double* __restrict__ boxes, int64_t n, int
     }
 }
 
+// The table builders of a frame LIST: k_extent_tables / k_filter_tables with the frame's size taken per box from the box's descriptor
+// (the entries and the rotation records are functions of that size).  A box outside the list gets the size 0 x 0: every entry "outside".
+__device__ __forceinline__ void list_size_of(int64_t b, const FrameListSel& s, int& fw, int& fh) {
+    int32_t r;
+    const int32_t f = list_frame_of(b, s, r);
+    fw = fh = 0;
+    if (f >= 0 && f < s.n_frames) {
+        fw = s.desc[f].w;
+        fh = s.desc[f].h;
+    }
+}
+__global__ void k_extent_tables_list(const double* __restrict__ boxes, int64_t n, int w, int h, int32_t* __restrict__ tabs, const double* __restrict__ angs,
+                                     RotCoef* __restrict__ rot, FrameListSel s) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wh = w + h;
+    if (id >= n * wh) return;
+    const int64_t b = id / wh;
+    const int e = (int)(id - b * wh);
+    int fw, fh;
+    list_size_of(b, s, fw, fh);
+    tabs[b * wh + e] = extent_entry(boxes + b * 4, e, w, h, fw, fh);
+    if (angs && e == 0) rot_coef_store(boxes, angs, b, fw, fh, rot);
+}
+__global__ void k_filter_tables_list(const double* __restrict__ boxes, int64_t n, int w, int h, FiltEnt* __restrict__ tabs, const double* __restrict__ angs,
+                                     RotAff* __restrict__ rot, FrameListSel s) {
+    const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int wh = w + h;
+    if (id >= n * wh) return;
+    const int64_t b = id / wh;
+    const int e = (int)(id - b * wh);
+    int fw, fh;
+    list_size_of(b, s, fw, fh);
+    tabs[b * wh + e] = filter_entry(boxes + b * 4, e, w, h, fw, fh);
+    if (angs && e == 0) {
+        RotAff ra{};
+        ra.rotated = rot_matrix(boxes, angs, b, ra.m) ? 1 : 0;
+        rot[b] = ra;
+    }
+}
+
+// The descriptors of a frame list, from the launch's own arguments into the device table (hg::put_frame_descs)
+constexpr int kDescChunk = 64;
+struct DescChunk {
+    hg::FrameDesc d[kDescChunk];
+};
+__global__ void k_put_descs(DescChunk c, int n, hg::FrameDesc* __restrict__ dst) {
+    const int i = threadIdx.x;
+    if (i < n) dst[i] = c.d[i];
+}
+
 // Pixel (xr, yr) of frame.rotate(angle, F, center): affine_transform with the rotation's matrix, then the filter on the frame
 template <int F>
 __device__ __forceinline__ uint8_t rot_pixel(const uint8_t* __restrict__ frame, int64_t ld, int W, int H, const double* m, int xr, int yr) {
@@ -549,7 +660,7 @@ __device__ __forceinline__ uint8_t rot_pixel(const uint8_t* __restrict__ frame, 
 
 // Unrotated windows: a workgroup per (group of output rows, box), a thread per output pixel
 template <int F, typename OT, typename... SEL>
-__global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict__ frame0, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+__global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict__ frame0, int64_t ld0, int fw0, int fh0, const FiltEnt* __restrict__ tabs,
                                                         int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo, SEL... sel) {
     const int y = blockIdx.x * blockDim.y + threadIdx.y;
     if (y >= h) return;
@@ -557,6 +668,9 @@ __global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict
         const uint8_t* frame = frame0;
         int64_t tb = b;
         const bool in_stack = frame_of(b, frame, tb, sel...);
+        const BoxGeo g = geo(b, BoxGeo{ld0, fw0, fh0}, sel...);
+        const int64_t ld = g.ld;
+        const int fw = g.fw, fh = g.fh;
         const FiltEnt* t = tabs + tb * (w + h);
         FiltEnt ey = t[w + y];
         if (!in_stack) ey.i = kFiltOutside;      // a box outside the stack: every row outside the frame
@@ -586,7 +700,7 @@ __global__ void __launch_bounds__(256) k_filter_gather(const uint8_t* __restrict
 //     at the same time and every one of them reads the frame from L2, where the staged tile reads LDS.
 constexpr int kFiltTile = 16, kFiltPatch = 256 * 16 * 2;
 template <int F, typename OT, typename... SEL>
-__global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __restrict__ frame0, int64_t ld, int fw, int fh, const FiltEnt* __restrict__ tabs,
+__global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __restrict__ frame0, int64_t ld0, int fw0, int fh0, const FiltEnt* __restrict__ tabs,
                                                             const RotAff* __restrict__ rot, int64_t n, int w, int h, OT* __restrict__ out, int64_t ldo,
                                                             int tiles_x, SEL... sel) {
     constexpr int LO = F == HG_FILTER_BICUBIC ? 1 : 0, HI = F == HG_FILTER_BICUBIC ? 2 : 1, TAPS = (LO + HI + 1) * (LO + HI + 1);
@@ -599,11 +713,17 @@ __global__ void __launch_bounds__(256) k_filter_gather_rot(const uint8_t* __rest
     const bool live = ox < w && oy < h;
     auto clip = [](int v, int lim) { return v < 0 ? 0 : v < lim ? v : lim - 1; };
     const uint8_t* frame = frame0;
+    int64_t ld = ld0;
+    int fw = fw0, fh = fh0;
     auto frame_tap = [&](int xc, int yc) { return (double)frame[(int64_t)yc * ld + xc]; };
     for (int64_t b = blockIdx.y; b < n; b += gridDim.y) {      // (every thread of the workgroup takes every trip: barriers below)
         int64_t tb = b;      // (rotated boxes: a table per box)
         frame = frame0;
-        const bool in_stack = frame_of(b, frame, tb, sel...);      // uniform per workgroup; a box outside the stack: no entry inside the frame
+        const bool in_stack = frame_of(b, frame, tb, sel...);
+        const BoxGeo g = geo(b, BoxGeo{ld0, fw0, fh0}, sel...);
+        ld = g.ld;      // (frame_tap reads frame and ld by reference)
+        fw = g.fw;
+        fh = g.fh;      // uniform per workgroup; a box outside the stack: no entry inside the frame
         const FiltEnt* t = tabs + b * (w + h);
         FiltEnt ex, ey;
         ex.i = ey.i = kFiltOutside;
@@ -1094,7 +1214,132 @@ int patcher_extract_frames(hg_patcher* p, uint64_t key, int64_t tab_n, int filte
         HG_HIP(hipGetLastError());
     });
 }
+void put_frame_descs(const FrameDesc* host, int n_frames, FrameDesc* dev, hipStream_t st) {
+    for (int at = 0; at < n_frames; at += kDescChunk) {
+        DescChunk c{};
+        const int m = std::min(kDescChunk, n_frames - at);
+        memcpy(c.d, host + at, (size_t)m * sizeof(FrameDesc));
+        hipLaunchKernelGGL(k_put_descs, 1, kDescChunk, 0, st, c, m, dev + at);
+    }
+    HG_HIP(hipGetLastError());
+}
+
+// The sibling of patcher_extract_frames for a LIST of grey uint8 frames of different sizes (hg_common.hpp, FrameList): the same kernels
+// instantiated with a FrameListSel, the tables of k_extent_tables_list / k_filter_tables_list (a table per box, its frame's size per
+// box), or, for the concatenated grids of a cascade's first stage (fl.key), the existing table kernels once per DISTINCT grid into the
+// list's own call-long buffer.  Every refusal comes before the handle or a data pointer is dereferenced and before anything is launched.
+int patcher_extract_frame_list(hg_patcher* p, const FrameList& fl, int filter, const double* boxes_dev, const double* delta_angs_dev,
+                               const int32_t* row_frame_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    return guarded([&] {
+        check_filter(filter, HG_U8);
+        if (!p || !fl.host || !boxes_dev || !row_frame_dev || !out_dev) fail(HG_ERR_ARG, "null pointer");
+        if (fl.n_frames < 1 || fl.n_frames > HG_MAX_STACK_FRAMES) fail(HG_ERR_ARG, "%d frames in a list (1..%d)", fl.n_frames, HG_MAX_STACK_FRAMES);
+        for (int f = 0; f < fl.n_frames; ++f) {
+            const FrameDesc& d = fl.host[f];
+            std::string bad = list_frame_refusal(f, d.px, d.h, d.w, d.ld, 1);      // (hg_frame_list.hpp: one text for the patcher and the cascade)
+            if (bad.empty() && filter == HG_FILTER_NEAREST && delta_angs_dev) bad = list_rotated_refusal(f, d.w, d.h);
+            if (!bad.empty()) fail(HG_ERR_ARG, "%s", bad.c_str());
+        }
+        if (out_dtype != HG_U8 && out_dtype != HG_F32 && out_dtype != HG_F64) fail(HG_ERR_ARG, "bad output dtype");
+        if (out_w <= 0 || out_h <= 0 || out_w > 4096 || out_h > 4096) fail(HG_ERR_ARG, "bad sub-image size");
+        if (n < 0 || ldo < (int64_t)out_w * out_h) fail(HG_ERR_ARG, "bad batch geometry");
+        if (fl.win_frame_dev && (fl.n_windows < 1 || fl.n_windows > 0x7fffffffll)) fail(HG_ERR_ARG, "bad window count of the list");
+        const bool shared = fl.key != 0 && !delta_angs_dev;
+        if (shared && (!fl.win_frame_dev || n != fl.n_windows || fl.tab_rows < 1 || fl.tab_rows > n)) fail(HG_ERR_ARG, "bad shared tables of the list");
+        if (n == 0) return;
+        HG_HIP(hipSetDevice(p->device));
+        hipStream_t st = (hipStream_t)stream;
+        const int wh = out_w + out_h;
+        if ((n * wh + 255) / 256 > 0x7fffffffll) fail(HG_ERR_ARG, "too many boxes");
+        const FrameDesc* desc = fl.dev;
+        if (!desc) {
+            p->list_desc.alloc((size_t)fl.n_frames * sizeof(FrameDesc));
+            put_frame_descs(fl.host, fl.n_frames, (FrameDesc*)p->list_desc.p, st);
+            desc = (const FrameDesc*)p->list_desc.p;
+        }
+        const FrameListSel sel{desc, row_frame_dev, fl.win_frame_dev, fl.n_frames, (int32_t)fl.n_windows, shared ? 1 : 0, 0};
+        const FrameDesc& d0 = fl.host[0];      // the kernels' own frame arguments: frame 0's (what a box outside the list keeps)
+        const bool filtered = filter != HG_FILTER_NEAREST;
+        const void* shared_tabs = nullptr;
+        if (shared) {
+            const size_t ent = filtered ? sizeof(FiltEnt) : 4;
+            if (!(p->list_key == fl.key && p->list_rows == fl.tab_rows && p->list_w == out_w && p->list_h == out_h && p->list_filtered == (int)filtered)) {
+                const size_t need = (size_t)fl.tab_rows * wh * ent;
+                if (p->list_tabs.p && need > p->list_tabs.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
+                p->list_tabs.alloc(need);
+                p->list_key = 0;      // (until every launch below is enqueued)
+                std::vector<char> built((size_t)fl.tab_rows, 0);
+                for (int f = 0; f < fl.n_frames; ++f) {
+                    const FrameDesc& d = fl.host[f];
+                    const int64_t n0 = (f + 1 < fl.n_frames ? fl.host[f + 1].first : fl.n_windows) - d.first;
+                    if (d.first < 0 || n0 < 0 || d.tab_row < 0 || d.tab_row + n0 > fl.tab_rows) fail(HG_ERR_ARG, "frame %d of the list: bad table rows", f);
+                    if (n0 == 0 || built[(size_t)d.tab_row]) continue;      // (an equal grid earlier in the list: its rows serve this frame too)
+                    built[(size_t)d.tab_row] = 1;
+                    const unsigned blocks = (unsigned)((n0 * wh + 255) / 256);
+                    if (filtered)
+                        hipLaunchKernelGGL(k_filter_tables, blocks, 256, 0, st, boxes_dev + (int64_t)d.first * 4, n0, out_w, out_h, d.w, d.h,
+                                           (FiltEnt*)p->list_tabs.p + (int64_t)d.tab_row * wh, (const double*)nullptr, (RotAff*)nullptr);
+                    else
+                        hipLaunchKernelGGL(k_extent_tables, blocks, 256, 0, st, boxes_dev + (int64_t)d.first * 4, n0, out_w, out_h, d.w, d.h,
+                                           (int32_t*)p->list_tabs.p + (int64_t)d.tab_row * wh, (const double*)nullptr, (RotCoef*)nullptr);
+                }
+                HG_HIP(hipGetLastError());
+                p->list_key = fl.key; p->list_rows = fl.tab_rows; p->list_w = out_w; p->list_h = out_h; p->list_filtered = (int)filtered;
+            }
+            shared_tabs = p->list_tabs.p;
+        }
+        const unsigned tab_blocks = (unsigned)((n * wh + 255) / 256);
+        if (!filtered) {
+            if (delta_angs_dev) {
+                p->tabs.alloc((size_t)n * wh * 4);
+                p->rot.alloc((size_t)n * sizeof(RotCoef));
+                hipLaunchKernelGGL(k_extent_tables_list, tab_blocks, 256, 0, st, boxes_dev, n, out_w, out_h, (int32_t*)p->tabs.p, delta_angs_dev, (RotCoef*)p->rot.p, sel);
+                launch_gather_rot<uint8_t>(d0.px, d0.ld, d0.w, d0.h, (const int32_t*)p->tabs.p, (const RotCoef*)p->rot.p, n, out_w, out_h, out_dev, out_dtype, ldo,
+                                           st, sel);
+            } else {
+                const int32_t* tabs = (const int32_t*)shared_tabs;
+                if (!tabs) {
+                    p->tabs.alloc((size_t)n * wh * 4);
+                    hipLaunchKernelGGL(k_extent_tables_list, tab_blocks, 256, 0, st, boxes_dev, n, out_w, out_h, (int32_t*)p->tabs.p, (const double*)nullptr,
+                                       (RotCoef*)nullptr, sel);
+                    tabs = (const int32_t*)p->tabs.p;
+                }
+                launch_gather<uint8_t>(d0.px, d0.ld, d0.w, tabs, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+            }
+        } else {
+            const FiltEnt* tabs = (const FiltEnt*)shared_tabs;
+            const RotAff* rot = nullptr;
+            if (!tabs) {
+                p->ftabs.alloc((size_t)n * wh * sizeof(FiltEnt));
+                if (delta_angs_dev) p->frot.alloc((size_t)n * sizeof(RotAff));
+                hipLaunchKernelGGL(k_filter_tables_list, tab_blocks, 256, 0, st, boxes_dev, n, out_w, out_h, (FiltEnt*)p->ftabs.p, delta_angs_dev,
+                                   delta_angs_dev ? (RotAff*)p->frot.p : nullptr, sel);
+                tabs = (const FiltEnt*)p->ftabs.p;
+                if (delta_angs_dev) rot = (const RotAff*)p->frot.p;
+            }
+            if (filter == HG_FILTER_BILINEAR)
+                launch_filter<HG_FILTER_BILINEAR>(d0.px, d0.ld, d0.w, d0.h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+            else
+                launch_filter<HG_FILTER_BICUBIC>(d0.px, d0.ld, d0.w, d0.h, tabs, rot, n, out_w, out_h, out_dev, out_dtype, ldo, st, sel);
+        }
+        HG_HIP(hipGetLastError());
+    });
+}
 }  // namespace hg
+
+extern "C" int hg_patcher_extract_frame_list_device(hg_patcher* p, int filter, const hg_frame_ref* frames, int n_frames, const double* boxes_dev,
+                                                    const double* delta_angs_dev, const int32_t* row_frame_dev, int64_t n, int out_w, int out_h, void* out_dev,
+                                                    int out_dtype, int64_t ldo, void* stream) {
+    return guarded([&] {
+        if (!frames) hg::fail(HG_ERR_ARG, "null pointer");
+        if (n_frames < 1 || n_frames > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "%d frames in a list (1..%d)", n_frames, HG_MAX_STACK_FRAMES);
+        std::vector<hg::FrameDesc> desc((size_t)n_frames);
+        for (int f = 0; f < n_frames; ++f) desc[(size_t)f] = hg::FrameDesc{(const uint8_t*)frames[f].frame_dev, frames[f].ld, frames[f].frame_w, frames[f].frame_h, 0, 0};
+        const hg::FrameList fl{desc.data(), nullptr, n_frames, nullptr, 0, 0, 0};
+        const int rc = hg::patcher_extract_frame_list(p, fl, filter, boxes_dev, delta_angs_dev, row_frame_dev, n, out_w, out_h, out_dev, out_dtype, ldo, stream);
+        if (rc != HG_OK) hg::fail(rc, "%s", hg_last_error());
+    });
+}
 
 extern "C" int hg_patcher_extract_frames_device(hg_patcher* p, int filter, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
                                                 int64_t ld, const double* boxes_dev, const double* delta_angs_dev, const int32_t* row_frame_dev, int64_t n,

@@ -382,6 +382,33 @@ __global__ void __launch_bounds__(1024) k_frame_segments(const int32_t* __restri
     }
 }
 
+// The two kernels above for a LIST of frames of different sizes (hg_cascade.hip, ListRun): the frame of original window o is
+// win_frame[o], the array k_cascade_init_list wrote (n_windows entries) — no division by a common n0.  An index outside the windows is
+// frame -1 (k_eye_row_frames_list: an all-zero eye row) or ends the segments (k_frame_segments_list), as an index beyond the stack does.
+__global__ void k_eye_row_frames_list(int64_t n, const int32_t* __restrict__ orig_index, const int32_t* __restrict__ win_frame, int n_windows,
+                                      int32_t* __restrict__ row_frame) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t o = orig_index[i];
+    const int32_t f = o >= 0 && o < n_windows ? win_frame[o] : -1;
+    row_frame[i] = f;
+    row_frame[n + i] = f;
+}
+__global__ void __launch_bounds__(1024) k_frame_segments_list(const int32_t* __restrict__ row_src, const int32_t* __restrict__ count,
+                                                              const int32_t* __restrict__ orig_index, const int32_t* __restrict__ win_frame, int n_windows,
+                                                              int n_frames, int32_t* __restrict__ seg_first) {
+    const int cnt = *count;
+    auto frame = [&](int j) -> int {
+        const int32_t o = orig_index[row_src[j]];
+        return o >= 0 && o < n_windows ? win_frame[o] : n_frames;
+    };
+    for (int j = threadIdx.x; j <= cnt; j += blockDim.x) {
+        const int f_prev = j == 0 ? -1 : frame(j - 1);
+        const int f_here = j == cnt ? n_frames : frame(j);
+        for (int f = (f_prev < -1 ? -1 : f_prev) + 1; f <= f_here && f <= n_frames; ++f) seg_first[f] = j;
+    }
+}
+
 // k_purge per frame: workgroup f purges rows [seg_first[f], seg_first[f + 1]).  Frame f's kept rows start at row seg_first[f] + f of
 // `out` and its scratch at 16 (seg_first[f] + f) bytes: every frame has room for its count + 1 rows (the first row appended twice).
 __global__ void __launch_bounds__(1024) k_purge_frames(const double* __restrict__ rows, const int32_t* __restrict__ seg_first, double* __restrict__ out,
@@ -416,6 +443,7 @@ struct EyeFrames {
     int n_frames;
     int64_t stride;
     const int32_t* row_frame;      // 2n entries, on the device
+    const hg::FrameList* list = nullptr;      // a list of frames of different sizes: eye row i is cut from frame list[row_frame[i]] (hg::patcher_extract_frame_list)
 };
 void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles, const double* conf,
               int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st,
@@ -429,7 +457,10 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
     const int64_t wh = (int64_t)c.eye_w * c.eye_h, n2 = 2 * n;
     hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, n_dev, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
     HG_HIP(hipGetLastError());
-    const int rc_x = F ? hg::patcher_extract_frames(e->patcher, 0, 0, e->filter, frame_dev, F->n_frames, F->stride, frame_h, frame_w, ld, (const double*)e->eboxes.p,
+    const int rc_x = F && F->list
+                         ? hg::patcher_extract_frame_list(e->patcher, *F->list, e->filter, (const double*)e->eboxes.p, (const double*)e->dang.p, F->row_frame, n2,
+                                                          c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st)
+                     : F ? hg::patcher_extract_frames(e->patcher, 0, 0, e->filter, frame_dev, F->n_frames, F->stride, frame_h, frame_w, ld, (const double*)e->eboxes.p,
                                                     (const double*)e->dang.p, F->row_frame, 1, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st)
                        : hg_patcher_extract_filter_device(e->patcher, e->filter, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p,
                                                           (const double*)e->dang.p, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st);
@@ -505,6 +536,8 @@ void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int
     *kept_idx = (const int32_t*)e->kept_idx.p;
 }
 
+void frames_tail_read(hg_eyes* e, int n_frames, int64_t n, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
+
 // The tail of hg_cascade_detect_faces_frames_device: the eye step on the n survivors of a STACK of frames as one batch (frame_dev: frame 0
 // of n_frames grey frames, frame_stride bytes apart; survivor i belongs to frame orig_index[i] / n0, the survivors are ordered by frame),
 // the discard and the rows, then the purge PER FRAME; one read-back of the per-frame counts and the rows at the end.
@@ -531,6 +564,45 @@ void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t f
     hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
                        (char*)e->scratch.p);
     HG_HIP(hipGetLastError());
+    frames_tail_read(e, n_frames, n, out_rows, out_cap, frame_first, n_before_purge, st);
+}
+
+// The tail of hg_cascade_detect_faces_frame_list_device: eyes_frames_tail for a LIST of frames of different sizes.  fl: the cascade's
+// list (descriptors on the device, win_frame_dev: the frame of every original window); survivor i belongs to frame
+// win_frame[orig_index[i]], the survivors are ordered by frame.  The eye rows carry their frame index itself.
+void eyes_frame_list_tail(hg_eyes* e, const FrameList& fl, const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n,
+                          double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
+    if (!e || !frame_first || !fl.host || !fl.dev || !fl.win_frame_dev || fl.n_frames < 1) fail(HG_ERR_ARG, "null argument");
+    const int n_frames = fl.n_frames;
+    for (int f = 0; f <= n_frames; ++f) frame_first[f] = 0;
+    for (int f = 0; f < n_frames && n_before_purge; ++f) n_before_purge[f] = 0;
+    if (n == 0) return;
+    e->reserve(n + n_frames);      // (see eyes_frames_tail)
+    e->row_frame.alloc((size_t)n * 2 * 4);
+    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
+    int32_t* seg_first = (int32_t*)e->seg.p;
+    int32_t* seg_kept = seg_first + n_frames + 1;
+    hipLaunchKernelGGL(k_eye_row_frames_list, (unsigned)((n + 255) / 256), 256, 0, st, n, orig_index, fl.win_frame_dev, (int)fl.n_windows, (int32_t*)e->row_frame.p);
+    HG_HIP(hipGetLastError());
+    FrameList rows = fl;      // the eye rows' own reading of the list: a frame index per row, a table per box
+    rows.win_frame_dev = nullptr;
+    rows.n_windows = 0;
+    rows.key = 0;
+    rows.tab_rows = 0;
+    const EyeFrames F{n_frames, 0, (const int32_t*)e->row_frame.p, &rows};
+    const FrameDesc& d0 = fl.host[0];
+    eyes_run(e, d0.px, d0.h, d0.w, d0.ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st, nullptr,
+             (int32_t*)e->row_src.p, &F);
+    hipLaunchKernelGGL(k_frame_segments_list, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, fl.win_frame_dev,
+                       (int)fl.n_windows, n_frames, seg_first);
+    hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
+                       (char*)e->scratch.p);
+    HG_HIP(hipGetLastError());
+    frames_tail_read(e, n_frames, n, out_rows, out_cap, frame_first, n_before_purge, st);
+}
+
+// The one read-back of a pooled tail (eyes_frames_tail, eyes_frame_list_tail): the per-frame counts and the purged rows, to the caller's layout
+void frames_tail_read(hg_eyes* e, int n_frames, int64_t n, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
     std::vector<int32_t> seg((size_t)2 * n_frames + 1);
     std::vector<double> purged((size_t)(n + n_frames) * 10);
     HG_HIP(hipMemcpyAsync(seg.data(), e->seg.p, seg.size() * 4, hipMemcpyDeviceToHost, st));
@@ -601,6 +673,7 @@ void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** 
 }
 
 int eyes_device(const hg_eyes* e) { return e ? e->device : -1; }
+int eyes_filter(const hg_eyes* e) { return e ? e->filter : HG_FILTER_NEAREST; }
 }  // namespace hg
 
 extern "C" {

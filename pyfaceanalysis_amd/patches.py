@@ -87,6 +87,21 @@ class Patcher(object):
             C.c_void_p(delta_angs_ptr) if delta_angs_ptr else None, C.c_void_p(row_frame_ptr), int(n), w, h, C.c_void_p(out_ptr),
             _capi.np_dtype_code(out_dtype), int(ldo), C.c_void_p(stream)))
 
+    def extract_frame_list_device(self, frames, boxes_ptr, row_frame_ptr, n, out_size, out_ptr, out_dtype, ldo, stream=0, delta_angs_ptr=None,
+                                  interpolation=0):
+        """Windows from a LIST of grey uint8 frames of different sizes (hg_patcher_extract_frame_list_device).  ``frames``: a sequence of
+        (frame_ptr, frame_h, frame_w, ld) — raw device pointers (ints) and each frame's own geometry; row i is cut from frame
+        ``row_frame[i]`` (int32 on the device), the bytes ``extract_device`` gives on that frame alone; a row whose frame lies outside
+        [0, len(frames)) is all zero.  The descriptors are consumed before the call returns.  Enqueued on ``stream``."""
+        filt = _capi.filter_code(interpolation)
+        w, h = int(out_size[0]), int(out_size[1])
+        refs = (_capi.HgFrameRef * max(len(frames), 1))()
+        for i, (ptr, fh, fw, ld) in enumerate(frames):
+            refs[i].frame_dev, refs[i].frame_h, refs[i].frame_w, refs[i].ld = int(ptr) or None, int(fh), int(fw), int(ld)
+        _capi.check(_capi.lib().hg_patcher_extract_frame_list_device(
+            self._handle(), filt, refs, len(frames), C.c_void_p(boxes_ptr), C.c_void_p(delta_angs_ptr) if delta_angs_ptr else None,
+            C.c_void_p(row_frame_ptr), int(n), w, h, C.c_void_p(out_ptr), _capi.np_dtype_code(out_dtype), int(ldo), C.c_void_p(stream)))
+
     def close(self):
         if self._h is not None:
             _capi.lib().hg_patcher_free(self._h)
