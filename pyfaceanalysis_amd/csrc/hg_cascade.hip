@@ -20,27 +20,7 @@
 #include "hg_frame_list.hpp"
 #include "hg_gauss_dev.hpp"
 
-namespace hg {
-void set_last_error(const std::string& s);
-void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                     const double* conf, int64_t n, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st);
-void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts,
-                             const int32_t** row_src, const int32_t** kept_idx, hipStream_t st);
-void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts);
-void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const double* boxes,
-                      const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n, double* out_rows, int64_t out_cap,
-                      int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
-void eyes_frames_tail_bounded(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
-                              const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n_bound,
-                              const int32_t* n_dev, const double** purged, const int32_t** seg_first, const int32_t** seg_kept, const int32_t** row_src,
-                              const int32_t** kept_idx, hipStream_t st);
-void eyes_frames_buffers(const hg_eyes* e, int n_frames, const double** purged, const int32_t** seg_first, const int32_t** seg_kept);
-void eyes_frame_list_tail(hg_eyes* e, const FrameList& fl, const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n,
-                          double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
-int eyes_device(const hg_eyes* e);
-int eyes_filter(const hg_eyes* e);
-}
+namespace hg { void set_last_error(const std::string& s); }
 
 // No contraction anywhere below (hg_gauss_dev.hpp, the regression, is included above and keeps the build's default): under hipcc's
 // -ffp-contract=fast-honor-pragmas the __dadd_rn / __dmul_rn of the HIP headers are plain operators, so `oa + net_Dang * tol` or
@@ -437,7 +417,7 @@ __global__ void __launch_bounds__(128) k_tracker_handover(const double* __restri
 // The start of the tracked pass: the nine windows of every held face of every stream, from the set's device state — faces
 // (n_streams, max_faces, 4) and held (n_streams) counts, clamped to 0 .. max_faces.  Original window o = s * 9 * max_faces + 9 j + i is
 // window i of held face j of stream s: orig_coords / orig_level are indexed by o with a fixed period per stream, so a row's stream is
-// o / (9 max_faces) wherever it travels — the divisor the stack machinery divides by already (FrameStack::n0, FrameSel::div,
+// o / (9 max_faces) wherever it travels — the divisor the stack machinery divides by already (StagePass::period, FrameSel::div,
 // k_eye_row_frames, k_frame_segments) — and its slot (o % (9 max_faces)) / 9.  The entries of faces not held are holes: never written,
 // never read.  The candidate arrays (coords .. oidx, nullable as everywhere) get the live rows COMPACTED, in order of o, with
 // oidx = o, and *count their number, 9 * sum of held: exactly the host's bound, no filler row at the first stage.  Every window comes
@@ -975,53 +955,11 @@ LevelTable make_level_table(const hg_cascade_level* levels, int n_levels) {
     return T;
 }
 
-// The stage loop.  `T`: the windows come from the grid's closed form (k_cascade_init_grid), else from boxes_host / level_host.
 // FNV-1a over a plain struct: the key under which the patcher keeps index tables of boxes that depend on sizes only
 uint64_t key_of(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
     for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
     return h ? h : 1;
 }
-
-// A TRACKED frame (`B`): the windows are the nine of k_cascade_init_tracked per held face (k_cascade_init_tracked_multi), built from the
-// B->n_faces boxes at B->face_dev, and the candidate count never visits the host.  n0 = 9 * n_faces bounds it from the start (nine in the
-// text below: one face), so every launch of every group is sized by that bound and the glue kernels
-// take the live count from the device word they already carry (A.count_in under A.n_max); no poll_count runs, stage_counts is -1
-// throughout, and nothing is copied out: the survivors stay in coords[*final_buf] ..., their count in *B->final_count, for the eye
-// step (eyes_frame_tail_bounded).  Rows between the live count and the bound: k_cascade_group gives them a defined window and
-// zero features after every compaction (A.pad_to), so each extraction reads finite boxes and each network defined pixels; the
-// sub-images carried over a Disc stage are gathered by the device count (k_gather_rows) and the rows past it keep earlier bytes —
-// any byte is a pixel, rows are independent, and the next glue launch skips them by the count.  A live count of 0 is a normal
-// case: every later launch runs on nine filler rows and compacts none.
-struct Bounded {
-    const double* face_dev;      // (n_faces, 4)
-    int n_faces;
-    hg_tracked_consts tc;
-    const int32_t* final_count;      // out
-    // a SET of streams (hg_stream_tracker; n_streams = 0: the one stream above): the faces are (n_streams, max_faces, 4), held_dev holds
-    // n_streams counts, n_faces is their sum over the streams — the host's mirror — and the call comes with a FrameStack of n_streams
-    // frames whose n0 is the period 9 * max_faces of the original windows (k_cascade_init_tracked_streams)
-    const int32_t* held_dev = nullptr;
-    int n_streams = 0, max_faces = 0;
-};
-
-// A STACK of frames (`FS`, hg_cascade_detect_frames_device): frame_dev is frame 0 of n_frames grey frames of one size, `stride` bytes
-// apart; the candidates are n_frames copies of the grid of `T` (n0 = n_frames * FS->n0: k_cascade_init_frames) and every extraction
-// cuts row i from frame orig_index[i] / FS->n0 (hg::patcher_extract_frames).  Nothing else differs: rows are independent, the
-// compaction keeps their order, so the survivors come out by frame and, inside a frame, in the order the frame alone gives.
-// A LIST of frames of different sizes (`list`, hg_cascade_detect_frame_list_device): frame_dev / frame_h / frame_w / ld are frame 0's,
-// stride and n0 are unused; the candidates are the concatenated grids (k_cascade_init_list) and every extraction takes row i's frame
-// from win_frame[orig_index[i]] (hg::patcher_extract_frame_list).  The same loop, for the same reason.
-struct ListRun {
-    hg::FrameList fl;
-    const LevelTable* tables_dev;      // one per distinct grid
-    const int32_t* grid_of_dev;        // per frame
-    int32_t* win_frame_dev;
-};
-struct FrameStack {
-    int n_frames;
-    int64_t stride, n0;
-    const ListRun* list = nullptr;
-};
 
 // Every frame-reading entry of this file refuses a bad frame as a bad ARGUMENT, before it launches or writes anything: a row stride
 // below the width (a broadcast view has 0) would have every row read its neighbours' pixels.
@@ -1030,87 +968,198 @@ void check_frame_geometry(int frame_h, int frame_w, int64_t ld, int bpp = 1) {
         hg::fail(HG_ERR_ARG, "bad frame geometry: %d rows of %d pixels of %d byte(s), %lld apart", frame_h, frame_w, bpp, (long long)ld);
 }
 
-void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes_host, const double* level_host,
-                 const LevelTable* T, int64_t n0, double* out_coords, double* out_angles, int32_t* out_orig_index, double* out_confidence,
-                 int64_t out_cap, int64_t* n_out, int32_t* stage_counts, int64_t* rows_executed, void* stream, int* final_buf = nullptr,
-                 Bounded* B = nullptr, const FrameStack* FS = nullptr) {
-    if (!c || !n_out) hg::fail(HG_ERR_ARG, "null argument");
-    if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
-    const ListRun* LS = FS ? FS->list : nullptr;
-    if (n0 > 0 && (!frame_dev || (!T && !B && !LS && (!boxes_host || !level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
-    // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
-    if (n0 > 0) check_frame_geometry(frame_h, frame_w, ld);
-    // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
-    const bool SB = B && B->n_streams > 0;      // the tracked pass of a stream set: Bounded and FrameStack together
-    if (LS && (T || B || FS->n_frames < 1 || FS->n_frames != LS->fl.n_frames || n0 != LS->fl.n_windows || !LS->tables_dev || !LS->win_frame_dev))
-        hg::fail(HG_ERR_ARG, "bad frame list");
-    if (FS && !LS && !SB && (!T || B || FS->n_frames < 1 || FS->n0 < 1 || n0 != FS->n0 * FS->n_frames)) hg::fail(HG_ERR_ARG, "bad frame stack");
-    if (B && !SB && (B->n_faces < 1 || B->n_faces > kMaxFaces || n0 != (int64_t)kTracked * B->n_faces || !B->face_dev)) hg::fail(HG_ERR_ARG, "bad tracked frame");
-    // the bound 9 * sum of held lies under the windows of the whole set, and those inside k_cascade_group's single-workgroup path (pad_to)
-    if (SB && (T || !FS || FS->n_frames != B->n_streams || B->max_faces < 1 || B->max_faces > kMaxFaces || FS->n0 != (int64_t)kTracked * B->max_faces ||
-               FS->n0 * FS->n_frames > 2 * kChunk || B->n_faces < 1 || n0 != (int64_t)kTracked * B->n_faces || n0 > FS->n0 * FS->n_frames || !B->face_dev ||
-               !B->held_dev))
-        hg::fail(HG_ERR_ARG, "bad tracked stream set");
-    set_dev(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int ns = (int)c->stages.size();
-    *n_out = 0;
-    if (rows_executed) *rows_executed = 0;
-    if (n0 == 0) {
-        for (int k = 0; k < ns && stage_counts; ++k) stage_counts[k] = 0;
-        return;
+// What a LIST of frames of different sizes keeps on the device (list_frames): the list itself, one level table per DISTINCT grid, the
+// grid number of every frame, and room for the frame of every original window, which k_cascade_init_list writes.
+struct ListRun {
+    hg::FrameList fl;
+    const LevelTable* tables_dev;
+    const int32_t* grid_of_dev;
+    int32_t* win_frame_dev;
+};
+
+// ---- one pass of the stage loop: where the windows come from, which frames the rows are cut from, what becomes of the survivors ----
+// The loop is the same for all of them: rows are independent and the compaction keeps their order, so the survivors of several frames
+// come out by frame and, inside a frame, in the order the frame alone gives.
+struct StagePass {
+    enum Windows {
+        HOST_BOXES,      // n0 boxes and level constants in host memory, copied in (k_cascade_init)
+        GRID,            // the closed form of level table T over ONE frame (k_cascade_init_grid)
+        GRID_STACK,      // a STACK of frames: n_frames copies of T's grid, window f * period + j = window j of frame f (k_cascade_init_frames);
+                         //   every extraction cuts row i from frame orig_index[i] / period
+        GRID_LIST,       // a LIST of frames: the concatenated grids (k_cascade_init_list), row i's frame is win_frame[orig_index[i]]
+        // TRACKED frames: nine windows per held face (tracked_window), from boxes the previous frame's last kernel left on the device; the
+        // candidate count never visits the host.  n0 = 9 * n_faces bounds it from the start, so every launch of every group is sized by
+        // that bound and the glue kernels take the live count from the device word they already carry (A.count_in under A.n_max).  Rows
+        // between the live count and the bound: k_cascade_group gives them a defined window and zero features after every compaction
+        // (A.pad_to), so each extraction reads finite boxes and each network defined pixels; the sub-images carried over a Disc stage are
+        // gathered by the device count (k_gather_rows) and the rows past it keep earlier bytes — any byte is a pixel, rows are independent,
+        // and the next glue launch skips them by the count.  A live count of 0 is a normal case: every later launch runs on filler rows
+        // and compacts none.  pad_to exists on k_cascade_group's single-workgroup path only: the bound stays at or under 2 * kChunk.
+        TRACKED,         // ONE stream: n_faces boxes at face_dev, n_faces known on the host (k_cascade_init_tracked_multi)
+        TRACKED_STREAMS  // a SET of streams over a stack of n_frames = n_streams frames: faces (n_streams, max_faces, 4), held_dev their
+                         //   n_streams counts, n_faces the host's mirror of their sum; period = 9 * max_faces original windows per stream,
+                         //   orig_coords / orig_level indexed over the whole set's period (k_cascade_init_tracked_streams)
+    };
+    enum Survivors {
+        TO_HOST,         // copied to the host arrays of `host` (each nullable), their number to *host.n_out; more than host.cap is refused
+        ON_DEVICE,       // left in coords[cur], angles[cur], conf[cur], oidx[cur] until the next call; the host knows their number
+        BOUNDED          // left there, and their number in a device word: nothing is read back in the whole pass, no poll runs,
+                         //   stage_counts is -1 throughout and the host knows the bound n0 only (what the tracked passes ask for)
+    };
+    Windows windows;
+    hg::FrameSource frames;
+    int64_t n0;                  // windows the pass starts with
+    Survivors survivors = ON_DEVICE;
+    struct {
+        double *coords, *angles;
+        int32_t* orig_index;
+        double* confidence;
+        int64_t cap, *n_out;
+    } host{};
+    const double *boxes_host = nullptr, *level_host = nullptr;      // HOST_BOXES
+    const LevelTable* T = nullptr;                                     // GRID, GRID_STACK: one frame's
+    const ListRun* list = nullptr;                                     // GRID_LIST
+    const double* face_dev = nullptr;                                  // TRACKED, TRACKED_STREAMS
+    const int32_t* held_dev = nullptr;
+    int n_faces = 0, max_faces = 0;
+    hg_tracked_consts tc{};
+
+    int64_t period() const { return windows == GRID_STACK ? T->first[T->n_levels] : windows == TRACKED_STREAMS ? (int64_t)kTracked * max_faces : 0; }
+    // the key of the first stage's boxes where they are a function of sizes alone (their index tables are kept)
+    uint64_t table_key() const { return windows == GRID || windows == GRID_STACK ? key_of(T, sizeof *T) : windows == GRID_LIST ? list->fl.key : 0; }
+
+    static StagePass boxes(const hg::FrameSource& one, const double* boxes_host, const double* level_host, int64_t n0) {
+        StagePass P{HOST_BOXES, one, n0};
+        P.boxes_host = boxes_host;
+        P.level_host = level_host;
+        return P;
     }
-    c->reserve(SB ? FS->n0 * FS->n_frames : n0);      // (a stream set: orig_coords / orig_level are indexed over the whole set's period)
-    if (SB) {
-        hipLaunchKernelGGL(k_cascade_init_tracked_streams, 1, 1024, 0, st, B->tc, B->face_dev, B->held_dev, B->n_streams, B->max_faces, (double*)c->orig_coords.p,
-                           (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p,
-                           (int32_t*)c->oidx[0].p, (int32_t*)c->count.p);
-    } else if (B) {
-        hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)((n0 + 63) / 64), 64, 0, st, B->tc, B->face_dev, B->n_faces, (double*)c->orig_coords.p,
-                           (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
-                           (int32_t*)c->count.p);
-    } else if (LS) {
-        hipLaunchKernelGGL(k_cascade_init_list, (unsigned)((n0 + 255) / 256), 256, 0, st, LS->tables_dev, LS->fl.dev, LS->grid_of_dev, LS->fl.n_frames, (int)n0,
-                           (double*)c->orig_coords.p, (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p,
-                           (double*)c->conf[0].p, (int32_t*)c->oidx[0].p, (int32_t*)c->count.p, LS->win_frame_dev);
-    } else if (T) {
-        hipLaunchKernelGGL(k_cascade_init_grid, (unsigned)((n0 + 255) / 256), 256, 0, st, *T, (double*)c->orig_coords.p, (double*)c->orig_level.p,
-                           (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p,
-                           (int32_t*)c->count.p);
-        if (FS && FS->n_frames > 1)
-            hipLaunchKernelGGL(k_cascade_init_frames, (unsigned)((n0 + 255) / 256), 256, 0, st, (int)FS->n0, (int)n0, (double*)c->orig_coords.p,
-                               (double*)c->orig_level.p, (double*)c->coords[0].p, (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p,
-                               (int32_t*)c->oidx[0].p, (int32_t*)c->count.p);
-    } else {
-        HG_HIP(hipMemcpyAsync(c->orig_coords.p, boxes_host, (size_t)n0 * 32, hipMemcpyHostToDevice, st));
-        HG_HIP(hipMemcpyAsync(c->orig_level.p, level_host, (size_t)n0 * 24, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cascade_init, (unsigned)((n0 + 255) / 256), 256, 0, st, (int)n0, (const double*)c->orig_coords.p, (double*)c->coords[0].p,
-                           (double*)c->angles[0].p, (double*)c->neg.p, (double*)c->conf[0].p, (int32_t*)c->oidx[0].p, (int32_t*)c->count.p);
+    static StagePass grid(const hg::FrameSource& fr, const LevelTable& T) {      // over one frame, or over every frame of a stack
+        const bool stack = fr.kind == hg::FrameSource::STACK;
+        StagePass P{stack ? GRID_STACK : GRID, fr, (int64_t)T.first[T.n_levels] * (stack ? fr.n_frames : 1)};
+        P.T = &T;
+        return P;
+    }
+    static StagePass grid_list(const ListRun& R) {
+        StagePass P{GRID_LIST, hg::FrameSource::of_list(R.fl), R.fl.n_windows};
+        P.list = &R;
+        return P;
+    }
+    static StagePass tracked(const hg::FrameSource& fr, const hg_tracked_consts& tc, const double* face_dev, int n_faces, const int32_t* held_dev = nullptr,
+                             int max_faces = 0) {      // held_dev: a stream set over the stack fr
+        StagePass P{held_dev ? TRACKED_STREAMS : TRACKED, fr, (int64_t)kTracked * n_faces, BOUNDED};
+        P.face_dev = face_dev;
+        P.held_dev = held_dev;
+        P.n_faces = n_faces;
+        P.max_faces = max_faces;
+        P.tc = tc;
+        return P;
+    }
+    StagePass& to_host(double* coords, double* angles, int32_t* orig_index, double* confidence, int64_t cap, int64_t* n_out) {
+        survivors = TO_HOST;
+        host = {coords, angles, orig_index, confidence, cap, n_out};
+        return *this;
+    }
+};
+// n: the survivors (BOUNDED: their bound); they are in the cur half of the ping-pong arrays; count_dev: the device word of their number
+struct PassResult {
+    int64_t n;
+    int cur;
+    const int32_t* count_dev;
+    int64_t rows;              // rows the networks executed
+    bool on_host;              // the last group's kernel has written the survivors to pinned memory (host_results) already
+};
+
+// The refusals of a pass: values only — what kind of pass it is cannot be wrong
+void check_pass(const hg_cascade* c, const StagePass& P) {
+    const hg::FrameSource& F = P.frames;
+    const int64_t n0 = P.n0;
+    if (!c || (P.survivors == StagePass::TO_HOST && !P.host.n_out)) hg::fail(HG_ERR_ARG, "null argument");
+    if (n0 < 0 || n0 > 0x7fffffffll / 64) hg::fail(HG_ERR_ARG, "bad window count");
+    if (n0 > 0 && (!F.px || (P.windows == StagePass::HOST_BOXES && (!P.boxes_host || !P.level_host)))) hg::fail(HG_ERR_ARG, "null data pointer");
+    // here, not by the patcher in the middle of the stage loop (whose refusal came back as HG_ERR_DEVICE after the grid kernel had run)
+    if (n0 > 0) check_frame_geometry(F.h, F.w, F.ld);
+    switch (P.windows) {
+        case StagePass::GRID_LIST:
+            if (F.n_frames < 1 || n0 != P.list->fl.n_windows || !P.list->tables_dev || !P.list->win_frame_dev) hg::fail(HG_ERR_ARG, "bad frame list");
+            break;
+        case StagePass::GRID_STACK:
+            if (F.n_frames < 1 || P.period() < 1 || n0 != P.period() * F.n_frames) hg::fail(HG_ERR_ARG, "bad frame stack");
+            break;
+        case StagePass::TRACKED:      // a positive multiple of nine matching the held count; beyond kMaxFaces the two-launch chunk path, which has no pad_to, would come near
+            if (P.n_faces < 1 || P.n_faces > kMaxFaces || n0 != (int64_t)kTracked * P.n_faces || !P.face_dev) hg::fail(HG_ERR_ARG, "bad tracked frame");
+            break;
+        case StagePass::TRACKED_STREAMS:      // the bound 9 * sum of held lies under the windows of the whole set, and those inside k_cascade_group's single-workgroup path (pad_to)
+            if (F.n_frames < 1 || P.max_faces < 1 || P.max_faces > kMaxFaces || P.period() * F.n_frames > 2 * kChunk || P.n_faces < 1 ||
+                n0 != (int64_t)kTracked * P.n_faces || n0 > P.period() * F.n_frames || !P.face_dev || !P.held_dev)
+                hg::fail(HG_ERR_ARG, "bad tracked stream set");
+            break;
+        default: break;
+    }
+}
+
+// The start of a pass: original windows, their level constants and the first candidates, by the kind of window source
+void launch_init(hg_cascade* c, const StagePass& P, hipStream_t st) {
+    const int64_t n0 = P.n0;
+    double *oc = (double*)c->orig_coords.p, *ol = (double*)c->orig_level.p, *co = (double*)c->coords[0].p, *an = (double*)c->angles[0].p, *ng = (double*)c->neg.p,
+           *cf = (double*)c->conf[0].p;
+    int32_t *oi = (int32_t*)c->oidx[0].p, *cnt = (int32_t*)c->count.p;
+    const unsigned blocks = (unsigned)((n0 + 255) / 256);
+    switch (P.windows) {
+        case StagePass::TRACKED_STREAMS:
+            hipLaunchKernelGGL(k_cascade_init_tracked_streams, 1, 1024, 0, st, P.tc, P.face_dev, P.held_dev, P.frames.n_frames, P.max_faces, oc, ol, co, an, ng, cf, oi, cnt);
+            break;
+        case StagePass::TRACKED:
+            hipLaunchKernelGGL(k_cascade_init_tracked_multi, (unsigned)((n0 + 63) / 64), 64, 0, st, P.tc, P.face_dev, P.n_faces, oc, ol, co, an, ng, cf, oi, cnt);
+            break;
+        case StagePass::GRID_LIST:
+            hipLaunchKernelGGL(k_cascade_init_list, blocks, 256, 0, st, P.list->tables_dev, P.list->fl.dev, P.list->grid_of_dev, P.list->fl.n_frames, (int)n0, oc, ol, co,
+                               an, ng, cf, oi, cnt, P.list->win_frame_dev);
+            break;
+        case StagePass::GRID:
+        case StagePass::GRID_STACK:
+            hipLaunchKernelGGL(k_cascade_init_grid, blocks, 256, 0, st, *P.T, oc, ol, co, an, ng, cf, oi, cnt);
+            if (P.windows == StagePass::GRID_STACK && P.frames.n_frames > 1)
+                hipLaunchKernelGGL(k_cascade_init_frames, blocks, 256, 0, st, (int)P.period(), (int)n0, oc, ol, co, an, ng, cf, oi, cnt);
+            break;
+        case StagePass::HOST_BOXES:
+            HG_HIP(hipMemcpyAsync(oc, P.boxes_host, (size_t)n0 * 32, hipMemcpyHostToDevice, st));
+            HG_HIP(hipMemcpyAsync(ol, P.level_host, (size_t)n0 * 24, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_cascade_init, blocks, 256, 0, st, (int)n0, (const double*)oc, co, an, ng, cf, oi, cnt);
+            break;
     }
     HG_HIP(hipGetLastError());
-    // the count word is polled, never waited for with a stream synchronisation (publish_count); a deadline guards against a
-    // device that never answers
-    auto poll_count = [&](int32_t seq) -> int64_t {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; ++spins) {
-            if (__atomic_load_n(c->host_count + 1, __ATOMIC_ACQUIRE) == seq) return c->host_count[0];
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                HG_HIP(hipStreamSynchronize(st));
-                if (__atomic_load_n(c->host_count + 1, __ATOMIC_ACQUIRE) == seq) return c->host_count[0];
-                hg::fail(HG_ERR_DEVICE, "cascade stage did not report its survivor count");
-            }
-            __builtin_ia32_pause();
+}
+
+// The host's wait for a pinned sequence word a kernel writes last, at system scope (publish_count): polled, never a stream
+// synchronisation, which costs the caller 20-40 us more before it has caught up with the device again.  A deadline guards against a
+// device that never answers: then one synchronisation, one more look, and `what` as the failure.
+void wait_for_seq(const int32_t* word, int32_t seq, hipStream_t st, const char* what) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != seq; ++spins) {
+        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+            HG_HIP(hipStreamSynchronize(st));
+            if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) return;
+            hg::fail(HG_ERR_DEVICE, "%s", what);
         }
-    };
-    HostResults H{};
-    H.coords = (double*)c->host_res;
-    H.angles = (double*)(c->host_res + (size_t)hg_cascade::kResCap * 32);
-    H.conf = (double*)(c->host_res + (size_t)hg_cascade::kResCap * 40);
-    H.oidx = (int32_t*)(c->host_res + (size_t)hg_cascade::kResCap * 48);
+        __builtin_ia32_pause();
+    }
+}
+
+HostResults host_results(const hg_cascade* c) {
+    constexpr size_t cap = hg_cascade::kResCap;
+    return HostResults{(double*)c->host_res, (double*)(c->host_res + cap * 32), (double*)(c->host_res + cap * 40), (int32_t*)(c->host_res + cap * 48), 0};
+}
+
+// The stage loop proper, group by group, from the candidates launch_init left; stage_counts (nullable): survivors after every stage
+PassResult run_groups(hg_cascade* c, const StagePass& P, int32_t* stage_counts, hipStream_t st) {
+    const int ns = (int)c->stages.size();
+    const bool bounded = P.survivors == StagePass::BOUNDED;
+    const hg::RowFrames row_frames{(const int32_t*)nullptr, true, P.period()};
     bool results_on_host = false;
     int cur = 0, cnt_slot = 0;
     int sb = 0;                                    // which of subs[] holds the extracted sub-images, row-aligned with the candidates
-    int64_t n_bound = n0, rows = 0;                // n_bound: host-side upper bound of the candidate count (exact after a Disc stage)
+    int64_t n_bound = P.n0, rows = 0;              // n_bound: host-side upper bound of the candidate count (exact after a Disc stage)
     const size_t row = (size_t)c->w * c->h;
     // The reference compacts subimages_arr after EVERY stage (FaceDetectUpdated.py:753) and reuses it in a stage that follows a
     // Disc stage and owns a network (:674-681).  Here the rows travel only while a later stage will read them before the next
@@ -1139,23 +1188,13 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         const bool skip_extract = (k > 0 && c->stages[k - 1].type == HG_STAGE_DISC) || !S.flow;      // FaceDetectUpdated.py:674-681
         if (!skip_extract) {
             // (the first stage's angles are all zero: the plain EXTENT kernel — a window with delta_ang == 0 is cut from the frame itself —
-            // and where the windows come from the level table they are a function of that table alone: their index tables are kept)
+            // and where the windows come from level tables they are a function of those alone: their index tables are kept)
             // the stage's filter: interpolation_formats[network_serial] (FaceDetectUpdated.py:671, :686)
-            const uint64_t key = k == 0 && T ? key_of(T, sizeof *T) : 0;
-            const double* dang = k == 0 ? nullptr : (const double*)c->neg.p;
-            hg::FrameList fl{};
-            if (LS) {
-                fl = LS->fl;
-                if (k != 0) fl.key = 0;      // the concatenated grids are the first stage's boxes only
-            }
-            const int rc = LS ? hg::patcher_extract_frame_list(c->patcher, fl, c->interp[S.serial], (const double*)c->coords[cur].p, dang,
-                                                               (const int32_t*)c->oidx[cur].p, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
-                         : FS ? hg::patcher_extract_frames(c->patcher, key, FS->n0, c->interp[S.serial], frame_dev, FS->n_frames, FS->stride, frame_h, frame_w, ld,
-                                                           (const double*)c->coords[cur].p, dang, (const int32_t*)c->oidx[cur].p, (int)FS->n0, n_bound, c->w,
-                                                           c->h, c->subs[sb].p, HG_U8, (int64_t)row, st)
-                              : hg::patcher_extract(c->patcher, key, c->interp[S.serial], frame_dev, HG_U8, frame_h, frame_w, ld,
-                                                    (const double*)c->coords[cur].p, dang, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st);
-            if (rc != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
+            hg::RowFrames rf = row_frames;
+            rf.index_dev = (const int32_t*)c->oidx[cur].p;
+            if (hg::patcher_extract_source(c->patcher, P.frames, k == 0 ? P.table_key() : 0, rf, c->interp[S.serial], (const double*)c->coords[cur].p,
+                                           k == 0 ? nullptr : (const double*)c->neg.p, n_bound, c->w, c->h, c->subs[sb].p, HG_U8, (int64_t)row, st) != HG_OK)
+                hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
         }
         if (S.flow) {
             if (hg_flow_execute_device(S.flow, c->subs[sb].p, HG_U8, n_bound, (int64_t)row, c->sl[cur].p, HG_F32, c->k, c->k, st) != HG_OK)
@@ -1196,21 +1235,21 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         A.k_feat = c->k;
         A.cur = cur;
         A.n_max = (int32_t)n_bound;
-        A.pad_to = B ? (int32_t)n_bound : 0;
+        A.pad_to = bounded ? (int32_t)n_bound : 0;
         // the host needs the exact count where it shrinks and sizes the next launches: after every group with a Disc stage (the
         // read-back is a poll of a pinned word, cheap enough for the small stages too), and at the end
         const bool last = k + m == ns;
-        const bool want_count = !B && (any_disc || last);      // a tracked frame: the bound sizes the launches, nothing is read back
+        const bool want_count = !bounded && (any_disc || last);      // a bounded pass: the bound sizes the launches, nothing is read back
         const int32_t seq = want_count ? ++c->seq : 0;
         HostResults Hk{};
-        if (n_bound > 2 * kChunk) {      // many frames' windows (never a tracked frame: no pad_to here, and 9 * kMaxFaces is far below): one workgroup per kChunk candidates, two launches
+        if (n_bound > 2 * kChunk) {      // many frames' windows (never a bounded pass: no pad_to here): one workgroup per kChunk candidates, two launches
             const unsigned chunks = (unsigned)((n_bound + kChunk - 1) / kChunk);
             c->chunk_count.alloc((size_t)chunks * kMaxGroup * 4);
             hipLaunchKernelGGL(k_cascade_group_mark, chunks, 1024, 0, st, G, c->base, A, c->cap, (int32_t*)c->chunk_count.p);
             hipLaunchKernelGGL(k_cascade_group_scatter, chunks, 1024, 0, st, m, A, (const int32_t*)c->chunk_count.p, want_count ? c->host_count : nullptr, seq);
         } else {
-            if (last && !B && n_bound <= hg_cascade::kResCap) {
-                Hk = H;
+            if (last && !bounded && n_bound <= hg_cascade::kResCap) {
+                Hk = host_results(c);
                 Hk.cap = hg_cascade::kResCap;
                 results_on_host = true;
             }
@@ -1226,36 +1265,64 @@ void detect_impl(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w,
         cur = 1 - cur;
         cnt_slot = 1 - cnt_slot;
         if (want_count) {
-            n_bound = poll_count(seq);
+            wait_for_seq(c->host_count + 1, seq, st, "cascade stage did not report its survivor count");
+            n_bound = c->host_count[0];
             for (int s = 0; s < m && stage_counts; ++s) stage_counts[k + s] = c->host_count[2 + s];      // written before the sequence number
         } else {
             for (int s = 0; s < m && stage_counts; ++s) stage_counts[k + s] = -1;      // not read back (no stage of the group discards by a cut-off: bound of the last Disc stage)
         }
         k += m;
     }
-    if (B) {      // the survivors and their count stay on the device
-        B->final_count = (const int32_t*)c->count.p + cnt_slot;
-        *n_out = n_bound;
-        if (rows_executed) *rows_executed = rows;
-        if (final_buf) *final_buf = cur;
-        return;
-    }
-    if (n_bound > out_cap) hg::fail(HG_ERR_ARG, "%lld detections but room for %lld", (long long)n_bound, (long long)out_cap);
-    if (n_bound > 0 && results_on_host) {      // written by the last group's kernel before it published the count
-        if (out_coords) memcpy(out_coords, H.coords, (size_t)n_bound * 32);
-        if (out_angles) memcpy(out_angles, H.angles, (size_t)n_bound * 8);
-        if (out_orig_index) memcpy(out_orig_index, H.oidx, (size_t)n_bound * 4);
-        if (out_confidence) memcpy(out_confidence, H.conf, (size_t)n_bound * 8);
-    } else if (n_bound > 0) {
-        if (out_coords) HG_HIP(hipMemcpyAsync(out_coords, c->coords[cur].p, (size_t)n_bound * 32, hipMemcpyDeviceToHost, st));
-        if (out_angles) HG_HIP(hipMemcpyAsync(out_angles, c->angles[cur].p, (size_t)n_bound * 8, hipMemcpyDeviceToHost, st));
-        if (out_orig_index) HG_HIP(hipMemcpyAsync(out_orig_index, c->oidx[cur].p, (size_t)n_bound * 4, hipMemcpyDeviceToHost, st));
-        if (out_confidence) HG_HIP(hipMemcpyAsync(out_confidence, c->conf[cur].p, (size_t)n_bound * 8, hipMemcpyDeviceToHost, st));
+    return PassResult{n_bound, cur, (const int32_t*)c->count.p + cnt_slot, rows, results_on_host};
+}
+
+// TO_HOST: the survivors into the caller's arrays — from pinned memory where the last group's kernel wrote them before it published
+// the count, else four copies and a synchronisation
+void read_survivors(hg_cascade* c, const StagePass& P, const PassResult& r, hipStream_t st) {
+    const auto& o = P.host;
+    const size_t n = (size_t)r.n;
+    if (r.n > o.cap) hg::fail(HG_ERR_ARG, "%lld detections but room for %lld", (long long)r.n, (long long)o.cap);
+    if (r.n > 0 && r.on_host) {
+        const HostResults H = host_results(c);
+        if (o.coords) memcpy(o.coords, H.coords, n * 32);
+        if (o.angles) memcpy(o.angles, H.angles, n * 8);
+        if (o.orig_index) memcpy(o.orig_index, H.oidx, n * 4);
+        if (o.confidence) memcpy(o.confidence, H.conf, n * 8);
+    } else if (r.n > 0) {
+        if (o.coords) HG_HIP(hipMemcpyAsync(o.coords, c->coords[r.cur].p, n * 32, hipMemcpyDeviceToHost, st));
+        if (o.angles) HG_HIP(hipMemcpyAsync(o.angles, c->angles[r.cur].p, n * 8, hipMemcpyDeviceToHost, st));
+        if (o.orig_index) HG_HIP(hipMemcpyAsync(o.orig_index, c->oidx[r.cur].p, n * 4, hipMemcpyDeviceToHost, st));
+        if (o.confidence) HG_HIP(hipMemcpyAsync(o.confidence, c->conf[r.cur].p, n * 8, hipMemcpyDeviceToHost, st));
         HG_HIP(hipStreamSynchronize(st));
     }
-    *n_out = n_bound;
-    if (rows_executed) *rows_executed = rows;
-    if (final_buf) *final_buf = cur;      // the survivors stay in coords[cur], angles[cur], conf[cur] until the next call
+    *o.n_out = r.n;
+}
+
+// One pass: the checks, the init kernel, the group loop, the read-back.  rows_executed (nullable) is zeroed, like *host.n_out, once the
+// pass is accepted and written at the end.
+PassResult run_pass(hg_cascade* c, const StagePass& P, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
+    check_pass(c, P);
+    set_dev(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (P.survivors == StagePass::TO_HOST) *P.host.n_out = 0;
+    if (rows_executed) *rows_executed = 0;
+    if (P.n0 == 0) {
+        for (size_t k = 0; k < c->stages.size() && stage_counts; ++k) stage_counts[k] = 0;
+        return PassResult{};
+    }
+    const int64_t set_windows = P.period() * P.frames.n_frames;      // (a stream set: orig_coords / orig_level are indexed over the whole set's period)
+    c->reserve(P.windows == StagePass::TRACKED_STREAMS ? set_windows : P.n0);
+    launch_init(c, P, st);
+    const PassResult r = run_groups(c, P, stage_counts, st);
+    if (P.survivors == StagePass::TO_HOST) read_survivors(c, P, r, st);
+    if (rows_executed) *rows_executed = r.rows;
+    return r;
+}
+
+// the survivors a pass left on the device, for the eye tail (hg_eyes.hip)
+hg::EyeSurvivors survivors_of(const hg_cascade* c, const StagePass& P, const PassResult& r) {
+    return hg::EyeSurvivors{(const double*)c->coords[r.cur].p, (const double*)c->angles[r.cur].p, (const double*)c->conf[r.cur].p, (const int32_t*)c->oidx[r.cur].p,
+                            P.period(), r.n, P.survivors == StagePass::BOUNDED ? r.count_dev : nullptr};
 }
 
 // FaceDetectUpdated.py:551-561: im.resize((w, h), NEAREST) before the grid is laid out — PIL's nearest resize is the EXTENT rule over
@@ -1277,12 +1344,8 @@ void gray_frame_of(hg_cascade* c, const void* frame_dev, int frame_h, int frame_
     fld = frame_w;
 }
 
-void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
-                    const void*& fr, int& fh, int& fw, int64_t& fld, void* dst = nullptr, const double* box_dev = nullptr) {
-    fr = frame_dev;
-    fh = frame_h;
-    fw = frame_w;
-    fld = ld;
+hg::FrameSource prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame_w, int64_t ld, int prescale_w, int prescale_h, void* stream,
+                               void* dst = nullptr, const double* box_dev = nullptr) {
     if (prescale_w > 0 || prescale_h > 0) {
         if (prescale_w <= 0 || prescale_h <= 0 || !frame_dev) hg::fail(HG_ERR_ARG, "bad prescale size %d x %d", prescale_w, prescale_h);
         check_frame_geometry(frame_h, frame_w, ld, hg::frame_bpp(c->frame_format));
@@ -1301,24 +1364,18 @@ void prescale_frame(hg_cascade* c, const void* frame_dev, int frame_h, int frame
             const int rc = hg_patcher_resize_device(c->patcher, c->prescale_filter, 0, frame_dev, c->frame_format, frame_h, frame_w, ld, HG_FRAME_L,
                                                     dst, prescale_h, prescale_w, prescale_w, stream);
             if (rc != HG_OK) hg::fail(rc, "%s", hg_last_error());
-            fr = dst;
-            fh = prescale_h;
-            fw = prescale_w;
-            fld = prescale_w;
-            return;
+            return hg::FrameSource::one(dst, prescale_h, prescale_w, prescale_w);
         }
         const int32_t pre_shape[4] = {frame_w, frame_h, prescale_w, prescale_h};      // the whole-frame box depends on these alone
         if (hg::patcher_extract_format(c->patcher, key_of(pre_shape, sizeof pre_shape, 0x9e3779b97f4a7c15ull), c->frame_format, frame_dev, frame_h, frame_w, ld,
                                        box_dev ? box_dev : (const double*)c->pre_box.p, 1, prescale_w, prescale_h, dst, HG_U8, (int64_t)prescale_w * prescale_h,
                                        stream) != HG_OK)
             hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
-        fr = dst;
-        fh = prescale_h;
-        fw = prescale_w;
-        fld = prescale_w;
-    } else if (c->frame_format != HG_FRAME_L && frame_dev) {      // (a null frame: detect_impl's refusal)
-        gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, fr, fld, dst);
+        return hg::FrameSource::one(dst, prescale_h, prescale_w, prescale_w);
     }
+    hg::FrameSource fr = hg::FrameSource::one(frame_dev, frame_h, frame_w, ld);
+    if (c->frame_format != HG_FRAME_L && frame_dev) gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, fr.px, fr.ld, dst);      // (a null frame: check_pass's refusal)
+    return fr;
 }
 
 // ---- a stack of same-size frames through one pooled pass (include/higsfa.h, hg_cascade_detect_frames_device) ----------------------
@@ -1341,38 +1398,26 @@ LevelTable check_frame_stack(const hg_cascade* c, const void* frames_dev, int n_
 
 // The grey frames the pooled stage loop reads: grey frames without a prescale in place; otherwise every frame through prescale_frame —
 // the code a single frame runs, one pass per frame — into its slot of the cascade's dense grey stack.
-FrameStack stack_frames(hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, int prescale_w,
-                        int prescale_h, int64_t n0, void* stream, const void*& fr, int& fh, int& fw, int64_t& fld) {
+hg::FrameSource stack_frames(hg_cascade* c, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, int prescale_w,
+                             int prescale_h, void* stream) {
     const bool pre = prescale_w > 0 || prescale_h > 0;
-    fr = frames_dev;
-    fh = frame_h;
-    fw = frame_w;
-    fld = ld;
-    if (!pre && c->frame_format == HG_FRAME_L) return FrameStack{n_frames, frame_stride, n0};
+    if (!pre && c->frame_format == HG_FRAME_L) return hg::FrameSource::stack(frames_dev, frame_h, frame_w, ld, n_frames, frame_stride);
     const int oh = pre ? prescale_h : frame_h, ow = pre ? prescale_w : frame_w;
     const size_t slot = (size_t)oh * ow;
     set_dev(c->device);
     c->frame_stack.alloc(slot * n_frames);
-    for (int f = 0; f < n_frames; ++f) {
-        const void* one;
-        prescale_frame(c, (const char*)frames_dev + (int64_t)f * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream, one, fh, fw, fld,
-                       (char*)c->frame_stack.p + slot * f);
-    }
-    fr = c->frame_stack.p;
-    return FrameStack{n_frames, (int64_t)slot, n0};
+    hg::FrameSource one;
+    for (int f = 0; f < n_frames; ++f)
+        one = prescale_frame(c, (const char*)frames_dev + (int64_t)f * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream,
+                             (char*)c->frame_stack.p + slot * f);
+    return hg::FrameSource::stack(c->frame_stack.p, one.h, one.w, one.ld, n_frames, (int64_t)slot);
 }
 
-// detect_impl's survivors of a stack, as the caller gets them: the index within the frame's own grid, and the first row of every frame
-// (they are ordered by frame: the compaction keeps the candidates' order)
-void split_by_frame(int32_t* orig_index, int64_t n, int64_t n0, int n_frames, int32_t* frame_first) {
-    int f = 0;
-    frame_first[0] = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const int fi = (int)(orig_index[i] / n0);
-        while (f < fi && f < n_frames) frame_first[++f] = (int32_t)i;
-        orig_index[i] = (int32_t)(orig_index[i] - (int64_t)fi * n0);
-    }
-    while (f < n_frames) frame_first[++f] = (int32_t)n;
+// The "fetch orig_index even if the caller does not want it" of the pooled entries: a survivor's frame is read off its index
+int32_t* index_room(int32_t* out_orig_index, std::vector<int32_t>& own, int64_t out_cap, int64_t total) {
+    if (out_orig_index) return out_orig_index;
+    own.resize((size_t)std::min<int64_t>(out_cap, total));
+    return own.data();
 }
 
 // ---- a list of frames of different sizes through one pooled pass (include/higsfa.h, hg_cascade_detect_frame_list_device) -----------
@@ -1381,7 +1426,7 @@ void split_by_frame(int32_t* orig_index, int64_t n, int64_t n0, int n_frames, in
 hg::ListLayout check_frame_list(const hg_cascade* c, const hg_eyes* e, const hg_cascade_frame* frames, int n_frames, int64_t out_cap, const int32_t* frame_first) {
     if (!c || !frames || !frame_first) hg::fail(HG_ERR_ARG, "null argument");
     if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
-    // a stage behind the first that extracts (detect_impl's skip_extract) with NEAREST, or a NEAREST eye step, cuts rotated NEAREST windows:
+    // a stage behind the first that extracts (run_groups' skip_extract) with NEAREST, or a NEAREST eye step, cuts rotated NEAREST windows:
     // a frame outside PIL's fixed-point range is refused here, not by the patcher in the middle of the stage loop
     bool rotated_nearest = e && hg::eyes_filter(e) == HG_FILTER_NEAREST;
     for (size_t k = 1; k < c->stages.size(); ++k)
@@ -1433,29 +1478,15 @@ void list_frames(hg_cascade* c, const hg_cascade_frame* frames, int n_frames, co
     desc.resize((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) {
         const hg_cascade_frame& F = frames[f];
-        const void* one;
-        int fh, fw;
-        int64_t fld;
-        prescale_frame(c, F.frame_dev, F.frame_h, F.frame_w, F.ld, F.prescale_w, F.prescale_h, stream, one, fh, fw, fld, (char*)c->list_gray.p + slot[(size_t)f],
-                       (const double*)((const char*)c->list_meta.p + off_box) + (size_t)f * 4);
-        desc[(size_t)f] = hg::FrameDesc{(const uint8_t*)one, fld, fw, fh, L.first[(size_t)f], L.tab_row[(size_t)f]};
+        const hg::FrameSource one = prescale_frame(c, F.frame_dev, F.frame_h, F.frame_w, F.ld, F.prescale_w, F.prescale_h, stream,
+                                                   (char*)c->list_gray.p + slot[(size_t)f], (const double*)((const char*)c->list_meta.p + off_box) + (size_t)f * 4);
+        desc[(size_t)f] = hg::FrameDesc{(const uint8_t*)one.px, one.ld, one.w, one.h, L.first[(size_t)f], L.tab_row[(size_t)f]};
     }
     hg::put_frame_descs(desc.data(), n_frames, (hg::FrameDesc*)c->list_desc.p, st);
     R.fl = hg::FrameList{desc.data(), (const hg::FrameDesc*)c->list_desc.p, n_frames, (const int32_t*)c->list_win.p, total, L.key, L.tab_rows};
     R.tables_dev = (const LevelTable*)c->list_meta.p;
     R.grid_of_dev = (const int32_t*)((const char*)c->list_meta.p + off_grid);
     R.win_frame_dev = (int32_t*)c->list_win.p;
-}
-
-// detect_impl's survivors of a list, as the caller gets them (split_by_frame with first[] in place of f n0)
-void split_by_list(int32_t* orig_index, int64_t n, const std::vector<int32_t>& first, int n_frames, int32_t* frame_first) {
-    int f = 0;
-    frame_first[0] = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        while (f + 1 < n_frames && orig_index[i] >= first[(size_t)f + 1]) frame_first[++f] = (int32_t)i;
-        orig_index[i] -= first[(size_t)f];
-    }
-    while (f < n_frames) frame_first[++f] = (int32_t)n;
 }
 
 }  // namespace
@@ -1468,8 +1499,9 @@ int hg_cascade_detect_device(hg_cascade* c, const void* frame_dev, int frame_h, 
                              void* stream) {
     return guarded([&] {
         if (c && c->frame_format != HG_FRAME_L && frame_dev && n0 > 0) gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, frame_dev, ld);
-        detect_impl(c, frame_dev, frame_h, frame_w, ld, boxes_host, level_host, nullptr, n0, out_coords, out_angles, out_orig_index, out_confidence,
-                    out_cap, n_out, stage_counts, rows_executed, stream);
+        run_pass(c, StagePass::boxes(hg::FrameSource::one(frame_dev, frame_h, frame_w, ld), boxes_host, level_host, n0)
+                        .to_host(out_coords, out_angles, out_orig_index, out_confidence, out_cap, n_out),
+                 stage_counts, rows_executed, stream);
     });
 }
 
@@ -1479,8 +1511,8 @@ int hg_cascade_detect_levels_device(hg_cascade* c, const void* frame_dev, int fr
     return guarded([&] {
         const LevelTable T = make_level_table(levels, n_levels);
         if (c && c->frame_format != HG_FRAME_L && frame_dev && T.first[T.n_levels] > 0) gray_frame_of(c, frame_dev, frame_h, frame_w, ld, stream, frame_dev, ld);
-        detect_impl(c, frame_dev, frame_h, frame_w, ld, nullptr, nullptr, &T, T.first[T.n_levels], out_coords, out_angles, out_orig_index,
-                    out_confidence, out_cap, n_out, stage_counts, rows_executed, stream);
+        run_pass(c, StagePass::grid(hg::FrameSource::one(frame_dev, frame_h, frame_w, ld), T).to_host(out_coords, out_angles, out_orig_index, out_confidence, out_cap, n_out),
+                 stage_counts, rows_executed, stream);
     });
 }
 
@@ -1490,12 +1522,8 @@ int hg_cascade_detect_frame_device(hg_cascade* c, const void* frame_dev, int fra
     return guarded([&] {
         if (!c) hg::fail(HG_ERR_ARG, "null argument");
         const LevelTable T = make_level_table(levels, n_levels);
-        const void* fr;
-        int fh, fw;
-        int64_t fld;
-        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, T.first[T.n_levels], out_coords, out_angles, out_orig_index, out_confidence, out_cap,
-                    n_out, stage_counts, rows_executed, stream);
+        const hg::FrameSource fr = prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream);
+        run_pass(c, StagePass::grid(fr, T).to_host(out_coords, out_angles, out_orig_index, out_confidence, out_cap, n_out), stage_counts, rows_executed, stream);
     });
 }
 
@@ -1509,16 +1537,10 @@ int hg_cascade_detect_faces_frame_device(hg_cascade* c, hg_eyes* e, const void* 
         if (out_cap < 0) hg::fail(HG_ERR_ARG, "negative output capacity");
         if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
         const LevelTable T = make_level_table(levels, n_levels);
-        const void* fr;
-        int fh, fw;
-        int64_t fld;
-        prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
-        int64_t n = 0;
-        int cur = 0;
-        const int64_t n0 = T.first[T.n_levels];
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
-        hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
-                            out_rows, out_cap, n_out, n_before_purge, (hipStream_t)stream);
+        const StagePass P = StagePass::grid(prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream), T);
+        const PassResult r = run_pass(c, P, stage_counts, rows_executed, stream);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, P.frames, survivors_of(c, P, r), (hipStream_t)stream);
+        hg::eyes_tail_read(e, tail, out_rows, out_cap, n_out, n_before_purge, (hipStream_t)stream);
     });
 }
 
@@ -1529,26 +1551,19 @@ int hg_cascade_detect_frames_device(hg_cascade* c, const void* frames_dev, int n
     return guarded([&] {
         const LevelTable T = check_frame_stack(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_cap,
                                                frame_first);
-        const int64_t n0 = T.first[T.n_levels], total = n0 * n_frames;
-        const void* fr;
-        int fh, fw;
-        int64_t fld;
-        const FrameStack FS = stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, n0, stream, fr, fh, fw, fld);
-        std::vector<int32_t> own_index;      // the frame of a survivor is read off its index: fetched even if the caller does not want it
-        if (!out_orig_index) {
-            own_index.resize((size_t)std::min<int64_t>(out_cap, total));
-            out_orig_index = own_index.data();
-        }
+        StagePass P = StagePass::grid(stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream), T);
+        std::vector<int32_t> own_index, first((size_t)n_frames);
+        out_orig_index = index_room(out_orig_index, own_index, out_cap, P.n0);
         int64_t n = 0;
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, total, out_coords, out_angles, out_orig_index, out_confidence, out_cap, &n, stage_counts,
-                    rows_executed, stream, nullptr, nullptr, &FS);
-        split_by_frame(out_orig_index, n, n0, n_frames, frame_first);
+        run_pass(c, P.to_host(out_coords, out_angles, out_orig_index, out_confidence, out_cap, &n), stage_counts, rows_executed, stream);
+        for (int f = 0; f < n_frames; ++f) first[(size_t)f] = (int32_t)(f * P.period());
+        hg::split_by_first(out_orig_index, n, first.data(), n_frames, frame_first);
     });
 }
 
-// the pooled stage loop, then the eye step on ALL survivors as one batch and the purge per frame (hg::eyes_frames_tail), on the grey
-// stack the cascade read; as in hg_cascade_detect_faces_frame_device the host reads nothing between the stage loop's last survivor count
-// and the one read-back of the per-frame counts and the rows
+// the pooled stage loop, then the eye step on ALL survivors as one batch and the purge per frame, on the grey stack the cascade read; as
+// in hg_cascade_detect_faces_frame_device the host reads nothing between the stage loop's last survivor count and the one read-back of
+// the per-frame counts and the rows
 int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w,
                                           int64_t ld, int prescale_w, int prescale_h, const hg_cascade_level* levels, int n_levels, double* out_rows,
                                           int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed,
@@ -1558,18 +1573,10 @@ int hg_cascade_detect_faces_frames_device(hg_cascade* c, hg_eyes* e, const void*
         const LevelTable T = check_frame_stack(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, levels, n_levels, out_cap,
                                                frame_first);
         if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
-        const int64_t n0 = T.first[T.n_levels], total = n0 * n_frames;
-        const void* fr;
-        int fh, fw;
-        int64_t fld;
-        const FrameStack FS = stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, n0, stream, fr, fh, fw, fld);
-        int64_t n = 0;
-        int cur = 0;
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, total, nullptr, nullptr, nullptr, nullptr, total, &n, stage_counts, rows_executed, stream, &cur,
-                    nullptr, &FS);
-        hg::eyes_frames_tail(e, fr, n_frames, FS.stride, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
-                             (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, n0, n, out_rows, out_cap, frame_first, n_before_purge,
-                             (hipStream_t)stream);
+        const StagePass P = StagePass::grid(stack_frames(c, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream), T);
+        const PassResult r = run_pass(c, P, stage_counts, rows_executed, stream);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, P.frames, survivors_of(c, P, r), (hipStream_t)stream);
+        hg::eyes_tail_read_frames(tail, out_rows, out_cap, frame_first, n_before_purge, (hipStream_t)stream);
     });
 }
 
@@ -1578,42 +1585,33 @@ int hg_cascade_detect_frame_list_device(hg_cascade* c, const hg_cascade_frame* f
                                         int64_t* rows_executed, void* stream) {
     return guarded([&] {
         const hg::ListLayout L = check_frame_list(c, nullptr, frames, n_frames, out_cap, frame_first);
-        const int64_t total = L.first[(size_t)n_frames];
         std::vector<hg::FrameDesc> desc;
         ListRun R{};
         list_frames(c, frames, n_frames, L, stream, desc, R);
-        const FrameStack FS{n_frames, 0, 0, &R};
-        std::vector<int32_t> own_index;      // the frame of a survivor is read off its index: fetched even if the caller does not want it
-        if (!out_orig_index) {
-            own_index.resize((size_t)std::min<int64_t>(out_cap, total));
-            out_orig_index = own_index.data();
-        }
+        StagePass P = StagePass::grid_list(R);
+        std::vector<int32_t> own_index;
+        out_orig_index = index_room(out_orig_index, own_index, out_cap, P.n0);
         int64_t n = 0;
-        detect_impl(c, desc[0].px, desc[0].h, desc[0].w, desc[0].ld, nullptr, nullptr, nullptr, total, out_coords, out_angles, out_orig_index, out_confidence,
-                    out_cap, &n, stage_counts, rows_executed, stream, nullptr, nullptr, &FS);
-        split_by_list(out_orig_index, n, L.first, n_frames, frame_first);
+        run_pass(c, P.to_host(out_coords, out_angles, out_orig_index, out_confidence, out_cap, &n), stage_counts, rows_executed, stream);
+        hg::split_by_first(out_orig_index, n, L.first.data(), n_frames, frame_first);
     });
 }
 
 // the list's pooled stage loop, then the eye step on ALL survivors as one batch, every eye row cut from its face's own grey frame, and
-// the purge per frame (hg::eyes_frame_list_tail)
+// the purge per frame
 int hg_cascade_detect_faces_frame_list_device(hg_cascade* c, hg_eyes* e, const hg_cascade_frame* frames, int n_frames, double* out_rows, int64_t out_cap,
                                               int32_t* frame_first, int32_t* n_before_purge, int32_t* stage_counts, int64_t* rows_executed, void* stream) {
     return guarded([&] {
         if (!e) hg::fail(HG_ERR_ARG, "null argument");
         const hg::ListLayout L = check_frame_list(c, e, frames, n_frames, out_cap, frame_first);
         if (hg::eyes_device(e) != c->device) hg::fail(HG_ERR_ARG, "eye handle on device %d, cascade on device %d", hg::eyes_device(e), c->device);
-        const int64_t total = L.first[(size_t)n_frames];
         std::vector<hg::FrameDesc> desc;
         ListRun R{};
         list_frames(c, frames, n_frames, L, stream, desc, R);
-        const FrameStack FS{n_frames, 0, 0, &R};
-        int64_t n = 0;
-        int cur = 0;
-        detect_impl(c, desc[0].px, desc[0].h, desc[0].w, desc[0].ld, nullptr, nullptr, nullptr, total, nullptr, nullptr, nullptr, nullptr, total, &n, stage_counts,
-                    rows_executed, stream, &cur, nullptr, &FS);
-        hg::eyes_frame_list_tail(e, R.fl, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p,
-                                 (const int32_t*)c->oidx[cur].p, n, out_rows, out_cap, frame_first, n_before_purge, (hipStream_t)stream);
+        const StagePass P = StagePass::grid_list(R);
+        const PassResult r = run_pass(c, P, stage_counts, rows_executed, stream);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, P.frames, survivors_of(c, P, r), (hipStream_t)stream);
+        hg::eyes_tail_read_frames(tail, out_rows, out_cap, frame_first, n_before_purge, (hipStream_t)stream);
     });
 }
 
@@ -1658,6 +1656,18 @@ void check_finite_consts(const hg_tracked_consts& t) {
         if (!(x > 0.0) || !std::isfinite(x)) hg::fail(HG_ERR_ARG, "tracked-grid constants must be positive and finite");
 }
 
+// The hand-over's rule (k_tracker_handover, k_stream_handover) on rows the host has already: of the first min(n, max_faces) rows, those
+// whose four box numbers are all finite are carried
+int carried_rows(const double* rows, int64_t n, int max_faces) {
+    int carried = 0;
+    for (int64_t j = 0; j < n && j < max_faces; ++j) {
+        bool ok = true;
+        for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(rows[j * 10 + q]);
+        carried += ok ? 1 : 0;
+    }
+    return carried;
+}
+
 void tracker_create(hg_cascade* c, hg_eyes* e, const hg_tracked_consts* consts, int max_faces, int rescan_every, hg_tracker** out) {
     if (!out) hg::fail(HG_ERR_ARG, "null output handle pointer");
     *out = nullptr;
@@ -1695,76 +1705,51 @@ void tracker_step(hg_tracker* t, const void* frame_dev, int frame_h, int frame_w
     *n_out = 0;
     if (n_before_purge) *n_before_purge = 0;
     if (used_tracked_grid) *used_tracked_grid = 0;
-    const void* fr;
-    int fh, fw;
-    int64_t fld;
-    prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream, fr, fh, fw, fld);
-    if (t->held && (fw != t->w || fh != t->h)) t->held = 0;      // the boxes mean nothing on another frame size
+    const hg::FrameSource fr = prescale_frame(c, frame_dev, frame_h, frame_w, ld, prescale_w, prescale_h, stream);
+    if (t->held && (fr.w != t->w || fr.h != t->h)) t->held = 0;      // the boxes mean nothing on another frame size
     if (n_held) *n_held = t->held;
-    int64_t n = 0;
-    int cur = 0;
-    const double* purged = nullptr;
-    const int32_t* counts = nullptr;
     // the path rule, on the host: nothing held (a size change drops every box), or rescan_every tracked steps in a row behind us
     if (!t->held || (t->rescan_every > 0 && t->tracked_run >= t->rescan_every)) {
         // what hg_cascade_detect_faces_frame_device runs, then the first rows (if any) become the tracked faces
         const LevelTable T = make_level_table(levels, n_levels);
-        const int64_t n0 = T.first[T.n_levels];
-        detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, &T, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur);
-        hg::eyes_frame_tail(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n,
-                            out_rows, out_cap, n_out, n_before_purge, st);
-        int carried = 0;      // the hand-over's rule, on the rows the host has already
-        for (int64_t j = 0; j < *n_out && j < t->max_faces; ++j) {
-            bool ok = true;
-            for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(out_rows[j * 10 + q]);
-            carried += ok ? 1 : 0;
-        }
+        const StagePass P = StagePass::grid(fr, T);
+        const PassResult r = run_pass(c, P, stage_counts, rows_executed, stream);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, fr, survivors_of(c, P, r), st);
+        hg::eyes_tail_read(e, tail, out_rows, out_cap, n_out, n_before_purge, st);
+        const int carried = carried_rows(out_rows, *n_out, t->max_faces);
         if (carried) {      // the boxes go from the purge's device rows into the tracker's state, in stream order before the next frame
-            hg::eyes_tail_buffers(e, &purged, &counts);
-            hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->held_dev(), t->max_faces, SlotChain{}, TrackerResults{}, 0);
+            hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, tail.purged, tail.counts, t->box_dev(), t->held_dev(), t->max_faces, SlotChain{}, TrackerResults{}, 0);
             HG_HIP(hipGetLastError());
         } else {
             HG_HIP(hipMemsetAsync(t->held_dev(), 0, 4, st));
         }
         t->held = carried;
         t->tracked_run = 0;
-        t->w = fw;
-        t->h = fh;
+        t->w = fr.w;
+        t->h = fr.h;
         for (int64_t j = 0; slots && j < *n_out; ++j) slots[j] = -1;      // no held face stands behind a row of the full grid
         if (n_held) *n_held = carried;
         return;
     }
     // the tracked frame: everything enqueued back to back, one wait at the end
     if (used_tracked_grid) *used_tracked_grid = 1;
-    const int64_t n0 = (int64_t)kTracked * t->held;
-    Bounded B{};
-    B.face_dev = t->box_dev();
-    B.n_faces = t->held;
-    B.tc = t->tc;
-    detect_impl(c, fr, fh, fw, fld, nullptr, nullptr, nullptr, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, stage_counts, rows_executed, stream, &cur, &B);
-    SlotChain S{};
-    hg::eyes_frame_tail_bounded(e, fr, fh, fw, fld, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p, (const double*)c->conf[cur].p, n0,
-                                B.final_count, &purged, &counts, &S.row_src, &S.kept_idx, st);
-    S.oidx = (const int32_t*)c->oidx[cur].p;
+    const StagePass P = StagePass::tracked(fr, t->tc, t->box_dev(), t->held);
+    const PassResult r = run_pass(c, P, stage_counts, rows_executed, stream);
+    const hg::EyeTail tail = hg::eyes_tail_enqueue(e, fr, survivors_of(c, P, r), st);
+    const SlotChain S{tail.kept_idx, tail.row_src, (const int32_t*)c->oidx[r.cur].p};
     TrackerResults R{};
     R.words = (int32_t*)t->host_res;
     R.rows = (double*)(t->host_res + 64);
     R.cap = t->rows_cap();
     R.slots = (int32_t*)(t->host_res + 64 + (size_t)R.cap * 80);
     const int32_t seq = ++t->seq;
-    hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, purged, counts, t->box_dev(), t->held_dev(), t->max_faces, S, R, seq);
+    hipLaunchKernelGGL(k_tracker_handover, 1, 128, 0, st, tail.purged, tail.counts, t->box_dev(), t->held_dev(), t->max_faces, S, R, seq);
     HG_HIP(hipGetLastError());
-    // the one wait: the sequence word is polled (a stream synchronisation costs 20-40 us more, see publish_count); a deadline guards
-    // against a device that never answers
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; __atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) != seq; ++spins) {
-        if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-            HG_HIP(hipStreamSynchronize(st));
-            if (__atomic_load_n(R.words + 3, __ATOMIC_ACQUIRE) == seq) break;
-            t->held = 0;
-            hg::fail(HG_ERR_DEVICE, "tracked frame did not report its result");
-        }
-        __builtin_ia32_pause();
+    try {      // the one wait
+        wait_for_seq(R.words + 3, seq, st, "tracked frame did not report its result");
+    } catch (...) {
+        t->held = 0;
+        throw;
     }
     const int64_t kept = R.words[0];
     if (n_before_purge) *n_before_purge = R.words[1];
@@ -1893,7 +1878,7 @@ void check_stream_set(int n_streams, int max_faces, int rescan_every) {
     if (n_streams < 1 || n_streams > HG_MAX_STACK_FRAMES) hg::fail(HG_ERR_ARG, "n_streams %d outside 1..%d", n_streams, HG_MAX_STACK_FRAMES);
     if (max_faces < 1 || max_faces > kMaxFaces) hg::fail(HG_ERR_ARG, "max_faces %d outside 1..%d", max_faces, kMaxFaces);
     // the bounded stage loop pads its filler rows on k_cascade_group's single-workgroup path only (pad_to); above 2 * kChunk
-    // candidates detect_impl takes the two-launch chunk path, which has no padding
+    // candidates run_groups takes the two-launch chunk path, which has no padding
     if ((int64_t)kTracked * n_streams * max_faces > HG_MAX_STREAM_WINDOWS)
         hg::fail(HG_ERR_ARG, "%d streams of %d faces: %lld tracked windows, at most %d", n_streams, max_faces, (long long)kTracked * n_streams * max_faces,
                  HG_MAX_STREAM_WINDOWS);
@@ -1940,12 +1925,9 @@ void stream_tracker_step(hg_stream_tracker* t, const void* frames_dev, int n_fra
     int64_t stride_t = frame_stride, stride_g = frame_stride, fld_t = ld, fld_g = ld;
     if (conv) {
         c->frame_stack.alloc(slot * 2 * Bn);
-        int g = 0, fh, fw;
-        int64_t fld;
-        for (int s = 0; s < Bn; ++s) {
-            const void* one;
+        for (int s = 0, g = 0; s < Bn; ++s) {
             const size_t at = in_g[(size_t)s] ? (size_t)Bn + g++ : (size_t)s;
-            prescale_frame(c, (const char*)frames_dev + (int64_t)s * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream, one, fh, fw, fld,
+            prescale_frame(c, (const char*)frames_dev + (int64_t)s * frame_stride, frame_h, frame_w, ld, prescale_w, prescale_h, stream,
                            (char*)c->frame_stack.p + slot * at);
         }
         fr_t = c->frame_stack.p;
@@ -1970,33 +1952,18 @@ void stream_tracker_step(hg_stream_tracker* t, const void* frames_dev, int n_fra
     if (nT) {
         for (int s : gs)      // due for a rescan: its boxes take no part (the full-grid pass's hand-over writes the count again)
             if (t->held[(size_t)s]) HG_HIP(hipMemsetAsync(t->held_dev() + s, 0, 4, st));
-        Bounded B{};
-        B.face_dev = t->box_dev();
-        B.n_faces = (int)held_sum;
-        B.tc = t->tc;
-        B.held_dev = t->held_dev();
-        B.n_streams = Bn;
-        B.max_faces = K;
-        const FrameStack FS{Bn, stride_t, (int64_t)kTracked * K};
-        const int64_t n0 = (int64_t)kTracked * held_sum;
-        int64_t n = 0;
-        int cur = 0;
-        detect_impl(c, fr_t, oh, ow, fld_t, nullptr, nullptr, nullptr, n0, nullptr, nullptr, nullptr, nullptr, n0, &n, nullptr, &rows_t, stream, &cur, &B, &FS);
-        SlotChain S{};
-        const double* purged = nullptr;
-        const int32_t *seg_first = nullptr, *seg_kept = nullptr;
-        hg::eyes_frames_tail_bounded(e, fr_t, Bn, stride_t, oh, ow, fld_t, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
-                                     (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, FS.n0, n0, B.final_count, &purged, &seg_first, &seg_kept,
-                                     &S.row_src, &S.kept_idx, st);
-        S.oidx = (const int32_t*)c->oidx[cur].p;
+        const StagePass P = StagePass::tracked(hg::FrameSource::stack(fr_t, oh, ow, fld_t, Bn, stride_t), t->tc, t->box_dev(), (int)held_sum, t->held_dev(), K);
+        const PassResult r = run_pass(c, P, nullptr, &rows_t, stream);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, P.frames, survivors_of(c, P, r), st);
+        const SlotChain S{tail.kept_idx, tail.row_src, (const int32_t*)c->oidx[r.cur].p};
         TrackerResults R{};
         R.words = t->res_words();
         R.rows = t->res_rows();
         R.slots = t->res_slots();
         R.cap = cap;
         seq = ++t->seq;
-        hipLaunchKernelGGL(k_stream_handover, (unsigned)Bn, 128, 0, st, purged, seg_first, seg_kept, (const int32_t*)nullptr, t->box_dev(), t->held_dev(), K, S,
-                           (int)FS.n0, R);
+        hipLaunchKernelGGL(k_stream_handover, (unsigned)Bn, 128, 0, st, tail.purged, tail.seg_first, tail.seg_kept, (const int32_t*)nullptr, t->box_dev(), t->held_dev(),
+                           K, S, (int)P.period(), R);
         hipLaunchKernelGGL(k_publish_seq, 1, 1, 0, st, (int32_t*)t->host_res, seq);
         HG_HIP(hipGetLastError());
     }
@@ -2005,52 +1972,31 @@ void stream_tracker_step(hg_stream_tracker* t, const void* frames_dev, int n_fra
     std::vector<double> g_rows;
     std::vector<int32_t> g_first((size_t)nG + 1, 0), g_before((size_t)nG, 0);
     if (nG) {
-        const int64_t n0 = T.first[T.n_levels], total = n0 * nG;
-        const FrameStack FS{nG, stride_g, n0};
-        int64_t n = 0;
-        int cur = 0;
-        detect_impl(c, fr_g, oh, ow, fld_g, nullptr, nullptr, &T, total, nullptr, nullptr, nullptr, nullptr, total, &n, nullptr, &rows_g, stream, &cur, nullptr, &FS);
-        g_rows.resize((size_t)(n + nG) * 10);
-        hg::eyes_frames_tail(e, fr_g, nG, stride_g, oh, ow, fld_g, (const double*)c->coords[cur].p, (const double*)c->angles[cur].p,
-                             (const double*)c->conf[cur].p, (const int32_t*)c->oidx[cur].p, n0, n, g_rows.data(), n + nG, g_first.data(), g_before.data(), st);
-        if (n > 0) {      // the first rows of every stream become its held faces: the purge's device rows into the state, in stream order
-            const double* purged = nullptr;
-            const int32_t *seg_first = nullptr, *seg_kept = nullptr;
-            hg::eyes_frames_buffers(e, nG, &purged, &seg_first, &seg_kept);
-            int32_t* gmap = t->res_gmap();      // (the tail above has synchronised the stream: no earlier kernel still reads it)
+        const StagePass P = StagePass::grid(hg::FrameSource::stack(fr_g, oh, ow, fld_g, nG, stride_g), T);
+        const PassResult r = run_pass(c, P, nullptr, &rows_g, stream);
+        g_rows.resize((size_t)(r.n + nG) * 10);
+        const hg::EyeTail tail = hg::eyes_tail_enqueue(e, P.frames, survivors_of(c, P, r), st);
+        hg::eyes_tail_read_frames(tail, g_rows.data(), r.n + nG, g_first.data(), g_before.data(), st);
+        if (r.n > 0) {      // the first rows of every stream become its held faces: the purge's device rows into the state, in stream order
+            int32_t* gmap = t->res_gmap();      // (the read above has synchronised the stream: no earlier kernel still reads it)
             for (int g = 0; g < nG; ++g) gmap[g] = gs[(size_t)g];
-            hipLaunchKernelGGL(k_stream_handover, (unsigned)nG, 128, 0, st, purged, seg_first, seg_kept, (const int32_t*)gmap, t->box_dev(), t->held_dev(), K,
-                               SlotChain{}, kTracked * K, TrackerResults{});
+            hipLaunchKernelGGL(k_stream_handover, (unsigned)nG, 128, 0, st, tail.purged, tail.seg_first, tail.seg_kept, (const int32_t*)gmap, t->box_dev(),
+                               t->held_dev(), K, SlotChain{}, kTracked * K, TrackerResults{});
             HG_HIP(hipGetLastError());
         } else if (nG == Bn) {
             HG_HIP(hipMemsetAsync(t->held_dev(), 0, (size_t)Bn * 4, st));
         } else {
             for (int s : gs) HG_HIP(hipMemsetAsync(t->held_dev() + s, 0, 4, st));
         }
-        for (int g = 0; g < nG; ++g) {      // the hand-over's rule, on the rows the host has already
+        for (int g = 0; g < nG; ++g) {
             const int s = gs[(size_t)g];
-            int carried = 0;
-            for (int64_t j = g_first[(size_t)g]; j < g_first[(size_t)g + 1] && j < g_first[(size_t)g] + K; ++j) {
-                bool ok = true;
-                for (int q = 0; q < 4 && ok; ++q) ok = std::isfinite(g_rows[(size_t)j * 10 + q]);
-                carried += ok ? 1 : 0;
-            }
-            t->held[(size_t)s] = carried;
+            t->held[(size_t)s] = carried_rows(g_rows.data() + (size_t)g_first[(size_t)g] * 10, g_first[(size_t)g + 1] - g_first[(size_t)g], K);
             t->run[(size_t)s] = 0;
         }
     }
-    // 3. the one wait of the tracked pass: the sequence word is polled (publish_count); a deadline guards against a device that never answers
+    // 3. the one wait of the tracked pass
     if (nT) {
-        int32_t* word = (int32_t*)t->host_res;
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != seq; ++spins) {
-            if ((spins & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                HG_HIP(hipStreamSynchronize(st));
-                if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) break;
-                hg::fail(HG_ERR_DEVICE, "tracked pass did not report its result");
-            }
-            __builtin_ia32_pause();
-        }
+        wait_for_seq((const int32_t*)t->host_res, seq, st, "tracked pass did not report its result");
         const int32_t* words = t->res_words();
         for (int s = 0; s < Bn; ++s) {
             if (in_g[(size_t)s]) continue;

@@ -207,6 +207,37 @@ struct FrameList {
 void put_frame_descs(const FrameDesc* host, int n_frames, FrameDesc* dev, hipStream_t st);
 int patcher_extract_frame_list(hg_patcher* p, const FrameList& fl, int filter, const double* boxes_dev, const double* delta_angs_dev,
                                const int32_t* row_frame_dev, int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
+
+// The grey uint8 frames a pass reads (the cascade's stage loop, the eye step), one of: ONE frame; a STACK of n_frames frames of one
+// size, `stride` bytes apart, px its frame 0 (a stack of one frame is still a stack: it runs the stack's kernels); a LIST of frames
+// of different sizes, alive while the source is used — px .. ld are then its frame 0's, what the kernels' own frame arguments carry.
+struct FrameSource {
+    enum Kind { ONE, STACK, LIST } kind = ONE;
+    const void* px = nullptr;
+    int h = 0, w = 0;
+    int64_t ld = 0;
+    int n_frames = 1;
+    int64_t stride = 0;
+    const FrameList* list = nullptr;
+    static FrameSource one(const void* px, int h, int w, int64_t ld) { return {ONE, px, h, w, ld}; }
+    static FrameSource stack(const void* px, int h, int w, int64_t ld, int n_frames, int64_t stride) { return {STACK, px, h, w, ld, n_frames, stride}; }
+    static FrameSource of_list(const FrameList& fl) {
+        const FrameDesc d0 = fl.host && fl.n_frames > 0 ? fl.host[0] : FrameDesc{};
+        return {LIST, d0.px, d0.h, d0.w, d0.ld, fl.n_frames, 0, &fl};
+    }
+};
+// How row i of a batch finds its frame in a source of several.  windows: index_dev holds the cascade's original-window indices — a
+// stack's frame is index / period (period: the windows of one frame, and under a key the tables of the first `period` boxes serve every
+// frame's copy of them), a list's is win_frame_dev[index]; else (the eye step) index_dev holds the frame index of every row itself.
+struct RowFrames {
+    const int32_t* index_dev;
+    bool windows;
+    int64_t period;
+};
+// hg_extract.hip: whichever of the three dispatches above the source calls for.  key (0: none): as for patcher_extract; a list's shared
+// first-stage tables are kept under it (the key of the whole list) and are not looked at without it.  A single frame ignores `rows`.
+int patcher_extract_source(hg_patcher* p, const FrameSource& src, uint64_t key, RowFrames rows, int filter, const double* boxes_dev, const double* delta_angs_dev,
+                           int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream);
 // hg_extract.hip: NEAREST, unrotated windows from a frame of format HG_FRAME_* (ld_bytes: row stride in bytes), the tables kept under
 // `key` as above.  What hg_patcher_extract_format_device (key = 0) and the cascade's prescale of a colour frame call.
 int patcher_extract_format(hg_patcher* p, uint64_t key, int format, const void* frame_dev, int frame_h, int frame_w, int64_t ld_bytes, const double* boxes_dev,
@@ -220,5 +251,38 @@ int patcher_device(const hg_patcher* p);
 // hg_normalize.hip: pose-normalised face crops (hg_patcher_normalize_device); its state hangs off the patcher the same way.
 void normalize_state_free(void* state);
 void*& patcher_normalize_state(hg_patcher* p);
+
+// hg_eyes.hip: the tail of every faces entry and tracker step of hg_cascade.hip — the eye step on the cascade's survivors as ONE
+// batch, the discard, the 10-column rows and the purge, all enqueued on the stream; a reader then fetches the result, or the caller's
+// own last kernel does (the trackers' hand-over).  The survivors are device arrays, ordered by frame (the compaction keeps the
+// candidates' order).  A row's frame is read off its original window: index / period in a stack, win_frame_dev[index] in a list.
+struct EyeSurvivors {
+    const double *boxes, *angles, *conf;
+    const int32_t* orig_index;
+    int64_t period;           // a stack: original windows per frame
+    int64_t n;                // their number — or, with n_dev, the host's bound of it (>= 1): every launch is sized by the bound
+    const int32_t* n_dev;     // nullable: the live count is this device word and NOTHING is read back.  Rows between the live count and
+                              // the bound carry index 0 (frame 0) and a window k_eye_boxes replaces; a live count of 0 runs through
+                              // every launch and gives counts of 0.  The kept indices a tracker's slots are made of are written then.
+};
+// What a tail leaves on the device until the handle's next call.  One frame: the purge ran once, `purged` holds the kept rows (room for
+// n + 1) and counts = {faces after the discard, faces after the purge}.  A stack or a list: the purge ran PER FRAME (it is a per-image
+// rule), frame f's kept rows start at row seg_first[f] + f of `purged`, seg_kept[f] of them, out of seg_first[f + 1] - seg_first[f]
+// assembled rows; seg_kept follows seg_first (n_frames + 1 words) in memory.  row_src: for every assembled row the survivor it was made
+// from; kept_idx (with n_dev only): for every kept row the assembled row it is — per frame from entry seg_first[f] + f on and relative
+// to the frame's first row.  n == 0: nothing was launched and every pointer is null.
+struct EyeTail {
+    const double* purged;
+    const int32_t *counts, *seg_first, *seg_kept, *row_src, *kept_idx;
+    int n_frames;
+    int64_t n;
+};
+EyeTail eyes_tail_enqueue(hg_eyes* e, const FrameSource& src, const EyeSurvivors& s, hipStream_t st);
+// The one read-back of a single frame's tail (n_out, n_before_purge: zero when there were no survivors) ...
+void eyes_tail_read(hg_eyes* e, const EyeTail& t, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st);
+// ... and of a pooled one: frame f's kept rows are out_rows[frame_first[f] .. frame_first[f + 1]); n_before_purge (n_frames, nullable)
+void eyes_tail_read_frames(const EyeTail& t, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
+int eyes_device(const hg_eyes* e);
+int eyes_filter(const hg_eyes* e);
 
 }  // namespace hg

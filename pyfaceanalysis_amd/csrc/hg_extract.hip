@@ -1325,6 +1325,25 @@ int patcher_extract_frame_list(hg_patcher* p, const FrameList& fl, int filter, c
         HG_HIP(hipGetLastError());
     });
 }
+
+// One of the three dispatches above, by the kind of the source (hg_common.hpp)
+int patcher_extract_source(hg_patcher* p, const FrameSource& src, uint64_t key, RowFrames rows, int filter, const double* boxes_dev, const double* delta_angs_dev,
+                           int64_t n, int out_w, int out_h, void* out_dev, int out_dtype, int64_t ldo, void* stream) {
+    if (src.kind == FrameSource::ONE)
+        return patcher_extract(p, key, filter, src.px, HG_U8, src.h, src.w, src.ld, boxes_dev, delta_angs_dev, n, out_w, out_h, out_dev, out_dtype, ldo, stream);
+    if (src.kind == FrameSource::STACK)
+        return patcher_extract_frames(p, key, rows.windows ? rows.period : 0, filter, src.px, src.n_frames, src.stride, src.h, src.w, src.ld, boxes_dev,
+                                      delta_angs_dev, rows.index_dev, rows.windows ? (int)rows.period : 1, n, out_w, out_h, out_dev, out_dtype, ldo, stream);
+    if (!src.list) return guarded([] { fail(HG_ERR_ARG, "null pointer"); });
+    FrameList fl = *src.list;
+    fl.key = key;      // (the concatenated grids are the first stage's boxes only: no key behind it)
+    if (!rows.windows) {      // a frame index per row, a table per box
+        fl.win_frame_dev = nullptr;
+        fl.n_windows = 0;
+        fl.tab_rows = 0;
+    }
+    return patcher_extract_frame_list(p, fl, filter, boxes_dev, delta_angs_dev, rows.index_dev, n, out_w, out_h, out_dev, out_dtype, ldo, stream);
+}
 }  // namespace hg
 
 extern "C" int hg_patcher_extract_frame_list_device(hg_patcher* p, int filter, const hg_frame_ref* frames, int n_frames, const double* boxes_dev,

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "hg_common.hpp"
+#include "hg_frame_list.hpp"
 #include "hg_gauss_dev.hpp"
 
 namespace hg { void set_last_error(const std::string& s); }
@@ -40,7 +41,7 @@ struct hg_eyes {
     hg::DevBuf eboxes, dang, pu8, pf32, sl, sl2, reg, ecoords, toofar, rows, purged, scratch, count;
     hg::DevBuf row_src, kept_idx;        // a tracker's slots: the face of every assembled row, the assembled row of every kept row
     int32_t* host_words = nullptr;       // pinned: {faces after the discard, faces after the purge}
-    hg::DevBuf row_frame, seg;           // a frame stack (eyes_frames_tail): the frame of every eye row; first row of every frame (n_frames + 1), rows kept per frame
+    hg::DevBuf row_frame, seg;           // a per-frame purge (eyes_tail_enqueue): the frame of every eye row; first row of every frame (n_frames + 1), rows kept per frame
 
     void reserve(int64_t n) {
         if (n <= cap) return;
@@ -360,7 +361,7 @@ __global__ void __launch_bounds__(1024) k_purge(const double* __restrict__ rows,
 }
 
 // ---- a stack of frames: the purge is a per-image rule, so it runs per frame -----------------------------------------------------------
-// The frame of every eye row of n faces (left eyes [0, n), right eyes [n, 2n)): the face's original window / n0 (hg_cascade.hip, FrameStack)
+// The frame of every eye row of n faces (left eyes [0, n), right eyes [n, 2n)): the face's original window / n0 (hg_cascade.hip, StagePass::period)
 __global__ void k_eye_row_frames(int64_t n, const int32_t* __restrict__ orig_index, int n0, int32_t* __restrict__ row_frame) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -382,7 +383,7 @@ __global__ void __launch_bounds__(1024) k_frame_segments(const int32_t* __restri
     }
 }
 
-// The two kernels above for a LIST of frames of different sizes (hg_cascade.hip, ListRun): the frame of original window o is
+// The two kernels above for a LIST of frames of different sizes (hg_cascade.hip, GRID_LIST): the frame of original window o is
 // win_frame[o], the array k_cascade_init_list wrote (n_windows entries) — no division by a common n0.  An index outside the windows is
 // frame -1 (k_eye_row_frames_list: an all-zero eye row) or ends the segments (k_frame_segments_list), as an index beyond the stack does.
 __global__ void k_eye_row_frames_list(int64_t n, const int32_t* __restrict__ orig_index, const int32_t* __restrict__ win_frame, int n_windows,
@@ -438,16 +439,10 @@ void launch_purge(const double* rows, int64_t n_max, const int32_t* n_dev, doubl
 // discard and the row assembly as well (conf needed then).  n_dev (nullable): the face count stays on the device and n bounds it —
 // every launch is sized by n; k_eye_boxes gives the faces past the live count a defined window, so the extraction, the contrast
 // step and the networks read defined data in all 2n rows, and k_eyes_glue assembles the live faces only.
-// F (nullable): frame_dev is frame 0 of a stack and eye row i is cut from frame F->row_frame[i] (hg::patcher_extract_frames)
-struct EyeFrames {
-    int n_frames;
-    int64_t stride;
-    const int32_t* row_frame;      // 2n entries, on the device
-    const hg::FrameList* list = nullptr;      // a list of frames of different sizes: eye row i is cut from frame list[row_frame[i]] (hg::patcher_extract_frame_list)
-};
-void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles, const double* conf,
-              int64_t n, double* ecoords, uint8_t* toofar, float* patches, double* reg, double* rows, int32_t* count, hipStream_t st,
-              const int32_t* n_dev = nullptr, int32_t* row_src = nullptr, const EyeFrames* F = nullptr) {
+// row_frame (2n entries on the device; a source of several frames): eye row i is cut from frame row_frame[i]
+void eyes_run(hg_eyes* e, const hg::FrameSource& src, const double* boxes, const double* angles, const double* conf, int64_t n, double* ecoords, uint8_t* toofar,
+              float* patches, double* reg, double* rows, int32_t* count, hipStream_t st, const int32_t* n_dev = nullptr, int32_t* row_src = nullptr,
+              const int32_t* row_frame = nullptr) {
     if (n == 0) {
         if (count) HG_HIP(hipMemsetAsync(count, 0, 4, st));
         return;
@@ -457,14 +452,9 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
     const int64_t wh = (int64_t)c.eye_w * c.eye_h, n2 = 2 * n;
     hipLaunchKernelGGL(k_eye_boxes, (unsigned)((n + 255) / 256), 256, 0, st, n, n_dev, boxes, angles, c, (double*)e->eboxes.p, (double*)e->dang.p);
     HG_HIP(hipGetLastError());
-    const int rc_x = F && F->list
-                         ? hg::patcher_extract_frame_list(e->patcher, *F->list, e->filter, (const double*)e->eboxes.p, (const double*)e->dang.p, F->row_frame, n2,
-                                                          c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st)
-                     : F ? hg::patcher_extract_frames(e->patcher, 0, 0, e->filter, frame_dev, F->n_frames, F->stride, frame_h, frame_w, ld, (const double*)e->eboxes.p,
-                                                    (const double*)e->dang.p, F->row_frame, 1, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st)
-                       : hg_patcher_extract_filter_device(e->patcher, e->filter, frame_dev, HG_U8, frame_h, frame_w, ld, (const double*)e->eboxes.p,
-                                                          (const double*)e->dang.p, n2, c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st);
-    if (rc_x != HG_OK) hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
+    if (hg::patcher_extract_source(e->patcher, src, 0, hg::RowFrames{row_frame, false, 0}, e->filter, (const double*)e->eboxes.p, (const double*)e->dang.p, n2,
+                                   c.eye_w, c.eye_h, e->pu8.p, HG_U8, wh, st) != HG_OK)
+        hg::fail(HG_ERR_DEVICE, "%s", hg_last_error());
     float* pf = patches ? patches : (float*)e->pf32.p;
     hipLaunchKernelGGL(k_eye_contrast, (unsigned)n2, 256, 0, st, (const uint8_t*)e->pu8.p, pf, wh, c.target_mean, c.target_std);
     HG_HIP(hipGetLastError());
@@ -489,187 +479,90 @@ void eyes_run(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64
 }  // namespace
 
 namespace hg {
-// The tail of hg_cascade_detect_faces_frame_device (hg_cascade.hip): the eye step on the cascade's n survivors (device arrays), the
-// discard, the rows and the purge; then the one read-back of the counts and the rows.
-void eyes_frame_tail(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                     const double* conf, int64_t n, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st) {
+// The one eye tail (hg_common.hpp).  The reserve comes before any workspace pointer is taken: eyes_run reserves too, but its arguments
+// are evaluated first — on a handle's first faces they were null (no rows written, the purge read an uninitialised count) and on growth
+// they were the freed buffers.  A per-frame purge reserves n + n_frames: the purged rows and the scratch hold count + 1 per frame.
+EyeTail eyes_tail_enqueue(hg_eyes* e, const FrameSource& src, const EyeSurvivors& s, hipStream_t st) {
+    const bool per_frame = src.kind != FrameSource::ONE, is_list = src.kind == FrameSource::LIST;
     if (!e) fail(HG_ERR_ARG, "null eye handle");
+    if (s.n_dev && s.n < 1) fail(HG_ERR_ARG, "bad bounded eye step");
+    if (is_list && (!src.list || !src.list->host || !src.list->dev || !src.list->win_frame_dev)) fail(HG_ERR_ARG, "null argument");
+    if (per_frame && (src.n_frames < 1 || (!is_list && s.period < 1))) fail(HG_ERR_ARG, "bad frame stack");
+    const int64_t n = s.n;
+    const int n_frames = per_frame ? src.n_frames : 0;
+    if (n == 0) return EyeTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n_frames, 0};
+    e->reserve(n + n_frames);
+    int32_t *seg_first = nullptr, *seg_kept = nullptr, *row_frame = nullptr;
+    int32_t* row_src = per_frame || s.n_dev ? (int32_t*)e->row_src.p : nullptr;
+    int32_t* kept_idx = s.n_dev ? (int32_t*)e->kept_idx.p : nullptr;
+    const int32_t* count = (const int32_t*)e->count.p;
+    if (per_frame) {
+        e->row_frame.alloc((size_t)n * 2 * 4);
+        e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
+        row_frame = (int32_t*)e->row_frame.p;
+        seg_first = (int32_t*)e->seg.p;
+        seg_kept = seg_first + n_frames + 1;
+        if (is_list)
+            hipLaunchKernelGGL(k_eye_row_frames_list, (unsigned)((n + 255) / 256), 256, 0, st, n, s.orig_index, src.list->win_frame_dev, (int)src.list->n_windows,
+                               row_frame);
+        else
+            hipLaunchKernelGGL(k_eye_row_frames, (unsigned)((n + 255) / 256), 256, 0, st, n, s.orig_index, (int)s.period, row_frame);
+        HG_HIP(hipGetLastError());
+    }
+    eyes_run(e, src, s.boxes, s.angles, s.conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st, s.n_dev, row_src, row_frame);
+    if (!per_frame) {
+        launch_purge((const double*)e->rows.p, n, count, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st, kept_idx);
+    } else {
+        if (is_list)
+            hipLaunchKernelGGL(k_frame_segments_list, 1, 1024, 0, st, (const int32_t*)row_src, count, s.orig_index, src.list->win_frame_dev,
+                               (int)src.list->n_windows, n_frames, seg_first);
+        else
+            hipLaunchKernelGGL(k_frame_segments, 1, 1024, 0, st, (const int32_t*)row_src, count, s.orig_index, (int)s.period, n_frames, seg_first);
+        if (kept_idx)
+            hipLaunchKernelGGL(k_purge_frames_kept, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p,
+                               seg_kept, (char*)e->scratch.p, kept_idx);
+        else
+            hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
+                               (char*)e->scratch.p);
+        HG_HIP(hipGetLastError());
+    }
+    return EyeTail{(const double*)e->purged.p, count, seg_first, seg_kept, row_src, kept_idx, n_frames, n};
+}
+
+void eyes_tail_read(hg_eyes* e, const EyeTail& t, double* out_rows, int64_t out_cap, int64_t* n_out, int64_t* n_before_purge, hipStream_t st) {
     *n_out = 0;
     if (n_before_purge) *n_before_purge = 0;
-    if (n == 0) return;
-    // before any workspace pointer is taken: eyes_run reserves too, but its arguments below are evaluated first — on a handle's
-    // first faces they were null (no rows written, the purge read an uninitialised count) and on growth they were the freed buffers
-    e->reserve(n);
-    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st);
-    launch_purge((const double*)e->rows.p, n, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st);
-    HG_HIP(hipMemcpyAsync(e->host_words, e->count.p, 8, hipMemcpyDeviceToHost, st));
+    if (t.n == 0) return;
+    HG_HIP(hipMemcpyAsync(e->host_words, t.counts, 8, hipMemcpyDeviceToHost, st));
     HG_HIP(hipStreamSynchronize(st));
     const int64_t kept = e->host_words[1];
     if (n_before_purge) *n_before_purge = e->host_words[0];
     if (kept > out_cap) fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)out_cap);
     if (kept > 0) {
         if (!out_rows) fail(HG_ERR_ARG, "null output rows");
-        HG_HIP(hipMemcpyAsync(out_rows, e->purged.p, (size_t)kept * 80, hipMemcpyDeviceToHost, st));
+        HG_HIP(hipMemcpyAsync(out_rows, t.purged, (size_t)kept * 80, hipMemcpyDeviceToHost, st));
         HG_HIP(hipStreamSynchronize(st));
     }
     *n_out = kept;
 }
 
-// The same tail for a tracked frame (hg_tracker_step_frame_device): the survivor count is the device word *n_dev, at most n_bound; the
-// eye step, the discard, the rows and the purge are enqueued and NOTHING is read back — the caller's last kernel fetches what the host
-// needs.  *purged: the kept rows (room for n_bound + 1); *counts: {faces after the discard, faces after the purge}, both on the device.
-// A live count of 0 runs through every launch: k_eyes_glue and k_purge then write counts of 0.
-// *row_src / *kept_idx: for every assembled row the survivor it was made from, for every kept row the assembled row it is (a tracker's
-// slots, k_tracker_handover).
-void eyes_frame_tail_bounded(hg_eyes* e, const void* frame_dev, int frame_h, int frame_w, int64_t ld, const double* boxes, const double* angles,
-                             const double* conf, int64_t n_bound, const int32_t* n_dev, const double** purged, const int32_t** counts,
-                             const int32_t** row_src, const int32_t** kept_idx, hipStream_t st) {
-    if (!e || !n_dev || n_bound < 1) fail(HG_ERR_ARG, "bad bounded eye step");
-    e->reserve(n_bound);      // before any workspace pointer is taken (see eyes_frame_tail)
-    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n_bound, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st,
-             n_dev, (int32_t*)e->row_src.p);
-    launch_purge((const double*)e->rows.p, n_bound, (const int32_t*)e->count.p, (double*)e->purged.p, (int32_t*)e->count.p + 1, e->scratch.p, st,
-                 (int32_t*)e->kept_idx.p);
-    *purged = (const double*)e->purged.p;
-    *counts = (const int32_t*)e->count.p;
-    *row_src = (const int32_t*)e->row_src.p;
-    *kept_idx = (const int32_t*)e->kept_idx.p;
-}
-
-void frames_tail_read(hg_eyes* e, int n_frames, int64_t n, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st);
-
-// The tail of hg_cascade_detect_faces_frames_device: the eye step on the n survivors of a STACK of frames as one batch (frame_dev: frame 0
-// of n_frames grey frames, frame_stride bytes apart; survivor i belongs to frame orig_index[i] / n0, the survivors are ordered by frame),
-// the discard and the rows, then the purge PER FRAME; one read-back of the per-frame counts and the rows at the end.
-// frame_first (n_frames + 1): frame f's kept rows are out_rows[frame_first[f] .. frame_first[f + 1]); n_before_purge (n_frames).
-void eyes_frames_tail(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const double* boxes,
-                      const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n, double* out_rows, int64_t out_cap,
-                      int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
-    if (!e || !frame_first) fail(HG_ERR_ARG, "null argument");
-    for (int f = 0; f <= n_frames; ++f) frame_first[f] = 0;
-    for (int f = 0; f < n_frames && n_before_purge; ++f) n_before_purge[f] = 0;
-    if (n == 0) return;
-    // before any workspace pointer is taken (see eyes_frame_tail); n + n_frames: the purged rows and the scratch hold count + 1 per frame
-    e->reserve(n + n_frames);
-    e->row_frame.alloc((size_t)n * 2 * 4);
-    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
-    int32_t* seg_first = (int32_t*)e->seg.p;
-    int32_t* seg_kept = seg_first + n_frames + 1;
-    hipLaunchKernelGGL(k_eye_row_frames, (unsigned)((n + 255) / 256), 256, 0, st, n, orig_index, (int)n0, (int32_t*)e->row_frame.p);
-    HG_HIP(hipGetLastError());
-    const EyeFrames F{n_frames, frame_stride, (const int32_t*)e->row_frame.p};
-    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st, nullptr,
-             (int32_t*)e->row_src.p, &F);
-    hipLaunchKernelGGL(k_frame_segments, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, (int)n0, n_frames, seg_first);
-    hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
-                       (char*)e->scratch.p);
-    HG_HIP(hipGetLastError());
-    frames_tail_read(e, n_frames, n, out_rows, out_cap, frame_first, n_before_purge, st);
-}
-
-// The tail of hg_cascade_detect_faces_frame_list_device: eyes_frames_tail for a LIST of frames of different sizes.  fl: the cascade's
-// list (descriptors on the device, win_frame_dev: the frame of every original window); survivor i belongs to frame
-// win_frame[orig_index[i]], the survivors are ordered by frame.  The eye rows carry their frame index itself.
-void eyes_frame_list_tail(hg_eyes* e, const FrameList& fl, const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n,
-                          double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
-    if (!e || !frame_first || !fl.host || !fl.dev || !fl.win_frame_dev || fl.n_frames < 1) fail(HG_ERR_ARG, "null argument");
-    const int n_frames = fl.n_frames;
-    for (int f = 0; f <= n_frames; ++f) frame_first[f] = 0;
-    for (int f = 0; f < n_frames && n_before_purge; ++f) n_before_purge[f] = 0;
-    if (n == 0) return;
-    e->reserve(n + n_frames);      // (see eyes_frames_tail)
-    e->row_frame.alloc((size_t)n * 2 * 4);
-    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
-    int32_t* seg_first = (int32_t*)e->seg.p;
-    int32_t* seg_kept = seg_first + n_frames + 1;
-    hipLaunchKernelGGL(k_eye_row_frames_list, (unsigned)((n + 255) / 256), 256, 0, st, n, orig_index, fl.win_frame_dev, (int)fl.n_windows, (int32_t*)e->row_frame.p);
-    HG_HIP(hipGetLastError());
-    FrameList rows = fl;      // the eye rows' own reading of the list: a frame index per row, a table per box
-    rows.win_frame_dev = nullptr;
-    rows.n_windows = 0;
-    rows.key = 0;
-    rows.tab_rows = 0;
-    const EyeFrames F{n_frames, 0, (const int32_t*)e->row_frame.p, &rows};
-    const FrameDesc& d0 = fl.host[0];
-    eyes_run(e, d0.px, d0.h, d0.w, d0.ld, boxes, angles, conf, n, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st, nullptr,
-             (int32_t*)e->row_src.p, &F);
-    hipLaunchKernelGGL(k_frame_segments_list, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, fl.win_frame_dev,
-                       (int)fl.n_windows, n_frames, seg_first);
-    hipLaunchKernelGGL(k_purge_frames, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)seg_first, (double*)e->purged.p, seg_kept,
-                       (char*)e->scratch.p);
-    HG_HIP(hipGetLastError());
-    frames_tail_read(e, n_frames, n, out_rows, out_cap, frame_first, n_before_purge, st);
-}
-
-// The one read-back of a pooled tail (eyes_frames_tail, eyes_frame_list_tail): the per-frame counts and the purged rows, to the caller's layout
-void frames_tail_read(hg_eyes* e, int n_frames, int64_t n, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
-    std::vector<int32_t> seg((size_t)2 * n_frames + 1);
-    std::vector<double> purged((size_t)(n + n_frames) * 10);
-    HG_HIP(hipMemcpyAsync(seg.data(), e->seg.p, seg.size() * 4, hipMemcpyDeviceToHost, st));
-    HG_HIP(hipMemcpyAsync(purged.data(), e->purged.p, purged.size() * 8, hipMemcpyDeviceToHost, st));      // (rows no frame wrote are never looked at)
+// (the bounds of the segment words and the placement of the rows are host-only code: hg_frame_list.hpp)
+void eyes_tail_read_frames(const EyeTail& t, double* out_rows, int64_t out_cap, int32_t* frame_first, int32_t* n_before_purge, hipStream_t st) {
+    if (!frame_first) fail(HG_ERR_ARG, "null argument");
+    for (int f = 0; f <= t.n_frames; ++f) frame_first[f] = 0;
+    for (int f = 0; f < t.n_frames && n_before_purge; ++f) n_before_purge[f] = 0;
+    if (t.n == 0) return;
+    std::vector<int32_t> seg((size_t)2 * t.n_frames + 1);
+    std::vector<double> purged((size_t)(t.n + t.n_frames) * 10);
+    HG_HIP(hipMemcpyAsync(seg.data(), t.seg_first, seg.size() * 4, hipMemcpyDeviceToHost, st));
+    HG_HIP(hipMemcpyAsync(purged.data(), t.purged, purged.size() * 8, hipMemcpyDeviceToHost, st));      // (rows no frame wrote are never looked at)
     HG_HIP(hipStreamSynchronize(st));
     int64_t kept = 0;
-    for (int f = 0; f < n_frames; ++f) {
-        const int64_t lo = seg[(size_t)f], nb = seg[(size_t)f + 1] - lo, kf = seg[(size_t)n_frames + 1 + f];
-        if (lo < 0 || nb < 0 || lo + nb > n || kf < 0 || kf > nb + 1) fail(HG_ERR_STATE, "frame %d: bad row bounds from the device", f);
-        kept += kf;
-    }
+    const std::string bad = tail_segments_refusal(seg.data(), t.n_frames, t.n, &kept);
+    if (!bad.empty()) fail(HG_ERR_STATE, "%s", bad.c_str());
     if (kept > out_cap) fail(HG_ERR_ARG, "%lld faces but room for %lld", (long long)kept, (long long)out_cap);
     if (kept > 0 && !out_rows) fail(HG_ERR_ARG, "null output rows");
-    int64_t at = 0;
-    for (int f = 0; f < n_frames; ++f) {
-        const int64_t lo = seg[(size_t)f], kf = seg[(size_t)n_frames + 1 + f];
-        frame_first[f] = (int32_t)at;
-        if (n_before_purge) n_before_purge[f] = (int32_t)(seg[(size_t)f + 1] - lo);
-        if (kf) memcpy(out_rows + at * 10, purged.data() + (size_t)(lo + f) * 10, (size_t)kf * 80);
-        at += kf;
-    }
-    frame_first[n_frames] = (int32_t)at;
-}
-
-// The stack tail for the TRACKED pass of a stream set (hg_stream_tracker_step_frames_device): eyes_frames_tail and eyes_frame_tail_bounded
-// combined.  The survivor count is the device word *n_dev, at most n_bound; survivor i belongs to frame orig_index[i] / n0 (the rows
-// between the live count and the bound carry index 0: frame 0, a window k_eye_boxes replaces anyway); the eye step runs on all n_bound
-// rows as one batch, the purge per frame with its kept indices, and NOTHING is read back.  *purged: frame f's kept rows from row
-// seg_first[f] + f on; *seg_first (n_frames + 1) / *seg_kept (n_frames): first assembled row and kept rows of every frame; *row_src /
-// *kept_idx: as eyes_frame_tail_bounded, kept_idx per frame from entry seg_first[f] + f on and relative to the frame's first row.
-void eyes_frames_tail_bounded(hg_eyes* e, const void* frame_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
-                              const double* boxes, const double* angles, const double* conf, const int32_t* orig_index, int64_t n0, int64_t n_bound,
-                              const int32_t* n_dev, const double** purged, const int32_t** seg_first, const int32_t** seg_kept, const int32_t** row_src,
-                              const int32_t** kept_idx, hipStream_t st) {
-    if (!e || !n_dev || n_bound < 1 || n_frames < 1 || n0 < 1) fail(HG_ERR_ARG, "bad bounded eye step");
-    e->reserve(n_bound + n_frames);      // before any workspace pointer is taken (see eyes_frame_tail); count + 1 rows per frame
-    e->row_frame.alloc((size_t)n_bound * 2 * 4);
-    e->seg.alloc((size_t)(2 * n_frames + 1) * 4);
-    int32_t* first = (int32_t*)e->seg.p;
-    int32_t* kept = first + n_frames + 1;
-    hipLaunchKernelGGL(k_eye_row_frames, (unsigned)((n_bound + 255) / 256), 256, 0, st, n_bound, orig_index, (int)n0, (int32_t*)e->row_frame.p);
-    HG_HIP(hipGetLastError());
-    const EyeFrames F{n_frames, frame_stride, (const int32_t*)e->row_frame.p};
-    eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes, angles, conf, n_bound, nullptr, nullptr, nullptr, nullptr, (double*)e->rows.p, (int32_t*)e->count.p, st,
-             n_dev, (int32_t*)e->row_src.p, &F);
-    hipLaunchKernelGGL(k_frame_segments, 1, 1024, 0, st, (const int32_t*)e->row_src.p, (const int32_t*)e->count.p, orig_index, (int)n0, n_frames, first);
-    hipLaunchKernelGGL(k_purge_frames_kept, (unsigned)n_frames, 1024, 0, st, (const double*)e->rows.p, (const int32_t*)first, (double*)e->purged.p, kept,
-                       (char*)e->scratch.p, (int32_t*)e->kept_idx.p);
-    HG_HIP(hipGetLastError());
-    *purged = (const double*)e->purged.p;
-    *seg_first = first;
-    *seg_kept = kept;
-    *row_src = (const int32_t*)e->row_src.p;
-    *kept_idx = (const int32_t*)e->kept_idx.p;
-}
-
-// What a stream set's hand-over kernel reads after eyes_frames_tail with n > 0 of a stack of n_frames: the same buffers.
-void eyes_frames_buffers(const hg_eyes* e, int n_frames, const double** purged, const int32_t** seg_first, const int32_t** seg_kept) {
-    *purged = (const double*)e->purged.p;
-    *seg_first = (const int32_t*)e->seg.p;
-    *seg_kept = (const int32_t*)e->seg.p + n_frames + 1;
-}
-
-// What the tracker's hand-over kernel reads after an ordinary frame's tail (eyes_frame_tail with n > 0): the same two buffers.
-void eyes_tail_buffers(const hg_eyes* e, const double** purged, const int32_t** counts) {
-    *purged = (const double*)e->purged.p;
-    *counts = (const int32_t*)e->count.p;
+    tail_place(seg.data(), purged.data(), t.n_frames, out_rows, frame_first, n_before_purge);
 }
 
 int eyes_device(const hg_eyes* e) { return e ? e->device : -1; }
@@ -742,8 +635,8 @@ int hg_eyes_locate_device(hg_eyes* e, const void* frame_dev, int frame_h, int fr
         if (n > 0 && (!frame_dev || !boxes_dev || !angles_dev || !eye_coords_dev || !too_far_dev)) hg::fail(HG_ERR_ARG, "null data pointer");
         if (frame_h <= 0 || frame_w <= 0 || ld < frame_w) hg::fail(HG_ERR_ARG, "bad frame shape");
         set_dev(e->device);
-        eyes_run(e, frame_dev, frame_h, frame_w, ld, boxes_dev, angles_dev, nullptr, n, eye_coords_dev, too_far_dev, patches_dev, reg_dev, nullptr,
-                 nullptr, (hipStream_t)stream);
+        eyes_run(e, hg::FrameSource::one(frame_dev, frame_h, frame_w, ld), boxes_dev, angles_dev, nullptr, n, eye_coords_dev, too_far_dev, patches_dev, reg_dev,
+                 nullptr, nullptr, (hipStream_t)stream);
     });
 }
 

@@ -1,7 +1,8 @@
 // The host-only part of the frame-LIST pass (include/higsfa.h, hg_cascade_detect_frame_list_device): what a list of hg_cascade_frame is
 // refused for, and the layout of its concatenated grids — first[], the distinct level tables, the rows of the shared first-stage tables
-// and the key of the whole list.  No HIP in here: hg_cascade.hip includes it, and tests/frame_list_driver.cpp runs it under the
-// sanitizers on its own.
+// and the key of the whole list — and what every pooled pass (stack or list) does on the host with what comes back: the split of the
+// survivors by frame, the bounds of an eye tail's segment words and the layout of its rows.  No HIP in here: hg_cascade.hip and
+// hg_eyes.hip include it, and tests/frame_list_driver.cpp and tests/pass_split_driver.cpp run it under the sanitizers on their own.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -137,6 +138,49 @@ inline std::string list_layout(const hg_cascade_frame* frames, int n_frames, int
     L.key = key ? key : 1;
     *out = std::move(L);
     return "";
+}
+
+// The survivors of a pooled pass, as the caller gets them: orig_index[i] (ascending by frame: the compaction keeps the candidates'
+// order) becomes the index within its frame's own grid, and frame_first (n_frames + 1) the first survivor of every frame.  first[f]
+// (n_frames entries): frame f's first original window — f * n0 for a stack, ListLayout::first for a list.
+inline void split_by_first(int32_t* orig_index, int64_t n, const int32_t* first, int n_frames, int32_t* frame_first) {
+    int f = 0;
+    frame_first[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        while (f + 1 < n_frames && orig_index[i] >= first[f + 1]) frame_first[++f] = (int32_t)i;
+        orig_index[i] -= first[f];
+    }
+    while (f < n_frames) frame_first[++f] = (int32_t)n;
+}
+
+// The segment words a pooled eye tail brings back from the device, seg = first[n_frames + 1] then kept[n_frames]: frame f assembled
+// rows [first[f], first[f + 1]) of n and kept kept[f] of them, at most one more than it had (the purge may append its first row a
+// second time).  "" and the number of kept rows of all frames, or what is wrong with them.
+inline std::string tail_segments_refusal(const int32_t* seg, int n_frames, int64_t n, int64_t* kept) {
+    *kept = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t lo = seg[f], nb = seg[f + 1] - lo, kf = seg[n_frames + 1 + f];
+        if (lo < 0 || nb < 0 || lo + nb > n || kf < 0 || kf > nb + 1) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "frame %d: bad row bounds from the device", f);
+            return msg;
+        }
+        *kept += kf;
+    }
+    return "";
+}
+// ... and the caller's layout of checked segments: frame f's kept rows, which start at row first[f] + f of `purged`, packed from
+// out_rows[frame_first[f]] on; n_before_purge (nullable): its assembled rows.
+inline void tail_place(const int32_t* seg, const double* purged, int n_frames, double* out_rows, int32_t* frame_first, int32_t* n_before_purge) {
+    int64_t at = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t lo = seg[f], kf = seg[n_frames + 1 + f];
+        frame_first[f] = (int32_t)at;
+        if (n_before_purge) n_before_purge[f] = (int32_t)(seg[f + 1] - lo);
+        if (kf) memcpy(out_rows + at * 10, purged + (size_t)(lo + f) * 10, (size_t)kf * 80);
+        at += kf;
+    }
+    frame_first[n_frames] = (int32_t)at;
 }
 
 }  // namespace hg
