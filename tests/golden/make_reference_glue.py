@@ -11,7 +11,9 @@ and numpy.linspace receives int(num) (the reference passes the float that numpy.
 
 Besides random inputs the fixture holds EDGE ROWS: inputs built with exact rational arithmetic so that the reference's comparison
 lands exactly on its threshold, and where a fused multiply-add (a * b + c rounded once) would decide the other way.  The
-generator asserts that every hazard kind has such a row.  No test imports this script; the tests read the .npz only."""
+generator asserts that every hazard kind has such a row.  The eye step's contrast rule (image_array_contrast_normalize_avg_std) is
+extracted too, on the crafted patches of tests/eye_tail_cases.py; its eye shift is not — the reference computes it inside
+find_Left_Right_eyes, which calls the networks (see contrast_fixture).  No test imports this script; the tests read the .npz only."""
 from __future__ import annotations
 
 import ast
@@ -30,7 +32,7 @@ OUT = os.path.join(HERE, "reference_glue.npz")
 
 FUNCTIONS = ("compute_sampling_values", "compute_posX_posY_values", "compute_subimage_coordinates_from_posX_posY_values",
              "update_current_subimage_coordinates", "identify_patches_to_discard", "compute_approximate_eye_boxes_coordinates",
-             "relative_error_detection", "purgue_detected_faces_angles_eyes_confidence")
+             "relative_error_detection", "purgue_detected_faces_angles_eyes_confidence", "image_array_contrast_normalize_avg_std")
 
 # the constants the product passes (grid.FACE_PIPELINE, cascade.DeviceCascade._consts, FaceDetectUpdated.py:113-115)
 NET_DX, NET_DY, NET_DANG, NET_MINS, NET_MAXS = 40.0, 20.0, 22.5, 0.694, 0.981
@@ -336,6 +338,27 @@ def purge_fixture(R, rng, out):
     out["purge_names"] = np.array(names)
 
 
+def contrast_fixture(R, out):
+    """image_array_contrast_normalize_avg_std on the crafted eye patches of tests/eye_tail_cases.py (constant, two-level, all zero, single
+    pixels off, narrow-band noise) at 16 x 16 and 24 x 20, two patches at 64 x 64, for every target pair of ``F_TARGETS``: the uint8
+    inputs and the function's float64 outputs (it works in place on a float64 copy).  The eye shift that follows it in the eye step is
+    NOT extracted: the reference computes it inside find_Left_Right_eyes, between the calls of its networks, not in a function of its
+    own; tests/eyes_restate.shift_eyes restates those lines."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests import eye_tail_cases as TC
+    kinds = np.zeros(4, dtype=np.int64)
+    for w, h in ((16, 16), (24, 20), (64, 64)):
+        u8 = TC.fixture_patches((w, h))
+        out["contrast_%dx%d_in" % (w, h)] = u8
+        for ti, (mean, std) in enumerate(TC.F_TARGETS):
+            x = u8.astype(np.float64)
+            R.image_array_contrast_normalize_avg_std(x, mean, std)
+            out["contrast_%dx%d_out%d" % (w, h, ti)] = x
+            kinds += np.array(TC.patch_kinds(u8, (mean, std)))
+    assert (kinds > 0).all(), kinds                         # std 0, clipped at 0, clipped at 255, all zero
+    out["contrast_targets"] = np.array(TC.F_TARGETS, dtype=np.float64)
+
+
 # ---- rotated windows: box centres where a fused m2 / m5 moves a 16.16 coefficient -------------------------------------------
 def pil_matrix(angle):
     """What Image.rotate builds (PIL's Image.py, Python floats): cos / sin of -radians(angle % 360) rounded to 15 decimals."""
@@ -463,6 +486,7 @@ def main(argv):
     eye_fixture(R, rng, out)
     purge_fixture(R, rng, out)
     rotation_fixture(rng, out)
+    contrast_fixture(R, out)
     np.savez_compressed(OUT, **out)
     print("%s: %d arrays, %d bytes; fma flips: %s" % (OUT, len(out), os.path.getsize(OUT),
                                                       {k: int(out["upd_%s_fma_flips" % k].sum()) for k in STAGES}))

@@ -116,6 +116,30 @@ def test_purge_restatement_equals_reference():
             assert np.array_equal(got, want, equal_nan=True), name
 
 
+def test_contrast_restatement_equals_reference():
+    """tests/eyes_restate.contrast (exact integer statistics) against image_array_contrast_normalize_avg_std on the crafted
+    eye patches of tests/eye_tail_cases.py — constant (std 0, divisor 1e-8), two-level, all zero, single pixels off, narrow-band noise —
+    at 16 x 16, 24 x 20 and 64 x 64 and three target pairs: the float32 of the reference's float64 output, element for element."""
+    g = load()
+    targets = g["contrast_targets"]
+    assert targets.shape == (3, 2) and [0.0, 0.16] in targets.tolist() and [128.0, 48.0] in targets.tolist()
+    seen = np.zeros(4, dtype=np.int64)                   # patches of std 0, with an output at the clip's 0, at its 255, all zero
+    n = 0
+    for size in ("16x16", "24x20", "64x64"):
+        u8 = g["contrast_%s_in" % size]
+        assert u8.dtype == np.uint8 and u8.shape[1] == int(size[:2]) * int(size[3:])
+        for ti, (mean, std) in enumerate(targets):
+            want = g["contrast_%s_out%d" % (size, ti)]
+            assert want.dtype == np.float64 and want.shape == u8.shape and want.min() >= 0.0 and want.max() <= 255.0
+            got = ER.contrast(u8, mean, std)
+            assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32)), (size, mean, std)
+            flat = np.array([not p.any() or len(np.unique(p)) == 1 for p in u8])
+            assert np.all(want[flat] == mean)
+            seen += [int(flat.sum()), int((want == 0.0).any(axis=1).sum()), int((want == 255.0).any(axis=1).sum()), int((~u8.any(axis=1)).sum())]
+            n += want.size
+    assert (seen > 0).all() and n > 80000, (seen, n)
+
+
 def rotated_pil_windows(frame, boxes, angs, size, m25=None):
     """Image.rotate about the box centre, then EXTENT (tests/test_grid_patches.py); with m25 given, the same through Image.transform(AFFINE)
     with that (m2, m5) in place of the ones Image.rotate computes (cos / sin of -radians(angle % 360) rounded to 15 decimals)."""
