@@ -941,6 +941,33 @@ int hg_estimator_estimate_frames_device(hg_estimator* e, int flags, const uint8_
                                         int frame_w, int64_t ld, const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n,
                                         double* out_dev, int64_t out_stride, float* patches_dev, float* features_dev, void* stream);
 
+/* --- Pose normalisation and estimation over a LIST of frames of different sizes (the rows of hg_cascade_detect_faces_frame_list_device) --
+ * The two entries above for a list: face i is cut from frames[face_frame_host[i]], a grey uint8 frame with its OWN pointer, size and row
+ * stride (hg_frame_ref, ld in BYTES; the descriptor array is host memory, consumed before the call returns).  Each result is DEFINED as
+ * what the single-frame entry returns for that face on its own frame, bit for bit (tests/test_estimate_frame_list_gpu.py).
+ * geoms_host[i] MUST HAVE BEEN COMPUTED FOR THE SIZE OF FACE i's OWN FRAME (hg_normalize_geometry_host with frames[face_frame_host[i]]'s
+ * frame_w, frame_h): a geom built for another size is refused.  The host resolves every face's frame into its record — one upload per
+ * call, as for the stack; no table of frames on the device.  A face whose index lies outside [0, n_frames) is treated like a refused
+ * face — an all-zero image, no address formed, its geom not looked at — and is NOT an error.  Staged and tap by tap, the flags, the
+ * 2^24 face bound, the records and the scratch as above; every grid and scratch size comes from the host geoms.  Frames of ONE size stay
+ * the stack entries' case.  Enqueued on `stream`; the host is not waited for.
+ * HG_ERR_ARG before anything is launched or written, reading nothing behind a frame pointer or out_dev: what the stack entry refuses about
+ * n, the flags, the output size and ldo, a null geoms_host / face_frame_host / out_dev with n > 0, n_frames < 1 or > HG_MAX_STACK_FRAMES,
+ * a null frames, ANY frame with frame_h <= 0, frame_w <= 0, ld < frame_w, a null frame_dev or more than 2^24 pixels per side — the
+ * message names the frame, and one bad frame refuses the whole call.  n == 0: HG_OK, nothing launched. */
+int hg_patcher_normalize_frame_list_device(hg_patcher* p, int flags, const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms_host,
+                                           const int32_t* face_frame_host, int64_t n, int out_w, int out_h, uint8_t* out_dev, int64_t ldo,
+                                           void* stream);
+/* hg_estimator_estimate_frames_device on the pooled faces of a list: the same chain on the same rows with the normalise entry above in
+ * front — one normalise, one patch step, one hg_flow_execute_device, the regressions, the finishing kernel.  out_dev ((4, n) float64,
+ * rows ldo >= n apart), patches_dev, features_dev, flags, the scratch and the one-stream rule as there.  A face whose frame index lies
+ * outside [0, n_frames) has NaN in all four rows.  Refusals: those of the entry above about the list, the geoms and face_frame_host,
+ * ldo < n, a null out_dev with n > 0, n above 2^20, bad flags.  n == 0: HG_OK, nothing launched.  The prescaled grey frames the rows of the
+ * cascade's list entries refer to are composed in Python (DeviceCascade.prescale_frame_list); there is no C entry for them. */
+int hg_estimator_estimate_frame_list_device(hg_estimator* e, int flags, const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms_host,
+                                            const int32_t* face_frame_host, int64_t n, double* out_dev, int64_t ldo, float* patches_dev,
+                                            float* features_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ HG_MAX_STREAM_WINDOWS = 8192    # 9 * n_streams * max_faces of a stream set (inc
 
 # HIGSFA_LIB: another build of the same library (same-box A/B of two commits, tools/build_ref_lib.sh) — never a different backend
 _LIB_PATH = os.environ.get("HIGSFA_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libhigsfa.so")
-# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks, the stream set, the frame lists
+# the only entries an older library selected with HIGSFA_LIB may lack (lib() below): the window filters, the step lanes, the colour frames, the multi-face tracker, the resize, the frame stacks, the stream set, the frame lists, estimation over a frame list
 _ENTRIES_SINCE_FILTERS = ("hg_patcher_extract_filter_device", "hg_patcher_extract_filter", "hg_cascade_set_interpolation", "hg_eyes_set_interpolation")
 _ENTRIES_SINCE_LANES = ("hg_flow_set_lanes", "hg_flow_lanes", "hg_flow_step_lane_device", "hg_flow_lane_done_event", "hg_flow_lane_join",
                         "hg_flow_check_errors", "hg_lane_stream_id", "hg_event_synchronize")
@@ -34,6 +34,7 @@ _ENTRIES_SINCE_ESTIMATE_FRAMES = ("hg_patcher_normalize_frames_device", "hg_esti
 _ENTRIES_SINCE_STREAM_SET = ("hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
                              "hg_cascade_tracked_grid_streams_device")
 _ENTRIES_SINCE_FRAME_LISTS = ("hg_patcher_extract_frame_list_device", "hg_cascade_detect_frame_list_device", "hg_cascade_detect_faces_frame_list_device")
+_ENTRIES_SINCE_ESTIMATE_FRAME_LIST = ("hg_patcher_normalize_frame_list_device", "hg_estimator_estimate_frame_list_device")
 _lib = None
 
 
@@ -186,6 +187,8 @@ def lib():
         "hg_estimator_estimate_device": (C.c_int, [vp, i32, vp, i32, i32, i64, vp, i64, vp, i64, vp, vp, vp]),
         "hg_patcher_normalize_frames_device": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, i64, vp, vp, i64, i32, i32, vp, i64, vp]),
         "hg_estimator_estimate_frames_device": (C.c_int, [vp, i32, vp, i32, i64, i32, i32, i64, vp, vp, i64, vp, i64, vp, vp, vp]),
+        "hg_patcher_normalize_frame_list_device": (C.c_int, [vp, i32, C.POINTER(HgFrameRef), i32, vp, vp, i64, i32, i32, vp, i64, vp]),
+        "hg_estimator_estimate_frame_list_device": (C.c_int, [vp, i32, C.POINTER(HgFrameRef), i32, vp, vp, i64, vp, i64, vp, vp, vp]),
         "hg_cascade_update_device": (C.c_int, [i32, i32, C.POINTER(HgCascadeConsts), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "hg_cascade_compact_device": (C.c_int, [i32, vp, i64, vp, vp, vp]),
         "hg_gather_rows_device": (C.c_int, [i32, vp, vp, i64, vp, vp, i64, vp]),
@@ -238,7 +241,8 @@ def lib():
             # those: calling one raises AttributeError there; any other missing symbol is a broken build and fails here
             if name in (_ENTRIES_SINCE_FILTERS + _ENTRIES_SINCE_LANES + _ENTRIES_SINCE_COLOR + _ENTRIES_SINCE_MULTI_TRACKING + _ENTRIES_SINCE_RESIZE +
                         _ENTRIES_SINCE_NORMALIZE + _ENTRIES_SINCE_ESTIMATION + _ENTRIES_SINCE_FRAME_STACKS +
-                        _ENTRIES_SINCE_ESTIMATE_FRAMES + _ENTRIES_SINCE_STREAM_SET + _ENTRIES_SINCE_FRAME_LISTS) and os.environ.get("HIGSFA_LIB"):
+                        _ENTRIES_SINCE_ESTIMATE_FRAMES + _ENTRIES_SINCE_STREAM_SET + _ENTRIES_SINCE_FRAME_LISTS +
+                        _ENTRIES_SINCE_ESTIMATE_FRAME_LIST) and os.environ.get("HIGSFA_LIB"):
                 continue
             raise
         fn.restype = res
@@ -272,6 +276,7 @@ EXPORTED_SYMBOLS = (
     "hg_stream_tracker_create", "hg_stream_tracker_free", "hg_stream_tracker_reset", "hg_stream_tracker_step_frames_device",
     "hg_cascade_tracked_grid_streams_device",
     "hg_patcher_extract_frame_list_device", "hg_cascade_detect_frame_list_device", "hg_cascade_detect_faces_frame_list_device",
+    "hg_patcher_normalize_frame_list_device", "hg_estimator_estimate_frame_list_device",
 )
 
 _EXC = {HG_ERR_ARG: ValueError, HG_ERR_FORMAT: ValueError, HG_ERR_DIM: ValueError,

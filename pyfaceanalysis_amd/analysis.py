@@ -276,6 +276,58 @@ class FaceAnalyzer(object):
         res = self.estimate_frames([] if stack is None else stack, eyes, face_frame, **kw)
         return [{k: v[int(first[f]):int(first[f + 1])] for k, v in res.items()} for f in range(b)]
 
+    def estimate_frame_list(self, frame_list, eyes=None, face_frame=None, geoms=None, return_intermediates=False, flags=0):
+        """``estimate`` for faces spread over a list of B frames of DIFFERENT sizes as ONE pooled chain
+        (hg_estimator_estimate_frame_list_device: the chain of ``estimate_frames`` with every face normalised from its own frame).
+        ``frame_list``: a list of (H, W) grey uint8 device tensors (``normalize.check_grey_list``) — for the rows of
+        ``detect_faces_frame_list`` the prescaled frames the cascade read, ``DeviceCascade.prescale_frame_list(frame_list)``; ``eyes``
+        (n, 4) in each face's own frame (or ``geoms``, record i for the size of face i's OWN frame); ``face_frame`` (n,) integers, the
+        frame of every face, in any order.  Returns the dict of ``estimate_frames`` — face i's values are, bit for bit, those of
+        ``estimate(frame_list[face_frame[i]], eyes[i:i + 1])`` — with one device-to-host copy of the (4, n) block, the call's only wait.
+        A face whose frame index is outside [0, B) has status ``normalize.STATUS_FRAME_RANGE``, NaN values and ``None`` labels.  An
+        empty list or n = 0 touches no library entry."""
+        import torch as t
+        frame_list = _normalize.check_grey_list(t, frame_list, "estimate_frame_list")      # layout first, then the faces, then the device
+        b = 0 if frame_list is None else len(frame_list)
+        if geoms is not None:
+            g = _normalize._check_geoms(geoms)
+            ff = _normalize.check_face_frame(face_frame, int(g.shape[0]))
+        else:
+            g, ff = self._norm.list_geometry(_normalize.list_sizes(frame_list), eyes, face_frame)
+        n = int(g.shape[0])
+        _normalize.check_list_device(frame_list, self.device, "estimate_frame_list")
+        status = np.where((ff < 0) | (ff >= b), _normalize.STATUS_FRAME_RANGE, g["status"]).astype(np.int32)
+        npix = self.patch_size[0] * self.patch_size[1]
+        if n == 0 or b == 0:
+            inter = (np.zeros((n, npix), dtype=np.float32), np.zeros((n, self.k), dtype=np.float32)) if return_intermediates else (None, None)
+            return self._result(np.full((4, n), np.nan), status, *inter)
+        dev = frame_list[0].device
+        out = t.empty((4, n), dtype=t.float64, device=dev)
+        pt = t.empty((n, npix), dtype=t.float32, device=dev) if return_intermediates else None
+        ft = t.empty((n, self.k), dtype=t.float32, device=dev) if return_intermediates else None
+        refs = _normalize.list_refs(frame_list)
+        _capi.check(_capi.lib().hg_estimator_estimate_frame_list_device(
+            self._handle(), int(flags), refs, b, g.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), n, out.data_ptr(), n,
+            None if pt is None else pt.data_ptr(), None if ft is None else ft.data_ptr(), t.cuda.current_stream(dev).cuda_stream))
+        return self._result(out.cpu().numpy(), status, pt, ft)
+
+    def estimate_faces_frame_list(self, frame_list, faces, **kw):
+        """The list of B (m_b, 10) arrays ``DeviceCascade.detect_faces_frame_list`` returns, on the frames the cascade read
+        (``DeviceCascade.prescale_frame_list(frame_list)``), through ONE ``estimate_frame_list``.  Returns a list of B dicts, each, key
+        for key, what ``estimate_faces(frame_list[b], faces[b])`` returns; a frame without faces gets the dict of ``estimate`` with n = 0.
+        A list whose length is not B raises ValueError."""
+        import torch as t
+        frame_list = _normalize.check_grey_list(t, frame_list, "estimate_faces_frame_list")
+        b = 0 if frame_list is None else len(frame_list)
+        if isinstance(faces, np.ndarray) or not hasattr(faces, "__len__") or len(faces) != b:
+            raise ValueError("faces must be the list of %d (m, 10) arrays detect_faces_frame_list returns, one per frame" % b)
+        rows = [np.asarray(f, dtype=np.float64).reshape(-1, 10) for f in faces]
+        first = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        eyes = np.concatenate([r[:, 5:9] for r in rows]) if rows else np.zeros((0, 4))
+        face_frame = np.repeat(np.arange(b, dtype=np.int32), [len(r) for r in rows]) if rows else np.zeros(0, dtype=np.int32)
+        res = self.estimate_frame_list([] if frame_list is None else frame_list, eyes, face_frame, **kw)
+        return [{k: v[int(first[f]):int(first[f + 1])] for k, v in res.items()} for f in range(b)]
+
     def estimate_faces(self, frame, faces, **kw):
         """The (n, 10) rows of ``detect_faces`` / ``FaceTracker`` (x0, y0, x1, y1, angle, eyeL_x, eyeL_y, eyeR_x, eyeR_y, confidence) on
         the frame the cascade read: ``estimate(frame, faces[:, 5:9])``."""

@@ -124,6 +124,7 @@ class DeviceCascade(object):
         self._prescale = {}      # (frame size, prescaled size) -> (box tensor, output tensor) of the prescale step
         self._frames = {}        # (frame size, smallest_face, prescale size) -> everything detect_frame needs per call
         self._list_bufs = {}     # kind of list call -> (rows, output buffers): one set, grown on demand (_list_plan)
+        self._list_pre = None    # the byte buffer of prescale_frame_list's outputs, grown on demand
         for st in self.stages:
             if st.classifier.input_dim > self.k:
                 raise ValueError("stage %s: classifier reads %d features, cascade keeps %d" % (st.name, st.classifier.input_dim, self.k))
@@ -518,6 +519,54 @@ class DeviceCascade(object):
             bufs = (out, first, counts, C.c_int64())
             self._list_bufs[what] = (rows, bufs)
         return arr, total, bufs
+
+    def prescale_frame_list(self, frame_list, prescale_size=grid.PRESCALE_SIZE):
+        """``prescale`` for a list of frames of DIFFERENT sizes (``_check_list``): the list of grey uint8 frames the rows of
+        ``detect_frame_list`` / ``detect_faces_frame_list`` refer to — what ``normalize.FaceNormalizer.normalize_frame_list`` and
+        ``analysis.FaceAnalyzer.estimate_faces_frame_list`` take beside those rows.  Composed here from the per-frame calls: frame f is
+        written by the code ``prescale(frame_list[f])`` runs (the configured filter, grey and colour formats), so its bytes are that
+        call's; B launches, no host wait.  NOT ``prescale``'s tensors, which are one per (frame size, prescaled size) — two frames of one
+        size would come back as the same tensor: the outputs are (ph, pw) views at 256-byte-aligned offsets of ONE cascade-owned byte
+        buffer, grown on demand, valid until the next ``prescale_frame_list`` on this cascade (a caller that keeps them longer clones
+        them).  A grey frame that needs no shrinking is returned as it is.  An empty list returns ``[]`` without touching the library."""
+        t = self.torch
+        frame_list = self._check_list(frame_list)
+        if frame_list is None:
+            return []
+        grey = self.frame_format == _capi.HG_FRAME_L
+        plan, total = [], 0
+        for f in frame_list:
+            fh, fw = int(f.shape[0]), int(f.shape[1])
+            pw, ph = grid.prescaled_size(fw, fh, prescale_size)
+            if (pw, ph) == (fw, fh) and grey:
+                plan.append(None)
+                continue
+            plan.append((fw, fh, pw, ph, total))
+            total += (pw * ph + 255) & ~255
+        stream = t.cuda.current_stream(self.dev)
+        buf = self._list_pre
+        if total and (buf is None or buf.numel() < total):
+            # a launch enqueued on this stream may still write the old buffer: it goes back to the allocator only behind that work (the
+            # views handed out earlier keep it alive as long as the caller holds them)
+            if buf is not None:
+                buf.record_stream(stream)
+            buf = self._list_pre = t.empty(max(total, 2 * (0 if buf is None else buf.numel())), dtype=t.uint8, device=self.dev)
+        out = []
+        for f, p in zip(frame_list, plan):
+            if p is None:
+                out.append(f)
+                continue
+            fw, fh, pw, ph, at = p
+            small = buf[at:at + pw * ph].view(ph, pw)
+            if (pw, ph) == (fw, fh):
+                frames.to_gray(f, self.frame_format, out=small)
+            else:
+                key = ("whole", fw, fh)
+                if key not in self._prescale:      # the box of the whole frame lives with the cascade, one per frame size
+                    self._prescale[key] = t.tensor([[0.0, 0.0, float(fw), float(fh)]], dtype=t.float64, device=self.dev)
+                self._shrink_into(f, fw, fh, pw, ph, self._prescale[key], small, stream.cuda_stream)
+            out.append(small)
+        return out
 
     def detect_frame_list(self, frame_list, smallest_face=0.2, prescale_size=grid.PRESCALE_SIZE):
         """``detect_frame`` for a list of frames of DIFFERENT sizes as ONE pooled pass (hg_cascade_detect_frame_list_device): every frame is

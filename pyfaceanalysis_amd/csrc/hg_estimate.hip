@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 #include "hg_common.hpp"
 #include "hg_gauss_dev.hpp"
@@ -366,18 +367,21 @@ int hg_estimator_patches_device(hg_estimator* e, int flags, const uint8_t* crops
 
 namespace {
 
-// The chain of both estimate entries behind their argument checks, n > 0.  frames_dev / n_frames / frame_stride / face_frame_host: the
-// stack's (face_frame_host == nullptr: the single frame at frames_dev).  A face whose frame index lies outside the stack counts as refused.
+// The chain of all three estimate entries behind their argument checks, n > 0.  frames_dev / n_frames / frame_stride / face_frame_host: the
+// stack's (face_frame_host == nullptr: the single frame at frames_dev); list != nullptr: the n_frames descriptors of a LIST of frames of
+// different sizes in place of frames_dev and the one frame shape.  A face whose frame index lies outside the stack / list counts as refused.
 void run_estimate(hg_estimator* e, bool fused, const uint8_t* frames_dev, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld,
                   const hg_norm_geom* geoms_host, const int32_t* face_frame_host, int64_t n, double* out_dev, int64_t out_stride, float* patches_dev,
-                  float* features_dev, void* stream) {
+                  float* features_dev, void* stream, const hg_frame_ref* list = nullptr) {
         set_dev(e->device);
         hipStream_t st = (hipStream_t)stream;
         const hg_estimator_consts& c = e->c;
         e->reserve(n, st);
         // 1. the crops (a refused face: all zero)
         const int64_t crop_bytes = (int64_t)c.crop_w * c.crop_h;
-        const int rc = face_frame_host
+        const int rc = list
+            ? hg_patcher_normalize_frame_list_device(e->patcher, 0, list, n_frames, geoms_host, face_frame_host, n, c.crop_w, c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st)
+            : face_frame_host
             ? hg_patcher_normalize_frames_device(e->patcher, 0, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n, c.crop_w,
                                                  c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st)
             : hg_patcher_normalize_device(e->patcher, 0, frames_dev, frame_h, frame_w, ld, geoms_host, n, c.crop_w, c.crop_h, (uint8_t*)e->crops.p, crop_bytes, st);
@@ -461,6 +465,24 @@ int hg_estimator_estimate_frames_device(hg_estimator* e, int flags, const uint8_
         if (n == 0) return;
         run_estimate(e, fused, frames_dev, n_frames, frame_stride, frame_h, frame_w, ld, geoms_host, face_frame_host, n, out_dev, out_stride, patches_dev, features_dev,
                      stream);
+    });
+}
+
+int hg_estimator_estimate_frame_list_device(hg_estimator* e, int flags, const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms_host,
+                                            const int32_t* face_frame_host, int64_t n, double* out_dev, int64_t out_stride, float* patches_dev,
+                                            float* features_dev, void* stream) {
+    return guarded([&] {
+        // as for the stack: what a host can tell comes first and reads nothing behind the handle
+        if (!e) hg::fail(HG_ERR_ARG, "null estimator handle");
+        if ((flags & ~3) || flags == 3) hg::fail(HG_ERR_ARG, "estimator: bad flags %d (1: composed patch path, 2: fused patch kernel)", flags);
+        if (n > kMaxFaces) hg::fail(HG_ERR_ARG, "bad face count");
+        const std::string why = hg::normalize_list_check(frames, n_frames, geoms_host, face_frame_host, n);
+        if (!why.empty()) hg::fail(HG_ERR_ARG, "%s", why.c_str());
+        if (out_stride < n) hg::fail(HG_ERR_ARG, "output rows %lld apart hold %lld faces", (long long)out_stride, (long long)n);
+        if (n > 0 && !out_dev) hg::fail(HG_ERR_ARG, "null data pointer");
+        const bool fused = use_fused(e, flags, n);
+        if (n == 0) return;
+        run_estimate(e, fused, nullptr, n_frames, 0, 0, 0, 0, geoms_host, face_frame_host, n, out_dev, out_stride, patches_dev, features_dev, stream, frames);
     });
 }
 

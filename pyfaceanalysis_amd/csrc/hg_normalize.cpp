@@ -5,6 +5,8 @@
 // machine this runs on.  The device path (hg_normalize.hip) takes the geometry from here and repeats the pixel arithmetic.
 #include "hg_normalize.hpp"
 
+#include "hg_frame_list.hpp"
+
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -277,6 +279,52 @@ const char* normalize_frames_check(const void* frames, int n_frames, int64_t fra
     if (ldo < (int64_t)out_w * out_h) return "normalize: ldo < out_w * out_h";
     if (n > 0 && (!frames || !geoms || !face_frame || !out)) return "normalize: null data pointer";
     return geoms_check(geoms, n, frame_w, frame_h);
+}
+
+namespace {
+
+// the list itself: n, the number of frames, every descriptor
+std::string list_shape_check(const hg_frame_ref* frames, int n_frames, int64_t n) {
+    if (n < 0) return "normalize: n < 0";
+    if (n_frames < 1 || n_frames > HG_MAX_STACK_FRAMES) return "normalize: n_frames must be 1 .. HG_MAX_STACK_FRAMES";
+    if (!frames) return "normalize: null frame list";
+    for (int f = 0; f < n_frames; ++f) {
+        const hg_frame_ref& F = frames[f];
+        std::string bad = list_frame_refusal(f, F.frame_dev, F.frame_h, F.frame_w, F.ld, 1);
+        if (!bad.empty()) return bad;
+        if (F.frame_w > (1 << 24) || F.frame_h > (1 << 24)) return "frame " + std::to_string(f) + " of the list: larger than 2^24 pixels per side";
+    }
+    return "";
+}
+
+// every face's geom against its own frame's size
+std::string list_geoms_check(const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms, const int32_t* face_frame, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t f = face_frame[i];
+        if (f < 0 || f >= n_frames) continue;
+        if (const char* why = geom_check(geoms[i], frames[f].frame_w, frames[f].frame_h))
+            return std::string(why) + " (face " + std::to_string((long long)i) + ", on frame " + std::to_string(f) + " of the list)";
+    }
+    return "";
+}
+
+}  // namespace
+
+std::string normalize_list_check(const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms, const int32_t* face_frame, int64_t n) {
+    std::string why = list_shape_check(frames, n_frames, n);
+    if (!why.empty()) return why;
+    if (n > 0 && (!geoms || !face_frame)) return "normalize: null data pointer";
+    return list_geoms_check(frames, n_frames, geoms, face_frame, n);
+}
+
+std::string normalize_frame_list_check(const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms, const int32_t* face_frame, int64_t n, int out_w,
+                                       int out_h, const void* out, int64_t ldo) {
+    std::string why = list_shape_check(frames, n_frames, n);
+    if (!why.empty()) return why;
+    if (out_w < 1 || out_h < 1 || out_w > 4096 || out_h > 4096) return "normalize: out_w / out_h must be 1 .. 4096";
+    if (ldo < (int64_t)out_w * out_h) return "normalize: ldo < out_w * out_h";
+    if (n > 0 && (!geoms || !face_frame || !out)) return "normalize: null data pointer";
+    return list_geoms_check(frames, n_frames, geoms, face_frame, n);
 }
 
 const char* normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,

@@ -22,9 +22,13 @@
 // Every grid and scratch size comes from the host's geoms; no launch is sized by anything read on the device.
 // The faces of a STACK of same-size frames (hg_patcher_normalize_frames_device) run the same bodies: k_norm_rect_frames and
 // k_norm_cut<…, StackRef, StackFace>, each face reading its own frame; the single frame keeps k_norm_rect and k_norm_cut<…, FrameRef, NormFace>.
+// The faces of a LIST of frames of different sizes (hg_patcher_normalize_frame_list_device) run them a third time: k_norm_rect_list and
+// k_norm_cut<…, ListRef, ListFace>, each record carrying the frame the host resolved for it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
+#include <type_traits>
 
 #include "hg_common.hpp"
 #include "hg_normalize.hpp"
@@ -69,8 +73,26 @@ struct StackRef {
     int w, h, n_frames;
 };
 
+// A LIST of frames of different sizes (hg_patcher_normalize_frame_list_device): the face record carries its RESOLVED frame — base
+// pointer, row stride, size — which the host fills from frames[face_frame[i]]; p == nullptr for a refused face and for one whose index
+// lies outside the list.  No table of frames on the device and no index to check there: the one upload of the records is all a call
+// sends.  The third instantiation, (ListRef, ListFace); the reference itself carries nothing the kernels read.
+struct ListFace {
+    NormFace f;
+    const uint8_t* p;
+    int64_t ld;
+    int32_t w, h;
+};
+
+struct ListRef {
+    static constexpr bool kStack = true;      // as for the stack: a face without a frame (p == nullptr) is the all-zero image
+    int32_t n_frames;                         // (not read on the device)
+};
+
 __device__ __forceinline__ const NormFace& rec(const NormFace& f) { return f; }
 __device__ __forceinline__ const NormFace& rec(const StackFace& s) { return s.f; }
+__device__ __forceinline__ const NormFace& rec(const ListFace& s) { return s.f; }
+__device__ __forceinline__ FrameRef frame_of(const ListRef&, const ListFace& s) { return FrameRef{s.p, s.ld, s.w, s.h}; }
 __device__ __forceinline__ FrameRef frame_of(const FrameRef& fr, const NormFace&) { return fr; }
 // the face's own frame; p == nullptr for an index outside [0, n_frames): no address is formed from such an index (the host has made
 // such a face kModeZero already; the kernels do not rely on it)
@@ -125,6 +147,9 @@ __global__ void __launch_bounds__(256) k_norm_rect(FrameRef fr, const NormFace* 
 }
 __global__ void __launch_bounds__(256) k_norm_rect_frames(StackRef sr, const StackFace* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
     norm_rect(sr, faces, n, scratch);
+}
+__global__ void __launch_bounds__(256) k_norm_rect_list(ListRef lr, const ListFace* __restrict__ faces, int64_t n, uint8_t* __restrict__ scratch) {
+    norm_rect(lr, faces, n, scratch);
 }
 
 // Pass B: the EXTENT / BICUBIC cut, a 16 x 16 tile of output pixels per workgroup.  MODE kModeStaged also writes the all-zero image of
@@ -217,16 +242,27 @@ void normalize_state_free(void* state) { delete (NormState*)state; }
 
 namespace {
 
-inline void set_frame(NormFace&, int32_t) {}
-inline void set_frame(StackFace& s, int32_t frame) { s.frame = frame; }
+// frame: the face's index, checked, or -1 for a face without a frame; list: the list's descriptors (nullptr elsewhere)
+inline void set_frame(NormFace&, int32_t, const hg_frame_ref*) {}
+inline void set_frame(StackFace& s, int32_t frame, const hg_frame_ref*) { s.frame = frame; }
+inline void set_frame(ListFace& s, int32_t frame, const hg_frame_ref* list) {
+    if (frame < 0) return;      // (the zeroed record: a null frame)
+    const hg_frame_ref& F = list[frame];
+    s.p = (const uint8_t*)F.frame_dev;
+    s.ld = F.ld;
+    s.w = F.frame_w;
+    s.h = F.frame_h;
+}
 inline NormFace& rec_host(NormFace& f) { return f; }
 inline NormFace& rec_host(StackFace& s) { return s.f; }
+inline NormFace& rec_host(ListFace& s) { return s.f; }
 
-// Both entries behind their argument checks, n > 0.  face_frame / n_frames: the stack's (nullptr / 0 for the single frame); a face whose
-// frame index lies outside [0, n_frames) is a refused face here already — kModeZero, no scratch, no part in any grid size.
+// All three entries behind their argument checks, n > 0.  face_frame / n_frames: the stack's or the list's (nullptr / 0 for the single
+// frame); list: the list's descriptors (host; nullptr elsewhere).  A face whose frame index lies outside [0, n_frames) is a refused face
+// here already — kModeZero, no scratch, no part in any grid size.
 template <typename Ref, typename Face>
 void normalize_run(hg_patcher* p, int flags, const Ref& ref, const hg_norm_geom* geoms_host, const int32_t* face_frame, int n_frames, int64_t n, int out_w, int out_h,
-                   uint8_t* out_dev, int64_t ldo, void* stream) {
+                   uint8_t* out_dev, int64_t ldo, void* stream, const hg_frame_ref* list = nullptr) {
     if (n > (1 << 24)) hg::fail(HG_ERR_ARG, "normalize: more than 2^24 faces in one call");
     auto live = [&](int64_t i) {
         const hg_norm_geom& g = geoms_host[i];
@@ -286,10 +322,10 @@ void normalize_run(hg_patcher* p, int flags, const Ref& ref, const hg_norm_geom*
                 f.scratch_off = off;
                 off += (np + 15) & ~(int64_t)15;
             }
-            if (face_frame) set_frame(F, face_frame[i]);
+            if (face_frame) set_frame(F, face_frame[i], list);
         } else if (face_frame) {
-            set_frame(F, -1);
-        }      // kModeZero — a refused face, one none of whose output pixels is inside rot, or one whose frame is outside the stack
+            set_frame(F, -1, list);
+        }      // kModeZero — a refused face, one none of whose output pixels is inside rot, or one whose frame is outside the stack / list
         host[i] = F;
     }
     if (S->faces.p && bytes > S->faces.bytes) HG_HIP(hipStreamSynchronize(st));      // a launch in flight may still read the old buffer
@@ -303,7 +339,8 @@ void normalize_run(hg_patcher* p, int flags, const Ref& ref, const hg_norm_geom*
     const unsigned ny = (unsigned)std::min<int64_t>(n, 65535);
     if (max_rect > 0) {
         const dim3 grid((unsigned)((max_rect + 255) / 256), ny);      // <= 2^20 chunks (16 * 4096 * 4096 pixels; forced: kForcedStageLimit)
-        if constexpr (Ref::kStack) hipLaunchKernelGGL(k_norm_rect_frames, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
+        if constexpr (std::is_same_v<Ref, ListRef>) hipLaunchKernelGGL(k_norm_rect_list, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
+        else if constexpr (Ref::kStack) hipLaunchKernelGGL(k_norm_rect_frames, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
         else hipLaunchKernelGGL(k_norm_rect, grid, 256, 0, st, ref, faces, n, (uint8_t*)S->scratch.p);
     }
     const int tiles_x = (out_w + kTile - 1) / kTile, tiles_y = (out_h + kTile - 1) / kTile;      // <= 256 each
@@ -341,6 +378,18 @@ int hg_patcher_normalize_frames_device(hg_patcher* p, int flags, const uint8_t* 
         if (n == 0) return;
         normalize_run<StackRef, StackFace>(p, flags, StackRef{frames_dev, ld, frame_stride, frame_w, frame_h, n_frames}, geoms_host, face_frame_host, n_frames, n, out_w,
                                            out_h, out_dev, ldo, stream);
+    });
+}
+
+int hg_patcher_normalize_frame_list_device(hg_patcher* p, int flags, const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms_host,
+                                           const int32_t* face_frame_host, int64_t n, int out_w, int out_h, uint8_t* out_dev, int64_t ldo, void* stream) {
+    return guarded([&] {
+        if (!p) hg::fail(HG_ERR_ARG, "null patcher handle");
+        if ((flags & ~3) || flags == 3) hg::fail(HG_ERR_ARG, "normalize: bad flags %d (1: staged, 2: tap by tap)", flags);
+        const std::string why = hg::normalize_frame_list_check(frames, n_frames, geoms_host, face_frame_host, n, out_w, out_h, out_dev, ldo);
+        if (!why.empty()) hg::fail(HG_ERR_ARG, "%s", why.c_str());
+        if (n == 0) return;
+        normalize_run<ListRef, ListFace>(p, flags, ListRef{n_frames}, geoms_host, face_frame_host, n_frames, n, out_w, out_h, out_dev, ldo, stream, frames);
     });
 }
 

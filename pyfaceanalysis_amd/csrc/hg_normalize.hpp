@@ -3,6 +3,7 @@
 // (hg_normalize.hip) reads the same geoms and shares the checks.
 #pragma once
 #include <cstdint>
+#include <string>
 
 #include "../../include/higsfa.h"
 
@@ -26,6 +27,17 @@ const char* normalize_stack_check(const void* frames, int n_frames, int64_t fram
                                   const int32_t* face_frame, int64_t n);
 const char* normalize_frames_check(const void* frames, int n_frames, int64_t frame_stride, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms,
                                    const int32_t* face_frame, int64_t n, int out_w, int out_h, const void* out, int64_t ldo);
+
+// The same for the faces of a LIST of frames of different sizes (hg_patcher_normalize_frame_list_device,
+// hg_estimator_estimate_frame_list_device): "" or why the call is refused, naming the frame where one frame is the reason.  n < 0, n_frames
+// outside 1 .. HG_MAX_STACK_FRAMES, a null frames, any frame hg::list_frame_refusal (hg_frame_list.hpp, bpp = 1) refuses or that is larger
+// than 2^24 per side, a bad output size or ldo, a null geoms / face_frame / out with n > 0, and a geom that was not built for the size of its
+// face's OWN frame.  The geom of a face whose index lies outside the list belongs to no frame and is not looked at: such a face is no
+// error.  Reads the descriptors and the geoms (host memory) and nothing behind a frame pointer or out.  normalize_list_check is the part
+// about the list and the faces alone (the estimator has no caller's images).
+std::string normalize_list_check(const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms, const int32_t* face_frame, int64_t n);
+std::string normalize_frame_list_check(const hg_frame_ref* frames, int n_frames, const hg_norm_geom* geoms, const int32_t* face_frame, int64_t n, int out_w,
+                                       int out_h, const void* out, int64_t ldo);
 
 // hg_normalize_faces_host
 const char* normalize_faces_host(const uint8_t* frame, int frame_h, int frame_w, int64_t ld, const hg_norm_geom* geoms, int64_t n, int out_w, int out_h,

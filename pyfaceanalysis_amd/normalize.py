@@ -36,7 +36,7 @@ STATUS = {0: "ok", 1: "left eye right of the right eye", 2: "a coordinate is not
 # the stack calls' own status (``normalize_frames``, ``FaceAnalyzer.estimate_frames``): the face's frame index lies outside the stack.  It
 # is Python's: the geometry knows no frames, hg_norm_geom.status stays 0 for such a face and the library treats it like a refused one.
 STATUS_FRAME_RANGE = 5
-STATUS[STATUS_FRAME_RANGE] = "the frame index is outside the stack"
+STATUS[STATUS_FRAME_RANGE] = "the frame index is outside the stack"      # (or outside the list: ``normalize_frame_list``, ``estimate_frame_list``)
 
 
 def check_configuration(normalization_method="eyes_inferred-mouth_area", centering_mode="mid_eyes_inferred-mouth", rotation_mode="EyeLineRotation",
@@ -205,6 +205,57 @@ def check_face_frame(face_frame, n):
     return np.ascontiguousarray(np.where((f < -(1 << 31)) | (f >= (1 << 31)), -1, f).astype(np.int32))
 
 
+def check_grey_list(t, frame_list, what):
+    """A list (or tuple) of grey frames of ANY sizes for ``what`` ("normalize_frame_list", "estimate_frame_list"), or ValueError naming the
+    frame; None for an empty list.  The rules of ``DeviceCascade._check_list`` for grey frames: every frame an (H, W) uint8 tensor, not
+    empty, rows contiguous and ``stride(0) >= W`` (a broadcast view is refused), at most ``HG_MAX_STACK_FRAMES`` frames; the tensors may be
+    separate allocations or views of one buffer, and one tensor may be listed twice.  Shapes, dtypes and strides only: the device is
+    ``check_list_device``'s, the last refusal before the library."""
+    if not isinstance(frame_list, (list, tuple)):
+        raise ValueError("%s takes a list or tuple of (H, W) grey uint8 device tensors (a stack of same-size frames goes through the _frames call)" % what)
+    if len(frame_list) == 0:
+        return None
+    if len(frame_list) > _capi.HG_MAX_STACK_FRAMES:
+        raise ValueError("%d frames in a list, at most %d" % (len(frame_list), _capi.HG_MAX_STACK_FRAMES))
+    for i, f in enumerate(frame_list):
+        if not isinstance(f, t.Tensor):
+            raise ValueError("frame %d of the list is not a tensor" % i)
+        if f.dtype != t.uint8 or f.dim() != 2:
+            raise ValueError("frame %d of the list must be (H, W) grey uint8 (a float frame is not offered; a colour frame goes through "
+                             "DeviceCascade.prescale_frame_list first)" % i)
+        h, w = int(f.shape[0]), int(f.shape[1])
+        if h == 0 or w == 0:
+            raise ValueError("frame %d of the list is empty" % i)
+        if w > 1 and f.stride(1) != 1:
+            raise ValueError("frame %d of the list must have contiguous rows, got strides %s" % (i, tuple(f.stride())))
+        if h > 1 and f.stride(0) < w:
+            raise ValueError("frame %d of the list: rows %d bytes apart hold %d bytes: a broadcast or overlapping view is not a frame" % (i, f.stride(0), w))
+    return list(frame_list)
+
+
+def check_list_device(frame_list, device, what):
+    """The last refusal before the library: every frame of the list (None: an empty one) lives on device ``device``."""
+    for i, f in enumerate(frame_list or ()):
+        if not f.is_cuda:
+            raise ValueError("%s takes device tensors (frame %d of the list is on the host)" % (what, i))
+        if (f.device.index or 0) != device:
+            raise ValueError("frame %d of the list is on %s, not on device %d" % (i, f.device, device))
+
+
+def list_sizes(frame_list):
+    """[(width, height)] of a checked list (None: [])."""
+    return [(int(f.shape[1]), int(f.shape[0])) for f in (frame_list or ())]
+
+
+def list_refs(frame_list):
+    """The ``hg_frame_ref`` array of a checked list of grey frames (ld in bytes; one row: the width)."""
+    arr = (_capi.HgFrameRef * len(frame_list))()
+    for a, f in zip(arr, frame_list):
+        h, w = int(f.shape[0]), int(f.shape[1])
+        a.frame_dev, a.frame_h, a.frame_w, a.ld = f.data_ptr(), h, w, (f.stride(0) if h > 1 else w)
+    return arr
+
+
 class FaceNormalizer(object):
     """``normalize_image`` for the faces of one frame, on the device.  ``preset``: "age" — (256, 260), areaZ, the crops
     ``estimate_age_race_gender`` makes (face_analysis.py:1172-1179) — or "pose" — (256, 192), area, those of
@@ -296,6 +347,57 @@ class FaceNormalizer(object):
             _capi.check(_capi.lib().hg_patcher_normalize_frames_device(
                 self._patcher._handle(), int(flags), stack.data_ptr(), b, stride, h, w, ld, g.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), n,
                 ow, oh, out.data_ptr(), out.stride(0) if n > 1 else ow * oh, t.cuda.current_stream(stack.device).cuda_stream))
+        return out, status
+
+    def list_geometry(self, sizes, eyes, face_frame):
+        """The records of faces spread over frames of DIFFERENT sizes: ``sizes`` a list of (width, height), ``face_frame`` (n,) the frame
+        of every face, in any order.  Record i is ``geometry(eyes[i], sizes[face_frame[i]])``, computed per frame on the host and
+        scattered back into the faces' order; a face whose index lies outside the list gets a zeroed record.  Returns (geoms, face_frame
+        as the checked int32 array)."""
+        e = _eyes(eyes)
+        ff = check_face_frame(face_frame, len(e))
+        g = np.zeros(len(e), dtype=_capi.NORM_GEOM_DTYPE)
+        for f in np.unique(ff[(ff >= 0) & (ff < len(sizes))]):
+            idx = np.flatnonzero(ff == f)
+            g[idx] = self.geometry(e[idx], sizes[int(f)])
+        return g, ff
+
+    def normalize_frame_list(self, frame_list, eyes=None, face_frame=None, geoms=None, out=None, flags=0):
+        """``normalize`` for faces spread over a list of B frames of DIFFERENT sizes, ONE call (hg_patcher_normalize_frame_list_device):
+        ``frame_list`` a list of (H, W) grey uint8 device tensors with contiguous rows, any row pitch, separate allocations or views of
+        one buffer (``check_grey_list``; the prescaled frames the rows of ``detect_faces_frame_list`` refer to are
+        ``DeviceCascade.prescale_frame_list(frame_list)``); ``eyes`` (n, 4) in the coordinates of each face's own frame, ``face_frame``
+        (n,) integers: the frame of every face, in any order.  ``geoms`` instead of ``eyes``: taken as given — record i must be
+        ``geometry`` for the size of face i's OWN frame (``list_geometry``).  Returns (images, status) as ``normalize_frames`` does, ``out``
+        as there; face i's image is, byte for byte, ``normalize(frame_list[face_frame[i]], eyes[i:i + 1])``'s.  A face whose frame index
+        is outside [0, B) gets an all-zero image and status ``STATUS_FRAME_RANGE``; it is no error.  Enqueued on the current stream, no
+        host wait.  An empty list or n = 0 touches no library entry."""
+        import torch as t
+        frame_list = check_grey_list(t, frame_list, "normalize_frame_list")      # layout first, then the faces, then the device
+        b = 0 if frame_list is None else len(frame_list)
+        ow, oh = self.out_size
+        if geoms is not None:
+            g = _check_geoms(geoms)
+            ff = check_face_frame(face_frame, int(g.shape[0]))
+        else:
+            g, ff = self.list_geometry(list_sizes(frame_list), eyes, face_frame)
+        n = int(g.shape[0])
+        check_list_device(frame_list, self.device, "normalize_frame_list")
+        status = np.where((ff < 0) | (ff >= b), STATUS_FRAME_RANGE, g["status"]).astype(np.int32)
+        # (an empty list has no tensor to say where its all-zero images live: where ``out`` does, else on the normalizer's device)
+        dev = frame_list[0].device if b else out.device if isinstance(out, t.Tensor) else t.device("cuda", self.device)
+        if out is None:
+            out = t.empty((n, oh, ow), dtype=t.uint8, device=dev) if b else t.zeros((n, oh, ow), dtype=t.uint8, device=dev)
+        elif (not isinstance(out, t.Tensor) or out.dtype != t.uint8 or out.device != dev or tuple(out.shape) != (n, oh, ow)
+              or (ow > 1 and out.stride(2) != 1) or (oh > 1 and out.stride(1) != ow) or (n > 1 and out.stride(0) < ow * oh)):
+            raise ValueError("out must be a (%d, %d, %d) uint8 tensor on %s whose images are contiguous" % (n, oh, ow, dev))
+        elif not b:
+            out.zero_()
+        if n and b:
+            refs = list_refs(frame_list)
+            _capi.check(_capi.lib().hg_patcher_normalize_frame_list_device(
+                self._patcher._handle(), int(flags), refs, b, g.ctypes.data_as(C.c_void_p), ff.ctypes.data_as(C.c_void_p), n, ow, oh, out.data_ptr(),
+                out.stride(0) if n > 1 else ow * oh, t.cuda.current_stream(dev).cuda_stream))
         return out, status
 
     def close(self):
