@@ -629,6 +629,7 @@ constexpr int kWeightLdsKiB = 64;       // target size of a node group's weights
 struct StageDev {
     DevBuf afrag, bias, kb1tab, chunks, runs, piece, koff, kmean, kcol, gcol, etab, pack_slot;
     DevBuf fold_frag, fold_bias;      // stage 1 of a plan with the link 0 -> 1 folded
+    DevBuf fold_last;                 // ... and its one-row k-steps packed (stage 0 of such a plan: fold_a1 / fold_b1 go up as afrag / bias)
     DevBuf pair_kids, kb1tab_pre, bias_pre;      // a hoisted stage whose nodes have two children each (HostStage::pair_kids)
 };
 struct SubRunDev {
@@ -661,6 +662,8 @@ public:
     std::string stage_name(int i) const override {
         if (i == 1 && plan_->fuse01 && !plan_->opt.fold01)
             return plan_->stages[i].name + "  [link 0 -> 1 stays as it is: switched off (HIGSFA_NO_FOLD01)]";
+        if (i == 1 && plan_->fold01 && !plan_->opt.fold01_pack)
+            return plan_->stages[i].name + "  [the link's one-row k-steps stay as they are: switched off (HIGSFA_NO_FOLD01_PACK)]";
         if (i < (int)plan_->stages.size() && plan_->stages[i].sum_in && !plan_->opt.pair)
             return plan_->stages[i].name + "; unpaired: switched off (HIGSFA_NO_PAIR)";
         if (i < (int)plan_->stages.size()) return plan_->stages[i].name;
@@ -697,15 +700,20 @@ public:
                 std::vector<float> part((size_t)s.n_nodes * count * 256);
                 for (int ni = 0; ni < s.n_nodes; ++ni)
                     std::copy_n(s.afrag.data() + ((size_t)ni * s.node_blocks + first) * 256, count * 256, part.data() + (size_t)ni * count * 256);
-                d.afrag.upload(part.data(), part.size() * 4);
+                // (packed one-row k-steps: stage 0's first affine is the variant with feature 12 repeated, HostStage::fold_a1 / fold_b1)
+                const bool variant = plan_->fold01_pack && si == 0;
+                if (variant) d.afrag.upload(s.fold_a1.data(), s.fold_a1.size() * 4);
+                else d.afrag.upload(part.data(), part.size() * 4);
                 if (si == 1) {
                     d.fold_frag.upload(s.fold_frag.data(), s.fold_frag.size() * 4);
                     d.fold_bias.upload(s.fold_bias.data(), s.fold_bias.size() * 4);
+                    if (plan_->fold01_pack) d.fold_last.upload(s.fold_last.data(), s.fold_last.size() * 4);
                 }
             } else {
                 d.afrag.upload(s.afrag.data(), s.afrag.size() * 4);
             }
-            d.bias.upload(s.bias.data(), s.bias.size() * 4);
+            if (plan_->fold01_pack && si == 0) d.bias.upload(s.fold_b1.data(), s.fold_b1.size() * 4);
+            else d.bias.upload(s.bias.data(), s.bias.size() * 4);
             if (!s.kb1tab.empty()) d.kb1tab.upload(s.kb1tab.data(), s.kb1tab.size() * 4);
             if (!s.gcol.empty()) d.gcol.upload(s.gcol.data(), s.gcol.size() * 4);
             if (!s.etab.empty()) d.etab.upload(s.etab.data(), s.etab.size() * 4);
@@ -957,6 +965,8 @@ private:
             R.node_blocks = first ? hs.kb1 * hs.mt1 : hs.node_blocks - hs.kb1 * hs.mt1;
             R.fold_frag = (const f32x4*)d.fold_frag.p;
             R.fold_bias = (const float*)d.fold_bias.p;
+            R.fold_last = (const float*)d.fold_last.p;
+            if (plan_->fold01_pack && first) R.bias_floats = 16;      // HostStage::fold_b1: the first bias alone
         }
         for (int fi = 0; fi < hs.nf; ++fi) {
             R.funcp |= (uint32_t)hs.funcs[fi].kind << (4 * fi);
@@ -1126,14 +1136,18 @@ private:
         // (k_stage01p's scalar staging branch).
         const bool fold = plan_->fold01;
         if (fold && !(rem4 && plan_->fuse01)) fail(HG_ERR_STATE, "internal: the link 0 -> 1 is folded but the front kernel's remainder-tile form does not apply");
+        const bool pack = plan_->fold01_pack;      // the folded link's one-row k-steps packed: the PACK instantiations and no others
+        if (pack && !fold) fail(HG_ERR_STATE, "internal: packed k-steps on a plan whose link 0 -> 1 is not folded");
         if (plan_->fuse01 && ((P.vec4 && n_tiles >= FT) || fold)) {
             // layers 0 and 1 in one persistent kernel; layer 1 writes where its own launch would
             StageParams Q = stage_params(plan_->stages[1], dev_[1], nullptr, out1, n_tiles);
+            if (pack && (!Q.fold_last || P.bias_floats != 16)) fail(HG_ERR_STATE, "internal: a packed plan without its packed fragments on the device");
             // every wave on its own (k_stage01d) where the input layout allows it, else the LDS-staged kernel
             const size_t esz = dtype_size(x_dtype);
             const bool direct = P.vec4 && fspec && rem4 && s.direct_ok && plan_->stages[1].pack_out && (int64_t)16 * ldx * (int64_t)esz + 2048 < 0x7fffffffll && s.max_chunk_nodes <= 8 && !plan_->opt.no_direct;   // (k_stage01d: 32-bit byte offsets inside a tile's rows; at most four waves)
             const bool wgq = !plan_->opt.no_wgq;       // k_stage01d: one tile queue per chunk, shared by the waves of a workgroup
-            StageFn2 fn = direct ? pick_stage01d(x_dtype, false, wgq, fold) : pick_stage01p(x_dtype, false, rem4, fspec, fold, fold && !P.vec4);
+            StageFn2 fn = direct ? pick_stage01d(x_dtype, false, wgq, fold, pack) : pick_stage01p(x_dtype, false, rem4, fspec, fold, fold && !P.vec4, pack);
+            if (!fn) fail(HG_ERR_STATE, "internal: no packed front kernel for this plan");      // never an unpacked kernel on packed fragments
             const int thr01 = 64 * std::max(1, (s.max_chunk_nodes + 1) / 2);   // one wave per pair of layer-0 nodes
             // LDS: the tile buffers of FT batch tiles (k_stage01p only) + 10 vectors of 16 floats (means, biases) per wave
             const size_t lds2 = direct ? (size_t)4 * 160 * 4 + 32 * 4 + (size_t)4 * 256 * 4      // constants | ring + progress words | reduction scratch per wave
@@ -1144,7 +1158,7 @@ private:
             if (plan_->opt.debug) fprintf(stderr, "[front] occ %d threads %d lds %zu chunks %d tile_parts %d\n", occ, thr01, lds2, P.n_chunks, P.tile_parts);
 #ifdef HIGSFA_DIAG
             if (plan_->opt.stamp_stage == 0 && x_dtype == HG_F32 && (direct || !fold)) {      // (the folded k_stage01p has no stamped form)
-                fn = direct ? pick_stage01d(HG_F32, true, wgq, fold) : pick_stage01p(HG_F32, true, rem4, fspec, fold);
+                fn = direct ? pick_stage01d(HG_F32, true, wgq, fold, pack) : pick_stage01p(HG_F32, true, rem4, fspec, fold);
                 stamps_begin(P, P.n_chunks * P.tile_parts, 12, st);
             }
 #endif
@@ -1549,6 +1563,7 @@ std::unique_ptr<Executor> make_fused_executor(const TNode& root, std::string* wh
     fused::FusedOptions opt = fused::FusedOptions::from_env();
     opt.hoist = getenv("HIGSFA_NO_HOIST") == nullptr;      // (an executor's switch, not the planner's: DESIGN.md §9)
     opt.fold01 = getenv("HIGSFA_NO_FOLD01") == nullptr;    // likewise
+    opt.fold01_pack = opt.fold01 && getenv("HIGSFA_NO_FOLD01_PACK") == nullptr;      // the folded link's one-row k-steps packed
     opt.pair = opt.hoist && getenv("HIGSFA_NO_PAIR") == nullptr;      // summed links ride on the hoisted ones
     auto plan = fused::build_fused_plan(root, opt, why_not);
     if (!plan) return nullptr;

@@ -83,6 +83,9 @@ struct StageParams {
     // blocks alone (node_blocks = 8, no first-affine blocks in front of them).
     const f32x4* fold_frag;
     const float* fold_bias;
+    // ... with its one-row k-steps packed (FusedPlan::fold01_pack, the PACK instantiations): HostStage::fold_last, [node][tile][lane].  Such a
+    // plan uploads stage 0's fold_a1 / fold_b1 in place of its first-affine blocks and biases (bias_floats = 16).
+    const float* fold_last;
     // Summed link, producer side (k_stage_sum_pair, hg_fused_sum.hip): the nodes of this stage taken two by two, pair j = the children of node j of
     // the stage above in the order that stage adds them; the output holds ONE tile set per pair, (pair_bias[j] + y of .x) + y of .y, at blocks
     // j * mto .. (nb_out = n_pairs x mto).  pair_bias: the stage above's own bias array (pair_bias_floats per node, the first bias in front).
@@ -513,9 +516,9 @@ typedef void (*StageFn2)(StageParams, StageParams);
 // kernels living in the other translation units
 StageFn pick_stage0(int mt1, int mt2, int T, int x_dtype);            // hg_fused_front.hip
 StageFn pick_stage0p(int x_dtype);
-StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold = false, bool scalar = false);      // fold: FusedPlan::fold01 (REM4 forms only); scalar: rows without 16-byte loads (fold only)
+StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold = false, bool scalar = false, bool pack = false);      // fold: FusedPlan::fold01 (REM4 forms only); scalar: rows without 16-byte loads (fold only); pack: FusedPlan::fold01_pack (fold only)
 int stage01p_tiles(bool rem4, bool fspec);
-StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold = false);       // every wave on its own, no LDS tile (hg_fused_front.hip)
+StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold = false, bool pack = false);       // every wave on its own, no LDS tile (hg_fused_front.hip)
 StageFn pick_igsfa(int ms, int mo, int T, int kb1);                   // hg_fused_igsfa.hip
 StageFn pick_igfold(int mo, int T, bool fs = false);
 StageFn pick_prod(int mt1, int mt2, int T);                           // hg_fused_prod.hip

@@ -245,10 +245,15 @@ __global__ void __launch_bounds__(512) k_stage0p(StageParams P) {
 // and in k_stage01d: z1 tile 0 starts from the folded bias, the 4x4-form accumulator d4 of tile 1 from zero; then child 0, then child
 // 1, each with the identity's k-steps 0..3 and then |x|^p's k-steps 0..3, every k-step one 16x16x4 into z1 tile 0 and one 4x4x1
 // into d4; after the 16 k-steps ONE lane-group sum of d4 goes onto tile 1's bias (add_rem4 here, rem4_total_lds there: the same bits).
+// PACK (with FOLD; FusedPlan::fold01_pack): layer 0 has 13 outputs per node, so register 3 of a child's z0 holds feature 12 in lane
+// group 0 and padding elsewhere, and the four k-steps of register 3 carry one real k-row each.  They are ONE k-step here: the children run
+// registers 0..2 (twelve k-steps, the order above), then s = z0[child 0][3] + z0[child 1][3] — the plan's first-affine variant (P.afrag / P.bias
+// of such a plan) puts child 0's feature 12 in lane groups 0 and 2 and child 1's in 1 and 3, zeros in the other two, so each lane group gets its
+// value plus an exact +0.0 — and the B operand is s in lane groups 0-1 and |s|^p in 2-3 against Q.fold_last.  The same in k_stage01d.
 // SCALAR (with FOLD: a folded plan has no unfused first layer to fall back on): for rows that allow no 16-byte loads (odd base or
 // pitch, P.vec4 == 0); the tile is filled through the chunk's run list with scalar loads, as k_stage0 does, unpipelined.  An
 // instantiation of its own: as a run-time branch it costs the pipelined form 44 bytes of scratch.
-template <typename XT, bool STAMP = false, bool REM4 = false, int TT = 2, int FSPEC = 0, bool FOLD = false, bool SCALAR = false>
+template <typename XT, bool STAMP = false, bool REM4 = false, int TT = 2, int FSPEC = 0, bool FOLD = false, bool SCALAR = false, bool PACK = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 2 ? 3 : TT == 1 ? 4 : 2, TT == 2 ? 3 : TT == 1 ? 4 : 2))) k_stage01p(StageParams P, StageParams Q) {
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
     float* lds = (float*)smem;
@@ -309,6 +314,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
     // (FOLD: ff in place of w_a2 and q_a1; a folded plan uploads stage 1's second-affine fragments alone, Q.node_blocks = 8)
     const int n1 = (ck.node_begin >> 1) + (w_ok ? wave : 0);
     f32x4 q_a1[2][2], q_a2[2][2][2], ff[2][2][2];
+    float fl[2] = {0.f, 0.f};      // PACK: the packed k-step's A fragments (of ff only registers 0..2 are used then)
     {
         const f32x4* wq = Q.afrag + (size_t)n1 * Q.node_blocks * 64 + lane;
         if constexpr (FOLD) {
@@ -319,6 +325,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
                 for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) ff[sl][fi][mt] = wf[((sl * 2 + fi) * 2 + mt) * 64];
+            if constexpr (PACK) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) fl[mt] = Q.fold_last[((size_t)n1 * 2 + mt) * 64 + lane];
+            }
         } else {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -487,6 +497,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
             for (int t = 0; t < T; ++t) d4[t] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (FOLD) {
                 // ---- layer 0's first affine, then layer 1's first affine folded with layer 0's second (order: see the head comment)
+                constexpr int NR = PACK ? 3 : 4;      // k-steps per child and function
+                float s12[T];                         // PACK: the two children's feature 12, by lane group (c0, c1, c0, c1)
 #pragma unroll
                 for (int sl = 0; sl < NPW; ++sl) {
                     f32x4 z[T], bf[T];
@@ -501,6 +513,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
                     for (int r = 0; r < 4; ++r)
 #pragma unroll
                         for (int t = 0; t < T; ++t) z[t] = MFMA16(w_a1[sl][r], bf[t][r], z[t]);
+                    if constexpr (PACK) {
+#pragma unroll
+                        for (int t = 0; t < T; ++t) s12[t] = sl == 0 ? z[t][3] : s12[t] + z[t][3];
+                    }
 #pragma unroll
                     for (int fi = 0; fi < 2; ++fi) {
                         f32x4 e[T];
@@ -508,12 +524,21 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
                         for (int t = 0; t < T; ++t)
                             e[t] = FSPEC == 1 ? (fi == 0 ? z[t] : pow_abs4(z[t], ex1)) : apply_func(fi == 0 ? fk0 : fk1, fi == 0 ? ex0 : ex1, z[t]);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
+                        for (int r = 0; r < NR; ++r) {
 #pragma unroll
                             for (int t = 0; t < T; ++t) z1[0][t] = MFMA16(ff[sl][fi][0][r], e[t][r], z1[0][t]);
 #pragma unroll
                             for (int t = 0; t < T; ++t) d4[t] = MFMA4(ff[sl][fi][1][r], e[t][r], d4[t]);
                         }
+                    }
+                }
+                if constexpr (PACK) {      // the packed k-step: a folded plan expands with (identity, |x|^p) whatever FSPEC
+#pragma unroll
+                    for (int t = 0; t < T; ++t) {
+                        const float pw = pow_abs(s12[t], ex1);
+                        const float b = g < 2 ? s12[t] : pw;
+                        z1[0][t] = MFMA16(fl[0], b, z1[0][t]);
+                        d4[t] = MFMA4(fl[1], b, d4[t]);
                     }
                 }
                 if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
@@ -663,8 +688,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TT == 
 // at nearly the same time and the 128-byte input lines and packed output blocks they share are fetched and written once
 // (the per-wave queues decorrelate them: 389 MB read / 235 MB written against 279 / 201).  No barrier in the loop: a
 // follower waits only when it is more than one pass ahead of wave 0, wave 0 only when a follower is eight passes behind.
-// FOLD: the link 0 -> 1 folded, as in k_stage01p (same products, same order).
-template <typename XT, bool STAMP = false, bool WGQ = true, bool FOLD = false>
+// FOLD: the link 0 -> 1 folded, as in k_stage01p (same products, same order).  PACK: its one-row k-steps packed, likewise.
+template <typename XT, bool STAMP = false, bool WGQ = true, bool FOLD = false, bool PACK = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) k_stage01d(StageParams P, StageParams Q) {
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
     unsigned long long rt_entry = 0;
@@ -717,6 +742,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     // a folded plan uploads stage 1's second-affine fragments alone (Q.node_blocks = 8, no first-affine blocks in front)
     f32x4 q_a1[2][2], q_a2[2][2], ff[2][2][2];
     float q_a2t[2][2];
+    float fl[2] = {0.f, 0.f};      // PACK: the packed k-step's A fragments (of ff only registers 0..2 are used then: 26 registers for 32)
     {
         const f32x4* wq = Q.afrag + (size_t)n1 * Q.node_blocks * 64 + lane;
         if constexpr (FOLD) {
@@ -727,6 +753,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) ff[sl][fi][mt] = wf[((sl * 2 + fi) * 2 + mt) * 64];
+            if constexpr (PACK) {
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) fl[mt] = Q.fold_last[((size_t)n1 * 2 + mt) * 64 + lane];
+            }
         } else {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -887,19 +917,27 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                 z1[mt] = *(const f32x4*)(cst + (C_QB1 + mt) * 16 + g * 4);
                 y1[mt] = *(const f32x4*)(cst + (C_QB2 + mt) * 16 + g * 4);
             }
+            constexpr int NR = PACK ? 3 : 4;      // k-steps per child and function
 #pragma unroll
             for (int sl = 0; sl < 2; ++sl) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < NR; ++r) {
                     z1[0] = MFMA16(ff[sl][0][0][r], z0[sl][r], z1[0]);
                     d4 = MFMA4(ff[sl][0][1][r], z0[sl][r], d4);
                 }
-                const f32x4 e = pow_abs4(z0[sl], ex1);
+                const f32x4 e = pow_abs4(z0[sl], ex1);      // (PACK: register 3 is not used, and not computed)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < NR; ++r) {
                     z1[0] = MFMA16(ff[sl][1][0][r], e[r], z1[0]);
                     d4 = MFMA4(ff[sl][1][1][r], e[r], d4);
                 }
+            }
+            if constexpr (PACK) {      // the packed k-step (see k_stage01p): feature 12 of both children, identity in lane groups 0-1, power in 2-3
+                const float s = z0[0][3] + z0[1][3];
+                const float pw = pow_abs(s, ex1);
+                const float b = g < 2 ? s : pw;
+                z1[0] = MFMA16(fl[0], b, z1[0]);
+                d4 = MFMA4(fl[1], b, d4);
             }
             if (STAMP) { unsigned long long t = stamp_now(); t_l0 += t - ts; ts = t; }
         } else {
@@ -966,11 +1004,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     }
 }
 
-StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold) {
+StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold, bool pack) {
 #ifdef HIGSFA_DIAG
+    if (stamp && x_dtype == HG_F32 && fold && pack) return wgq ? (StageFn2)k_stage01d<float, true, true, true, true> : (StageFn2)k_stage01d<float, true, false, true, true>;
     if (stamp && x_dtype == HG_F32 && fold) return wgq ? (StageFn2)k_stage01d<float, true, true, true> : (StageFn2)k_stage01d<float, true, false, true>;
     if (stamp && x_dtype == HG_F32) return wgq ? (StageFn2)k_stage01d<float, true, true> : (StageFn2)k_stage01d<float, true, false>;
 #endif
+    if (fold && pack) {
+        if (!wgq) return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, false, true, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, false, true, true> : (StageFn2)k_stage01d<double, false, false, true, true>;
+        return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, true, true, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, true, true, true> : (StageFn2)k_stage01d<double, false, true, true, true>;
+    }
     if (fold) {
         if (!wgq) return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, false, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, false, true> : (StageFn2)k_stage01d<double, false, false, true>;
         return x_dtype == HG_U8 ? (StageFn2)k_stage01d<uint8_t, false, true, true> : x_dtype == HG_F32 ? (StageFn2)k_stage01d<float, false, true, true> : (StageFn2)k_stage01d<double, false, true, true>;
@@ -1017,7 +1060,17 @@ StageFn pick_stage0p(int x_dtype) {
 // tiles at three waves), the generic form two tiles at three waves (168 VGPRs).
 int stage01p_tiles(bool rem4, bool fspec) { return fspec ? 1 : 2; }
 
-StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold, bool scalar) {
+template <typename XT>
+static StageFn2 pick_stage01p_pack(bool fspec, bool scalar) {      // the folded REM4 forms with the one-row k-steps packed
+    if (scalar) return fspec ? (StageFn2)k_stage01p<XT, false, true, 1, 1, true, true, true> : (StageFn2)k_stage01p<XT, false, true, 2, 0, true, true, true>;
+    return fspec ? (StageFn2)k_stage01p<XT, false, true, 1, 1, true, false, true> : (StageFn2)k_stage01p<XT, false, true, 2, 0, true, false, true>;
+}
+
+StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold, bool scalar, bool pack) {
+    if (pack) {      // a packed plan runs a packed kernel or none (the caller fails on nullptr)
+        if (!(rem4 && fold)) return nullptr;
+        return x_dtype == HG_U8 ? pick_stage01p_pack<uint8_t>(fspec, scalar) : x_dtype == HG_F32 ? pick_stage01p_pack<float>(fspec, scalar) : pick_stage01p_pack<double>(fspec, scalar);
+    }
     if (rem4 && fold && scalar) {
         if (fspec)
             return x_dtype == HG_U8 ? (StageFn2)k_stage01p<uint8_t, false, true, 1, 1, true, true>

@@ -776,6 +776,7 @@ struct Planner : FusedPlan {
             stages[0].name += "  [+ stage 1 fused in the same persistent kernel when the input allows 16-byte loads]";
         }
         if (opt.fold01) plan_fold01(fs);
+        if (opt.fold01_pack) plan_fold01_pack(fs);
         col_base.resize(out_dim);
         col_of.assign((size_t)std::max(prev_nb, 1) * 16, -1);      // inverse map for k_tail: (output block, feature of the tile) -> caller column
         for (int c = 0; c < out_dim; ++c) {
@@ -1681,6 +1682,85 @@ struct Planner : FusedPlan {
         b.name += "  [" + fold01_note + "]";
     }
 
+    // The folded link's one-row k-steps.  A layer-0 node of 13 outputs keeps feature q in register q / 4 of lane group
+    // q % 4, so register 3 holds feature 12 in lane group 0 and padding in the other three: of the folded sum's sixteen k-steps the four
+    // of register 3 (per child and function) carry ONE real k-row each.  Packed, the four k-rows are one k-step, k = lane group:
+    //     0: child 0, feature 12      1: child 1, feature 12      2: |child 0, feature 12|^p      3: |child 1, feature 12|^p.
+    // No cross-lane move: layer 0's first affine itself puts feature 12 where the k-step reads it.  Its fragment and bias get the row
+    // of feature 12 (tile row 3) at rows 3 and 11 for an even node and at rows 7 and 15 — not 3 — for an odd one; these rows are
+    // padding otherwise.  The kernel adds the two children's registers 3 (each lane group: its value plus an exact +0.0), takes the
+    // power of the sum and selects the sum in lane groups 0-1 and the power in 2-3.  Twelve full k-steps and the packed one, 13 in place of
+    // 16; the power is evaluated on seven registers of layer 0 instead of eight.  Every value is plan_fold01's (fold_link's float64, rounded once) or layer 0's own float, moved.
+    // Taken where the link is folded and every layer-0 node has 13 outputs (4 m + 1 with all four k-steps in use) that both functions expand.
+    void plan_fold01_pack(const std::vector<FStage>& fs) {
+        if (stages.size() < 2) return;
+        auto refuse = [&](const std::string& why) {
+            fold01_pack_note = "the link's one-row k-steps stay as they are: " + why;
+            stages[1].name += "  [" + fold01_pack_note + "]";
+        };
+        if (!fold01) return refuse(opt.fold01 ? "the link 0 -> 1 stays as it is" : "the link 0 -> 1 stays as it is (fold01 is off)");
+        const FStage& ch = fs[0];
+        HostStage &a = stages[0], &b = stages[1];
+        for (auto& n : ch.nodes) {
+            const int p0 = n.A1.out;
+            if (p0 != 13)
+                return refuse("a layer-0 node has " + std::to_string(p0) + " outputs, not 13 (4 m + 1: one feature alone in the last register)");
+            if (n.funcs[0].used(p0) != p0 || n.funcs[1].used(p0) != p0) return refuse("a layer-0 function does not expand all 13 outputs");
+        }
+        if (a.kb1 != 1 || a.mt1 != 1 || a.bias_floats < 16) return refuse("internal: layer 0's first affine is not one block");
+        const int nc = a.n_nodes, np = b.n_nodes;
+        a.fold_a1.assign((size_t)nc * 256, 0.f);
+        a.fold_b1.assign((size_t)nc * 16, 0.f);
+        for (int ci = 0; ci < nc; ++ci) {
+            const float* blk = a.afrag.data() + (size_t)ci * a.node_blocks * 256;      // block 0: the first affine; lane (g, i) holds tile row i
+            const float* bias = a.bias.data() + (size_t)ci * a.bias_floats;            // position = tile row
+            float* nb = a.fold_a1.data() + (size_t)ci * 256;
+            float* bb = a.fold_b1.data() + (size_t)ci * 16;
+            std::copy_n(blk, 256, nb);
+            std::copy_n(bias, 16, bb);
+            for (int row : {7, 11, 15}) {
+                bool zero = bias[row] == 0.f;
+                for (int g = 0; g < 4; ++g)
+                    for (int r = 0; r < 4; ++r) zero = zero && blk[((g * 16 + row) * 4) + r] == 0.f;
+                if (!zero) fail(HG_ERR_FORMAT, "internal: a padding row of layer 0's first affine is in use");
+            }
+            auto copy_row = [&](int to) {
+                for (int g = 0; g < 4; ++g)
+                    for (int r = 0; r < 4; ++r) nb[((g * 16 + to) * 4) + r] = blk[((g * 16 + 3) * 4) + r];
+                bb[to] = bias[3];
+            };
+            if (ci & 1) {
+                copy_row(7);
+                copy_row(15);
+                for (int g = 0; g < 4; ++g)
+                    for (int r = 0; r < 4; ++r) nb[((g * 16 + 3) * 4) + r] = 0.f;
+                bb[3] = 0.f;
+            } else {
+                copy_row(11);
+            }
+        }
+        b.fold_last.assign((size_t)np * 2 * 64, 0.f);
+        for (int q = 0; q < np; ++q)
+            for (int sl = 0; sl < 2; ++sl)
+                for (int fi = 0; fi < 2; ++fi)
+                    for (int mt = 0; mt < 2; ++mt) {
+                        float* blk = b.fold_frag.data() + ((((size_t)q * 2 + sl) * 2 + fi) * 2 + mt) * 256;
+                        const int g = 2 * fi + sl;
+                        // lane (0, i), register 3 = k-row (function fi, feature 12) at the tile's row i (4x4 form: at row 4 (i % 4))
+                        for (int i = 0; i < 16; ++i) b.fold_last[((size_t)q * 2 + mt) * 64 + g * 16 + i] = blk[i * 4 + 3];
+                        for (int lane = 0; lane < 64; ++lane) blk[lane * 4 + 3] = 0.f;
+                    }
+        const int64_t before = padded_flops;
+        b.mfma16_tile -= 3 * (int64_t)np;
+        b.mfma4_tile -= 3 * (int64_t)np;
+        padded_flops -= (3 * (int64_t)np * 2048 + 3 * (int64_t)np * 512) / 16;
+        fold01_flops += padded_flops - before;
+        fold01_pack = true;
+        fold01_pack_note = "one-row k-steps packed: feature 12 of both children and both functions in ONE k-step behind twelve full ones, this layer then issues " +
+                           std::to_string(b.mfma16_tile) + " x 16x16x4 + " + std::to_string(b.mfma4_tile) + " x 4x4x1";
+        b.name += "  [" + fold01_pack_note + "]";
+    }
+
     // Layers 0 and 1 can share one kernel when a wave's two layer-0 node slots are exactly the two
     // children of one layer-1 node (see k_stage01p).
     bool can_fuse01() const {
@@ -1774,6 +1854,7 @@ std::unique_ptr<const FusedPlan> build_fused_plan(const TNode& root, const Fused
                 FusedOptions o = opt;
                 o.hoist = false;
                 o.fold01 = false;
+                o.fold01_pack = false;
                 given = Planner(root, std::move(plain), o).padded_flops;
             } catch (const Error&) {
             }

@@ -50,6 +50,8 @@ struct FusedOptions {
                                   // not an environment switch of the planner: the executor turns it on unless HIGSFA_NO_HOIST is set
     bool fold01 = false;          // fold layer 0's second affine into layer 1's first inside the front kernels (Planner::plan_fold01); like hoist,
                                   // the executor's switch: on unless HIGSFA_NO_FOLD01 is set
+    bool fold01_pack = false;     // with fold01: the four one-row k-steps of the folded link (feature 12 of a 13-output layer 0, per child and function) packed
+                                  // into ONE k-step (Planner::plan_fold01_pack); the executor's switch: on unless HIGSFA_NO_FOLD01_PACK is set
     bool pair = false;            // record, for hoisted stages whose parents all have two children, what the layer below needs to store
                                   // (bias + child 0) + child 1 once per parent (Planner::plan_pairs); rides on hoist, and like it
                                   // the executor's switch: on unless HIGSFA_NO_PAIR is set
@@ -130,6 +132,15 @@ struct HostStage {
     // fold_frag [node][child 0..1][function 0..1][tile: 0 = 16x16 form, 1 = 4x4 form][lane][4]: A fragments of F_c = A2_c A1[rows of c, :]
     // (k = z0 feature 4 r + lane group of child c, per function; rows = z1 features), fold_bias [node][2 x 16]: z1's ONE bias vector.
     std::vector<float> fold_frag, fold_bias;
+    // ... with its four one-row k-steps packed (FusedPlan::fold01_pack; layer-0 nodes of 13 outputs: feature 12 sits alone in register 3).  The
+    // k-steps of register 3 are gone from fold_frag (zeros) and ONE k-step carries their four k-rows, k = lane group: 0 = child 0's feature 12,
+    // 1 = child 1's, 2 = |child 0's|^p, 3 = |child 1's|^p.
+    // fold_last [node][tile: 0 = 16x16 form, 1 = 4x4 form][lane]: that k-step's A fragments (lane (g, i): row (child g % 2, function g / 2,
+    // feature 12) of F_c at the tile's row i) — stage 1.
+    // fold_a1 [node][lane][4], fold_b1 [node][16]: STAGE 0's first-affine block and first bias with feature 12 (tile row 3) repeated where the
+    // packed k-step reads it — rows 3 and 11 of an even node, rows 7 and 15 of an odd node, whose row 3 is zero — so that the sum of the two
+    // children's registers 3 holds (c0, c1, c0, c1) by lane group, each value plus an exact +0.0.  Those rows are padding in afrag / bias.
+    std::vector<float> fold_last, fold_a1, fold_b1;
     // Summed link (FusedOptions::pair; hoisted stages whose nodes all have exactly two children).  The layer below may then store ONE tile set
     // per node of this stage, (bias + child 0's tiles) + child 1's tiles, in place of its own two (k_stage_sum_pair); this stage reads it as a
     // hoisted stage of one child per node whose first bias adds nothing.  Empty where the stage has no pairs.
@@ -144,6 +155,8 @@ struct FusedPlan {
     bool s0_transpose = false, fuse01 = false;
     bool fold01 = false;                // the front kernels run the link 0 -> 1 folded (stages[1].fold_frag / fold_bias); implies fuse01
     std::string fold01_note;            // why, or why not (stage 1's line of hg_flow_describe); empty where FusedOptions::fold01 is off
+    bool fold01_pack = false;           // ... with the four one-row k-steps packed into one (stages[1].fold_last, stages[0].fold_a1 / fold_b1); implies fold01
+    std::string fold01_pack_note;       // why, or why not (appended to stage 1's line); empty where FusedOptions::fold01_pack is off
     std::vector<HostStage> stages;
     std::vector<int32_t> col_base, col_of;
     int tail_begin = -1;          // first stage of the top-of-hierarchy launch (k_tail); -1: none

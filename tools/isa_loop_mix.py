@@ -1,10 +1,11 @@
 """Instruction mix of the front kernel's pass loop from the compiler's ISA listing (where do the vector
 instructions between the MFMAs come from?).
 
-    python tools/isa_loop_mix.py [--keep DIR] [--fold]
+    python tools/isa_loop_mix.py [--keep DIR] [--fold [--pack]]
 
 compiles pyfaceanalysis_amd/csrc/hg_fused_front.hip with --save-temps, takes k_stage01d<float, false, true, false> (--fold:
-<float, false, true, true>, the link 0 -> 1 folded: the instantiation the headline runs), cuts out the pass loop (the outermost loop of the kernel) and prints per class — MFMA, transcendental,
+<float, false, true, true>, the link 0 -> 1 folded; with --pack <float, false, true, true, true>, its one-row k-steps packed: the
+instantiation the headline runs), cuts out the pass loop (the outermost loop of the kernel) and prints per class — MFMA, transcendental,
 other vector ALU, LDS, vector memory, scalar — the count and an attribution of the vector instructions to their source
 constructs (by opcode and by the value they produce).  Counts are per pass and wave over ALL paths of the loop (grabber and
 follower branches of the tile queue, error paths), so the scalar / readfirstlane figures are upper bounds for one wave."""
@@ -17,7 +18,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "pyfaceanalysis_amd", "csrc", "hg_fused_front.hip")
-KERNEL = "_ZN2hg5fused10k_stage01dIfLb0ELb1ELb%dEEEvNS0_11StageParamsES2_" % (1 if "--fold" in sys.argv else 0)
+KERNEL = "_ZN2hg5fused10k_stage01dIfLb0ELb1ELb%dELb%dEEEvNS0_11StageParamsES2_" % (1 if "--fold" in sys.argv else 0, 1 if "--pack" in sys.argv else 0)
 
 
 def main():
