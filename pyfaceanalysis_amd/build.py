@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhigsfa.so")
-SOURCES = ["hg_tree.cpp", "hg_capi.cpp", "hg_hostpack.cpp", "hg_resample.cpp", "hg_normalize.cpp", "hg_normalize.hip", "hg_generic.hip", "hg_fused_plan.cpp", "hg_fused.hip", "hg_fused_sum.hip", "hg_fused_front.hip", "hg_fused_igsfa.hip", "hg_fused_prod.hip", "hg_fused_tail.hip",
+SOURCES = ["hg_tree.cpp", "hg_capi.cpp", "hg_hostpack.cpp", "hg_resample.cpp", "hg_normalize.cpp", "hg_normalize.hip", "hg_generic.hip", "hg_fused_plan.cpp", "hg_fused_call.cpp", "hg_fused.hip", "hg_fused_sum.hip", "hg_fused_front.hip", "hg_fused_igsfa.hip", "hg_fused_prod.hip", "hg_fused_tail.hip",
            "hg_gauss.hip", "hg_extract.hip", "hg_resample.hip", "hg_cascade.hip", "hg_eyes.hip", "hg_estimate.hip", "hg_train.hip"]
 HEADERS = ["hg_common.hpp", os.path.join("..", "..", "include", "higsfa.h")]
 # no HIP in them: built with g++ (function multiversioning, which the device pass rejects), with these extra flags.  hg_resample.cpp

@@ -622,7 +622,7 @@ StageFn pick_stage(int mt1, int mt2, int T, bool rem = false, int kbf = 0, bool 
 
 
 // ---- the executor --------------------------------------------------------------------------------
-constexpr int kWeightLdsKiB = 64;       // target size of a node group's weights in LDS
+// What a call launches — route and shape per stage — is the call plan's (hg_fused_call.hpp, host only); here its steps are carried out.
 
 // Device mirrors of the plan's tables (hg_fused_plan.hpp): one StageDev per stage and one SubRunDev per sub-tree run, in the plan's
 // order; filled by to_device(), freed by release().
@@ -651,6 +651,7 @@ struct Lane {
     WorkQueue wq_front, wq_direct, wq_direct_wg;
     int32_t* err_host = nullptr;          // error word the polling kernels write (device_error_word)
     int32_t* err_dev = nullptr;
+    std::vector<CallStep> steps;          // the call being enqueued (plan_call): sized by the first call, refilled by every one
 };
 
 class FusedExecutor : public Executor {
@@ -791,7 +792,11 @@ public:
     void run_range(Lane& L, const void* x, int x_dtype, int64_t n, int64_t ldx, void* y, int y_dtype, int64_t y_cols, int64_t ldy,
                    hipStream_t st, hipEvent_t* ev) {
         const int n_tiles = (int)((n + 15) / 16);
-        const int sub_set = plan_->pick_sub_set(n_tiles);
+        FrontInput fi;
+        fi.vec4_ok = rows_vec4(x, ldx, x_dtype);
+        fi.x_dtype = x_dtype;
+        fi.ldx = ldx;
+        plan_call(*plan_, n_tiles, fi, L.steps);
         int e = 0;
         auto record = [&](int k) {      // k events after the last launch: one per stage it covered (the first carries its time)
             if (ev)
@@ -800,55 +805,51 @@ public:
         record(1);
         f32x4* cur = (f32x4*)L.bufA.p;
         f32x4* nxt = (f32x4*)L.bufB.p;
-        bool in_summed = false;      // the stage about to run reads ONE tile set per node (the stage below stored the link summed)
-        for (int si = 0; si < (int)plan_->stages.size(); ++si) {
-            if (in_summed && !on_sweep(si, n_tiles, sub_set)) fail(HG_ERR_STATE, "internal: stage %d was handed a summed link but does not run the node-group sweep", si);
-            if (plan_->tail_begin >= 0 && si == plan_->tail_start(n_tiles)) {
+        for (const CallStep& step : L.steps) {
+            const int si = step.stage;
+            if (step.route == Route::Top) {
+                debug_line(step, 0, 1);
                 launch_top(si, cur, n_tiles, y, y_dtype, y_cols, ldy, n, st);
-                record((int)plan_->stages.size() + 1 - si);      // this stage, the ones above and the unpack pass it replaces
+                record(step.covered + 1);      // this stage, the ones above and the unpack pass it replaces
                 HG_HIP(hipGetLastError());
                 return;
             }
-            const SubRun* sr = nullptr;
-            const SubRunDev* sd = nullptr;
-            for (size_t ri = 0; ri < plan_->sub_runs.size(); ++ri) {
-                const SubRun& r = plan_->sub_runs[ri];
-                if (r.begin == si && r.set == sub_set && plan_->sub_run_pays(r, n_tiles)) { sr = &r; sd = &sub_dev_[ri]; }
-            }
-            if (sr) {
-                launch_subtrees(*sr, *sd, cur, nxt, n_tiles, st);
+            if (step.route == Route::Subtree) {
+                debug_line(step, 0, 1);
+                launch_subtrees(plan_->sub_runs[step.sub_run], sub_dev_[step.sub_run], cur, nxt, n_tiles, st);
                 std::swap(cur, nxt);
-                record(sr->len);
-                si += sr->len - 1;
+                record(step.covered);
                 continue;
             }
             const HostStage& s = plan_->stages[si];
             const StageDev& d = dev_[si];
             StageParams P = stage_params(s, d, cur, nxt, n_tiles);
-            int covered = 1;
-            if (s.kind == 1)      // row-major input -> fragment order
-                launch_im2frag(x, x_dtype, ldx, n, n_tiles, s.nb_out, (const int32_t*)d.gcol.p, nxt, vec4_ok(s, x, ldx, x_dtype) ? 1 : 0, st);
-            else if (s.kind == 2)
-                launch_igsfa(s, P, n_tiles, si, st);
-            else if (s.from_x)
-                covered = launch_front(L, s, d, P, x, x_dtype, ldx, n, n_tiles, cur, st) ? 2 : 1;
-            else if (s.kind == 3)
-                launch_prod(s, d, P, n_tiles, si, st);
-            else if (!launch_splitm(s, P, n_tiles, st)) {
-                if (in_summed) {      // a hoisted stage of one child per node whose first bias adds nothing: (-0.0f) + x == x
-                    P.kb1tab = (const int2*)d.kb1tab_pre.p;
-                    P.bias = (const float*)d.bias_pre.p;
-                    P.kb1 = s.mt1;
-                    P.n_kids = 1;
-                    P.nb_in = s.n_nodes * s.mt1;
-                }
-                in_summed = link_summed(si, n_tiles, sub_set, in_summed);
-                if (in_summed) launch_stage_pair(s, plan_->stages[si + 1], dev_[si + 1], P, n_tiles, si, st);
-                else launch_stage(s, P, n_tiles, si, st);
+            switch (step.route) {
+                case Route::Gather:      // row-major input -> fragment order
+                    debug_line(step, 0, 1);
+                    launch_im2frag(x, x_dtype, ldx, n, n_tiles, s.nb_out, (const int32_t*)d.gcol.p, nxt, step.sh.vec4 ? 1 : 0, (unsigned)step_blocks(step, 1), st);
+                    break;
+                case Route::IgSweep:
+                case Route::IgSplit: launch_igsfa(step, s, P, st); break;
+                case Route::Front01d:
+                case Route::Front01p: launch_front_pair(L, step, s, d, P, x, x_dtype, ldx, n, n_tiles, cur, st); break;
+                case Route::Front0p:
+                case Route::Front0: launch_front(step, s, d, P, x, x_dtype, ldx, n, st); break;
+                case Route::ProdSweep: launch_prod(step, s, d, P, st); break;
+                case Route::Splitm: launch_splitm(step, s, P, st); break;
+                default:
+                    if (step.in_summed) {      // a hoisted stage of one child per node whose first bias adds nothing: (-0.0f) + x == x
+                        P.kb1tab = (const int2*)d.kb1tab_pre.p;
+                        P.bias = (const float*)d.bias_pre.p;
+                        P.kb1 = step.sh.kb1;
+                        P.n_kids = step.sh.n_kids;
+                        P.nb_in = s.n_nodes * s.mt1;
+                    }
+                    if (step.route == Route::SumPair) launch_stage_pair(step, s, plan_->stages[si + 1], dev_[si + 1], P, st);
+                    else launch_stage(step, s, P, st);
             }
-            if (covered == 1) std::swap(cur, nxt);      // (fused front: layer 1 wrote `cur`, which stage 2 reads)
-            record(covered);
-            si += covered - 1;
+            if (step.covered == 1) std::swap(cur, nxt);      // (fused front: layer 1 wrote `cur`, which stage 2 reads)
+            record(step.covered);
         }
         launch_unpack(cur, n, y, y_dtype, y_cols, ldy, st);
         record(1);
@@ -871,6 +872,7 @@ private:
         L.bufA.alloc(need);
         L.bufB.alloc(need);
         L.cap_rows = std::max(L.cap_rows, tiles * 16);
+        L.steps.reserve(plan_->stages.size());
     }
     void release_lane(Lane& L) {
         L.bufA.free();
@@ -976,47 +978,30 @@ private:
         return R;
     }
 
-    // 16-byte loads of the caller's rows (4-byte for uint8): the row gather and the front kernels
-    static bool vec4_ok(const HostStage& s, const void* x, int64_t ldx, int x_dtype) {
+    // the caller's rows allow 16-byte loads (4-byte for uint8): FrontInput::vec4_ok, for the row gather and the front kernels
+    static bool rows_vec4(const void* x, int64_t ldx, int x_dtype) {
         const size_t esz = dtype_size(x_dtype), valign = x_dtype == HG_U8 ? 4 : 16;
-        return s.vec_ok && ldx % 4 == 0 && ((uintptr_t)x % valign) == 0 && (ldx * esz) % valign == 0;
+        return ldx % 4 == 0 && ((uintptr_t)x % valign) == 0 && (ldx * esz) % valign == 0;
     }
 
-    // waves x tiles per workgroup of a node-group sweep (k_stage, k_stage_prod): the first of `cand` that still gives every CU a
-    // workgroup (>= 256 over n_groups node groups); never fewer than 4 waves to copy a node's weights unless the batch is tiny
-    struct Shape {
-        int nw, T;
-    };
-    template <size_t N>
-    static Shape sweep_shape(const int (&cand)[N][2], int n_tiles, int n_groups) {
-        Shape sh{4, 1};
-        for (auto& c : cand) {
-            const int64_t tg = (n_tiles + c[0] * c[1] - 1) / (c[0] * c[1]);
-            if (c[0] * c[1] <= n_tiles && tg * n_groups >= 256) {
-                sh = {c[0], c[1]};
-                break;
-            }
-        }
-        while (sh.nw * sh.T > std::max(n_tiles, 1) && sh.nw > 1) sh.nw >>= 1;
-        return sh;
+    // The step's sweep parameters, from its shape and — the second phase of the call plan — the occupancy of the kernel the shape
+    // mapped to.  Returns the grid.
+    int64_t fill_sweep(const CallStep& step, StageFn fn, StageParams& P) {
+        const CallShape& sh = step.sh;
+        const int occ = resident_blocks(fn, sh.threads, sh.lds);
+        P.nodes_per_group = sh.per_group;
+        P.nodes_per_wg = sh.per_group;
+        P.n_chunks = sh.n_groups;
+        P.tile_groups = sh.tile_groups;
+        P.tile_parts = step_tile_parts(step, occ);
+        debug_line(step, occ, P.tile_parts);
+        return step_blocks(step, P.tile_parts);
     }
 
-    // Persistent sweep: each workgroup copies its node group's weights once and walks tile groups part, part + tile_parts, ...
-    // cost(parts) = rounds of resident workgroups (occ per CU; node groups padded to 8) x (weight copy + tile iterations per workgroup)
-    static int sweep_tile_parts(int n_groups, int tile_groups, int occ) {
-        const double capacity = 256.0 * occ;
-        const int64_t g8 = (int64_t)(n_groups + 7) / 8 * 8;
-        int tile_parts = 1;
-        double best = 1e300;
-        for (int pp = 1; pp <= tile_groups; ++pp) {
-            const double rounds = std::ceil(g8 * pp / capacity);
-            const double cost = rounds * (0.35 + (double)((tile_groups + pp - 1) / pp));
-            if (cost < best - 1e-9) {
-                best = cost;
-                tile_parts = pp;
-            }
-        }
-        return tile_parts;
+    void debug_line(const CallStep& step, int occ, int tile_parts) const {
+        if (!plan_->opt.debug) return;
+        char buf[512];
+        fprintf(stderr, "%s\n", format_step(*plan_, step, occ, tile_parts, buf, sizeof buf));
     }
 
     // the top of the hierarchy as one launch that ends in the caller's rows (hg_fused_tail.hip)
@@ -1047,64 +1032,27 @@ private:
 #endif
     }
 
-    // iGSFA layer: the folded top of a hierarchy in small workgroups (k_igfold split), else k_igfold (folded) / k_igsfa (unfolded)
-    void launch_igsfa(const HostStage& s, StageParams& P, int n_tiles, int si, hipStream_t st) {
-        if (s.ig_folded && s.n_nodes <= 8 && s.nf <= 2 && s.kb1 <= 8 && (int64_t)s.n_nodes * n_tiles <= 16384) {
-            // top of an iGSFA hierarchy: one node and two tiles per small workgroup, output tiles split over waves
+    // iGSFA layer: the folded top of a hierarchy in small workgroups (k_igfold_split), else k_igfold (folded) / k_igsfa (unfolded)
+    void launch_igsfa(const CallStep& step, const HostStage& s, StageParams& P, hipStream_t st) {
+        const CallShape& sh = step.sh;
+        if (step.route == Route::IgSplit) {
             P.ig_folded = 1;
-            launch_igfold_split(P, s.mt2, n_tiles, st);
+            debug_line(step, 0, 1);
+            launch_igfold_split(P, s.mt2, sh.T, (unsigned)step_blocks(step, 1), sh.threads, sh.lds, st);
             return;
         }
-        // Waves that take tiles (nwt) x tiles per wave (T): the largest shape that still gives every CU
-        // a workgroup (the top layers have 16 .. 1 nodes: with 8 x 2 a single node would run on 16 CUs).
-        // Measured on the 11-layer net (us per layer, 4096 rows): 8x2 beats 4x2 / 16x1 / 8x1 wherever
-        // it fills the chip; T = 1 loses 30-50 % (half the MFMAs per A fragment read from LDS) even where it
-        // is the only way to give every CU a workgroup; waves
-        // per workgroup must be a multiple of 4 (6x2 places 2,2,1,1 waves on the SIMDs and a second
-        // workgroup no longer fits).  Nodes of 5-6 input blocks fit 3 waves per SIMD: 12x2 there.
-        const size_t ig_lds = (size_t)s.node_blocks * 1024 + (size_t)s.bias_floats * 4 + (size_t)s.kb1 * 8;
-        int nwt = 1, T = 1;
-        static const int cand[][2] = {{12, 2}, {8, 2}, {4, 2}};
-        for (auto& c : cand) {
-            if (c[0] == 12 && (s.ig_folded || !(s.kb1 == 5 || s.kb1 == 6))) continue;   // k_igfold: <= 8 waves
-            const int64_t tg = (n_tiles + c[0] * c[1] - 1) / (c[0] * c[1]);
-            if (c[0] * c[1] <= std::max(n_tiles, 1) && tg * s.n_nodes >= 256) {
-                nwt = c[0];
-                T = c[1];
-                break;
-            }
-        }
-        if (nwt == 1 && T == 1) {
-            // too few (node, tile) pairs to fill the chip: still two tiles per wave — 4 x 2 with 32
-            // workgroups beats 1 x 1 with 256 by a third on the single top node (every workgroup
-            // copies the node's 64-80 KiB of weights, and T = 1 halves the MFMAs per LDS read)
-            T = n_tiles >= 2 ? 2 : 1;
-            nwt = n_tiles >= 8 ? 4 : n_tiles >= 4 ? 2 : 1;
-        }
-        // folded layers stream their input blocks (k_igfold)
-        const bool ig_fs = s.ig_folded && s.nf == 2 && s.funcs[0].kind == E_IDENTITY && s.funcs[1].kind == E_ABS_POW && !plan_->opt.no_fspec;
-        StageFn fn = s.ig_folded ? pick_igfold(s.mt2, T, ig_fs) : pick_igsfa(s.mt1, s.mt2, T, s.kb1);
-        const int ig_occ = resident_blocks(fn, std::max(nwt, 4) * 64, ig_lds);
-        const int nw = std::max(nwt, 4);   // never fewer than 4 waves to copy a node's weights
-        P.nodes_per_wg = nwt;
+        StageFn fn = s.ig_folded ? pick_igfold(s.mt2, sh.T, sh.fs) : pick_igsfa(s.mt1, s.mt2, sh.T, s.kb1);
+        const int64_t blocks = fill_sweep(step, fn, P);
+        P.nodes_per_wg = sh.nw;      // (k_igsfa / k_igfold: the waves of a workgroup that take batch tiles)
         P.ig_has_lr = s.ig_has_lr ? 1 : 0;
         P.ig_folded = s.ig_folded ? 1 : 0;
         P.nk2p[0] = 0;
         for (int ms = 0; ms < s.mt1; ++ms) P.nk2p[0] |= (uint32_t)s.ig_nks[ms] << (4 * ms);
-        P.tile_groups = (n_tiles + nwt * T - 1) / (nwt * T);
-        const int npg = 1;   // one node per workgroup measured fastest (236/180 us vs 246-288/220-269 us with 32-96 KiB groups on the 11-layer net)
-        P.nodes_per_group = npg;
-        P.n_chunks = (s.n_nodes + npg - 1) / npg;
-        P.tile_parts = std::max(1, std::min(P.tile_groups, 256 * ig_occ / std::max(1, P.n_chunks)));
-        set_lds_limit(fn, ig_lds);
-        if (plan_->opt.debug) fprintf(stderr, "[igsfa stage %d] nodes %d kb1 %d shape %dx%d occ %d lds %zu tile_groups %d parts %d\n", si, s.n_nodes, s.kb1, nwt, T, ig_occ, ig_lds, P.tile_groups, P.tile_parts);
-        hipLaunchKernelGGL(fn, (unsigned)(P.n_chunks * P.tile_parts), nw * 64, ig_lds, st, P);
+        hipLaunchKernelGGL(fn, (unsigned)blocks, sh.threads, sh.lds, st, P);
     }
 
-    // Stage 0, which reads the caller's rows.  Returns true where stage 1 ran fused in the same launch (k_stage01d / k_stage01p,
-    // writing out1 where its own launch would); else k_stage0p (persistent) or k_stage0.
-    bool launch_front(Lane& L, const HostStage& s, const StageDev& d, StageParams& P, const void* x, int x_dtype, int64_t ldx, int64_t n, int n_tiles, f32x4* out1,
-                      hipStream_t st) {
+    // what every first-layer kernel reads of the caller's rows and of stage 0's tables
+    void front_params(const CallStep& step, const HostStage& s, const StageDev& d, StageParams& P, const void* x, int64_t ldx, int64_t n) const {
         P.chunks = (const DChunk*)d.chunks.p;
         P.runs = (const DRun*)d.runs.p;
         P.piece_col = (const int2*)d.piece.p;
@@ -1117,142 +1065,85 @@ private:
         P.lds_stride = s.lds_stride;
         P.nk_last = s.nk_last;
         P.contig4 = s.contig4 ? 1 : 0;
-        P.n_chunks = (int)s.chunks.size();
-        P.vec4 = vec4_ok(s, x, ldx, x_dtype) ? 1 : 0;
-        const int T = (n_tiles >= 4 && s.mt1 * s.mt2 <= 4) ? 4 : 1;
-        const int groups = (n_tiles + T - 1) / T;
-        const size_t lds_bytes = (size_t)T * 16 * s.lds_stride * 4;
-        bool rem4 = false, fspec = false;
-        if (plan_->fuse01) {
-            // second tiles of both layer-1 affines hold <= 4 real rows: 4x4x1 MFMA form (HIGSFA_NO_REM4: off)
-            rem4 = plan_->stages[1].rem4 || (plan_->stages[1].p_max <= 20 && plan_->stages[1].s_max <= 20 && plan_->stages[1].nk2[1][0] <= 1 &&
-                                       plan_->stages[1].nk2[1][1] <= 1 && !plan_->opt.no_rem4);
-            auto id_pow = [](const HostStage& hs) { return hs.nf == 2 && hs.funcs[0].kind == E_IDENTITY && hs.funcs[1].kind == E_ABS_POW; };
-            fspec = id_pow(s) && id_pow(plan_->stages[1]) && !plan_->opt.no_fspec;
-        }
-        const int FT = stage01p_tiles(rem4, fspec);      // batch tiles per pass of the fused front kernel
-        // A folded plan has ONE arithmetic, the front pair kernels': they also take what otherwise falls through to the unfused
-        // kernels — a batch shorter than a pass (k_stage01p guards every tile and row) and rows that allow no 16-byte loads
-        // (k_stage01p's scalar staging branch).
-        const bool fold = plan_->fold01;
-        if (fold && !(rem4 && plan_->fuse01)) fail(HG_ERR_STATE, "internal: the link 0 -> 1 is folded but the front kernel's remainder-tile form does not apply");
-        const bool pack = plan_->fold01_pack;      // the folded link's one-row k-steps packed: the PACK instantiations and no others
-        if (pack && !fold) fail(HG_ERR_STATE, "internal: packed k-steps on a plan whose link 0 -> 1 is not folded");
-        if (plan_->fuse01 && ((P.vec4 && n_tiles >= FT) || fold)) {
-            // layers 0 and 1 in one persistent kernel; layer 1 writes where its own launch would
-            StageParams Q = stage_params(plan_->stages[1], dev_[1], nullptr, out1, n_tiles);
-            if (pack && (!Q.fold_last || P.bias_floats != 16)) fail(HG_ERR_STATE, "internal: a packed plan without its packed fragments on the device");
-            // every wave on its own (k_stage01d) where the input layout allows it, else the LDS-staged kernel
-            const size_t esz = dtype_size(x_dtype);
-            const bool direct = P.vec4 && fspec && rem4 && s.direct_ok && plan_->stages[1].pack_out && (int64_t)16 * ldx * (int64_t)esz + 2048 < 0x7fffffffll && s.max_chunk_nodes <= 8 && !plan_->opt.no_direct;   // (k_stage01d: 32-bit byte offsets inside a tile's rows; at most four waves)
-            const bool wgq = !plan_->opt.no_wgq;       // k_stage01d: one tile queue per chunk, shared by the waves of a workgroup
-            StageFn2 fn = direct ? pick_stage01d(x_dtype, false, wgq, fold, pack) : pick_stage01p(x_dtype, false, rem4, fspec, fold, fold && !P.vec4, pack);
-            if (!fn) fail(HG_ERR_STATE, "internal: no packed front kernel for this plan");      // never an unpacked kernel on packed fragments
-            const int thr01 = 64 * std::max(1, (s.max_chunk_nodes + 1) / 2);   // one wave per pair of layer-0 nodes
-            // LDS: the tile buffers of FT batch tiles (k_stage01p only) + 10 vectors of 16 floats (means, biases) per wave
-            const size_t lds2 = direct ? (size_t)4 * 160 * 4 + 32 * 4 + (size_t)4 * 256 * 4      // constants | ring + progress words | reduction scratch per wave
-                                       : (size_t)(kDoubleBuffer01 ? 2 : 1) * FT * 16 * s.lds_stride * 4 + (size_t)(thr01 / 64) * 160 * 4 + 16;   // + tile-group queue slots
-            const int groups2 = (n_tiles + FT - 1) / FT;
-            const int occ = resident_blocks((StageFn)fn, thr01, lds2);
-            P.tile_parts = std::max(1, std::min(groups2, 256 * occ / std::max(1, P.n_chunks)));
-            if (plan_->opt.debug) fprintf(stderr, "[front] occ %d threads %d lds %zu chunks %d tile_parts %d\n", occ, thr01, lds2, P.n_chunks, P.tile_parts);
-#ifdef HIGSFA_DIAG
-            if (plan_->opt.stamp_stage == 0 && x_dtype == HG_F32 && (direct || !fold)) {      // (the folded k_stage01p has no stamped form)
-                fn = direct ? pick_stage01d(HG_F32, true, wgq, fold, pack) : pick_stage01p(HG_F32, true, rem4, fspec, fold);
-                stamps_begin(P, P.n_chunks * P.tile_parts, 12, st);
-            }
-#endif
-            P.err = device_error_word(L);
-            {   // k_stage01p: one queue of tile groups per chunk; k_stage01d: one queue of tiles per layer-1 node (or per chunk)
-                WorkQueue& wq = direct ? (wgq ? L.wq_direct_wg : L.wq_direct) : L.wq_front;
-                P.work_ctr = work_counters(wq, direct && !wgq ? plan_->stages[1].n_nodes : P.n_chunks, st);
-                P.work_base = wq.base;
-                wq.base += (uint32_t)groups2;      // what this launch adds to every counter (StageParams::work_ctr)
-            }
-#ifdef HIGSFA_DIAG
-            if (const char* e = getenv("HIGSFA_WHATIF")) P.whatif = atoi(e);
-#endif
-            hipLaunchKernelGGL(fn, (unsigned)(P.n_chunks * P.tile_parts), thr01, lds2, st, P, Q);
-#ifdef HIGSFA_DIAG
-            if (P.stamps) front_stamps_report(P.n_chunks, st);
-#endif
-            return true;
-        }
-        if (fold) fail(HG_ERR_STATE, "internal: an unfused first-layer kernel on a plan whose link 0 -> 1 is folded");
-        const bool persistent = T == 4 && P.vec4 && s.contig4 && s.has_exp && s.mt1 == 1 && s.mt2 == 1 && s.kb1 == 1 &&
-                                s.nf <= 2 && s.max_chunk_nodes <= 16 && 64 * s.max_chunk_pieces <= 8 * 512;
-        if (persistent) {
-            StageFn fn = pick_stage0p(x_dtype);
-            const int occ = resident_blocks(fn, 512, lds_bytes);
-            P.tile_parts = std::max(1, std::min(groups, 256 * occ / std::max(1, P.n_chunks)));
-            hipLaunchKernelGGL(fn, (unsigned)(P.n_chunks * P.tile_parts), 512, lds_bytes, st, P);
-        } else {
-            const int64_t blocks = (int64_t)groups * P.n_chunks;
-            if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
-            StageFn fn = pick_stage0(s.mt1, s.mt2, T, x_dtype);
-            set_lds_limit(fn, lds_bytes);
-            hipLaunchKernelGGL(fn, (unsigned)blocks, T == 4 ? 512 : 256, lds_bytes, st, P);
-        }
-        return false;
+        P.n_chunks = step.sh.n_groups;
+        P.vec4 = step.sh.vec4 ? 1 : 0;
     }
 
-    // k_stage_splitm (one node and T tiles per small workgroup, weights straight from L2, no LDS copy): the top of the
-    // hierarchy at any batch size, and EVERY ordinary layer while its grid is small enough to be resident at once —
-    // a k_stage workgroup first copies 27-52 KiB of weights into LDS (5 us), which small batches never earn back
-    // (N = 16: 92 -> 70 us per call, N = 340: 137 -> 129, N = 1024: the same; grids of more than ~500 workgroups: k_stage wins).
-    // Returns false where the layer does not qualify.
-    // (the qualifying test alone, which launches nothing: run_range asks it about the NEXT layer too)
-    bool splitm_takes(const HostStage& s, int n_tiles) const {
-        const int T = n_tiles >= 2 * 256 / std::max(1, s.n_nodes) ? 2 : 1;
-        const int groups = (n_tiles + T - 1) / T;
-        const int64_t wgs = (int64_t)groups * s.n_nodes;
-        return s.kind == 0 && (!s.rem4 || s.mt1 == s.mt2) && (s.rem4 || !s.pack_out) && s.mt1 * s.nf <= 8 &&
-               (s.n_nodes <= plan_->opt.splitm_max_nodes ? (int64_t)s.n_nodes * n_tiles <= 8192 : wgs <= plan_->opt.splitm_max_wgs);
+    // layers 0 and 1 in one persistent kernel (k_stage01d / k_stage01p); layer 1 writes out1, where its own launch would
+    void launch_front_pair(Lane& L, const CallStep& step, const HostStage& s, const StageDev& d, StageParams& P, const void* x, int x_dtype, int64_t ldx, int64_t n,
+                           int n_tiles, f32x4* out1, hipStream_t st) {
+        const CallShape& sh = step.sh;
+        const bool direct = step.route == Route::Front01d;
+        front_params(step, s, d, P, x, ldx, n);
+        StageParams Q = stage_params(plan_->stages[1], dev_[1], nullptr, out1, n_tiles);
+        if (sh.pack && (!Q.fold_last || P.bias_floats != 16)) fail(HG_ERR_STATE, "internal: a packed plan without its packed fragments on the device");
+        StageFn2 fn = direct ? pick_stage01d(x_dtype, false, sh.wgq, sh.fold, sh.pack) : pick_stage01p(x_dtype, false, sh.rem4, sh.fspec, sh.fold, sh.scalar, sh.pack);
+        if (!fn) fail(HG_ERR_STATE, "internal: no packed front kernel for this plan");      // never an unpacked kernel on packed fragments
+        const int occ = resident_blocks((StageFn)fn, sh.threads, sh.lds);
+        P.tile_parts = step_tile_parts(step, occ);
+        debug_line(step, occ, P.tile_parts);
+        const unsigned blocks = (unsigned)step_blocks(step, P.tile_parts);
+#ifdef HIGSFA_DIAG
+        if (plan_->opt.stamp_stage == 0 && x_dtype == HG_F32 && (direct || !sh.fold)) {      // (the folded k_stage01p has no stamped form)
+            fn = direct ? pick_stage01d(HG_F32, true, sh.wgq, sh.fold, sh.pack) : pick_stage01p(HG_F32, true, sh.rem4, sh.fspec, sh.fold);
+            stamps_begin(P, (int)blocks, 12, st);
+        }
+#endif
+        P.err = device_error_word(L);
+        {   // k_stage01p: one queue of tile groups per chunk; k_stage01d: one queue of tiles per layer-1 node (or per chunk)
+            WorkQueue& wq = direct ? (sh.wgq ? L.wq_direct_wg : L.wq_direct) : L.wq_front;
+            P.work_ctr = work_counters(wq, sh.queue_ctrs, st);
+            P.work_base = wq.base;
+            wq.base += (uint32_t)sh.tile_groups;      // what this launch adds to every counter (StageParams::work_ctr)
+        }
+#ifdef HIGSFA_DIAG
+        if (const char* e = getenv("HIGSFA_WHATIF")) P.whatif = atoi(e);
+#endif
+        hipLaunchKernelGGL(fn, blocks, sh.threads, sh.lds, st, P, Q);
+#ifdef HIGSFA_DIAG
+        if (P.stamps) front_stamps_report(P.n_chunks, st);
+#endif
     }
-    bool launch_splitm(const HostStage& s, const StageParams& P, int n_tiles, hipStream_t st) {
-        if (!splitm_takes(s, n_tiles)) return false;
-        const int T = n_tiles >= 2 * 256 / std::max(1, s.n_nodes) ? 2 : 1;
-        const int groups = (n_tiles + T - 1) / T;
-        const int nwv = std::max(s.mt1, s.has_exp ? s.mt2 : 1);
-        const size_t lds_bytes = (size_t)std::max(1, s.nf) * s.mt1 * T * 1024;
-        const unsigned grid = (unsigned)(groups * s.n_nodes);
-        if (s.rem4) {
-            if (T == 2) hipLaunchKernelGGL((k_stage_splitm<2, true>), grid, nwv * 64, lds_bytes, st, P, s.mt1, s.mt2);
-            else hipLaunchKernelGGL((k_stage_splitm<1, true>), grid, nwv * 64, lds_bytes, st, P, s.mt1, s.mt2);
-        } else if (T == 2)
-            hipLaunchKernelGGL(k_stage_splitm<2>, grid, nwv * 64, lds_bytes, st, P, s.mt1, s.mt2);
+
+    // layer 0 alone: k_stage0p (persistent) or k_stage0
+    void launch_front(const CallStep& step, const HostStage& s, const StageDev& d, StageParams& P, const void* x, int x_dtype, int64_t ldx, int64_t n, hipStream_t st) {
+        const CallShape& sh = step.sh;
+        front_params(step, s, d, P, x, ldx, n);
+        const bool persistent = step.route == Route::Front0p;
+        StageFn fn = persistent ? pick_stage0p(x_dtype) : pick_stage0(s.mt1, s.mt2, sh.T, x_dtype);
+        const int occ = persistent ? resident_blocks(fn, sh.threads, sh.lds) : 0;      // (k_stage0: one workgroup per tile group and chunk)
+        if (persistent) P.tile_parts = step_tile_parts(step, occ);
+        const int64_t blocks = step_blocks(step, P.tile_parts);
+        debug_line(step, occ, P.tile_parts);
+        set_lds_limit(fn, sh.lds);
+        hipLaunchKernelGGL(fn, (unsigned)blocks, sh.threads, sh.lds, st, P);
+    }
+
+    void launch_splitm(const CallStep& step, const HostStage& s, const StageParams& P, hipStream_t st) {
+        const CallShape& sh = step.sh;
+        const unsigned grid = (unsigned)step_blocks(step, 1);
+        debug_line(step, 0, 1);
+        if (sh.rem4) {
+            if (sh.T == 2) hipLaunchKernelGGL((k_stage_splitm<2, true>), grid, sh.threads, sh.lds, st, P, s.mt1, s.mt2);
+            else hipLaunchKernelGGL((k_stage_splitm<1, true>), grid, sh.threads, sh.lds, st, P, s.mt1, s.mt2);
+        } else if (sh.T == 2)
+            hipLaunchKernelGGL(k_stage_splitm<2>, grid, sh.threads, sh.lds, st, P, s.mt1, s.mt2);
         else
-            hipLaunchKernelGGL(k_stage_splitm<1>, grid, nwv * 64, lds_bytes, st, P, s.mt1, s.mt2);
-        return true;
+            hipLaunchKernelGGL(k_stage_splitm<1>, grid, sh.threads, sh.lds, st, P, s.mt1, s.mt2);
     }
 
     // an ordinary layer on k_stage: node groups whose weights sit in LDS, swept over the batch's tile groups
-    void launch_stage(const HostStage& s, StageParams& P, int n_tiles, int si, hipStream_t st) {
-        // node groups sized so a group's weights are ~64 KiB of LDS (always >= 1 node)
-        const int npg = std::max(1, std::min(s.n_nodes, (s.sum_in ? plan_->opt.sum_lds_kib : kWeightLdsKiB) / std::max(1, s.node_blocks)));
-        const int n_groups = (s.n_nodes + npg - 1) / npg;
-        static const int shapes[][2] = {{8, 2}, {8, 1}, {4, 2}, {4, 1}};      // 8 x 1 before 4 x 2 (layer 7: 20.6 -> 19.0 us)
-        const Shape sh = sweep_shape(shapes, n_tiles, n_groups);
-        const int nw = sh.nw, T = sh.T;
-        const int tile_groups = (n_tiles + nw * T - 1) / (nw * T);
-        const size_t lds_bytes = (size_t)npg * s.node_blocks * 1024 + (size_t)npg * s.bias_floats * 4 + (size_t)npg * s.kb1 * 8;
-        const int kbf = (T == 2 && s.mt1 == s.mt2 && (s.mt1 == 2 || s.mt1 == 3)) ? (s.kb1 == 4 ? 4 : (s.kb1 == 3 && s.rem4 ? 3 : 0)) : 0;
-        const bool fs = s.has_exp && s.nf == 2 && s.funcs[0].kind == E_IDENTITY && s.funcs[1].kind == E_ABS_POW && !plan_->opt.no_fspec;
+    void launch_stage(const CallStep& step, const HostStage& s, StageParams& P, hipStream_t st) {
+        const CallShape& sh = step.sh;
         // slot-major packed input (plan_slot_major): the whole-visit-prefetch instantiation reads it at a fixed code position; any
         // other shape of this call (one tile per wave: small batches) takes the generic remainder-tile loop, which tests per block
-        StageFn fn = s.pk_kbi >= 0 ? (kbf == 3 ? pick_stage(s.mt1, s.mt2, T, s.rem4, kbf, fs, s.pk_kbi) : nullptr) : pick_stage(s.mt1, s.mt2, T, s.rem4, kbf, fs);
-        if (!fn) fn = pick_stage(s.mt1, s.mt2, T, s.rem4, 0, false);
-        if (s.sum_in) fn = pick_stage_sum(s.mt1, s.mt2, T, fs);      // hoisted first affine: hg_fused_sum.hip
-        const int tile_parts = sweep_tile_parts(n_groups, tile_groups, resident_blocks(fn, nw * 64, lds_bytes));
-        P.nodes_per_group = npg;
-        P.nodes_per_wg = npg;
-        P.n_chunks = n_groups;
-        P.pair_chunks = (s.pack_out && !s.pack_soa && npg == 2 && n_groups % 16 == 0) ? 1 : 0;
-        P.tile_groups = tile_groups;
-        P.tile_parts = tile_parts;
-        const int64_t blocks = (int64_t)((P.n_chunks + 7) / 8) * 8 * tile_parts;
-        if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
+        StageFn fn = s.pk_kbi >= 0 ? (sh.kbf == 3 ? pick_stage(s.mt1, s.mt2, sh.T, s.rem4, sh.kbf, sh.fs, s.pk_kbi) : nullptr) : pick_stage(s.mt1, s.mt2, sh.T, s.rem4, sh.kbf, sh.fs);
+        if (!fn) fn = pick_stage(s.mt1, s.mt2, sh.T, s.rem4, 0, false);
+        if (s.sum_in) fn = pick_stage_sum(s.mt1, s.mt2, sh.T, sh.fs);      // hoisted first affine: hg_fused_sum.hip
+        const int64_t blocks = fill_sweep(step, fn, P);
+        P.pair_chunks = sh.pair_chunks ? 1 : 0;
 #ifdef HIGSFA_DIAG
+        const int si = step.stage, T = sh.T, kbf = sh.kbf;
         const bool stamp_kbf3 = s.mt1 == 3 && s.mt2 == 3 && T == 2 && s.rem4 && kbf == 3;
         if (plan_->opt.stamp_stage == si && !s.sum_in && (stamp_kbf3 || (s.mt1 == s.mt2 && (s.mt1 == 4 || s.mt1 == 3) && T == 2 && !s.rem4 && kbf == 0))) {
             // diagnostic instantiation with s_memtime stamps (never used in timed runs)
@@ -1260,75 +1151,40 @@ private:
             stamps_begin(P, (int)blocks, 8, st);
         }
 #endif
-        set_lds_limit(fn, lds_bytes);
+        set_lds_limit(fn, sh.lds);
 #ifdef HIGSFA_DIAG
         if (const char* e = getenv("HIGSFA_WHATIF")) P.whatif = atoi(e);
 #endif
-        hipLaunchKernelGGL(fn, (unsigned)blocks, nw * 64, lds_bytes, st, P);
+        hipLaunchKernelGGL(fn, (unsigned)blocks, sh.threads, sh.lds, st, P);
 #ifdef HIGSFA_DIAG
-        if (P.stamps) stage_stamps_report(si, blocks, nw, st);
+        if (P.stamps) stage_stamps_report(si, blocks, sh.nw, st);
 #endif
     }
 
-    // ---- summed links ----
-    // Stage si reaches launch_stage in a call of n_tiles: run_range's dispatch, asked without launching anything
-    bool on_sweep(int si, int n_tiles, int sub_set) const {
-        if (si < 0 || si >= (int)plan_->stages.size()) return false;
-        if (plan_->tail_begin >= 0 && si >= plan_->tail_start(n_tiles)) return false;
-        for (const SubRun& r : plan_->sub_runs)
-            if (r.set == sub_set && r.begin <= si && si < r.begin + r.len && plan_->sub_run_pays(r, n_tiles)) return false;
-        const HostStage& s = plan_->stages[si];
-        return s.kind == 0 && !s.from_x && !splitm_takes(s, n_tiles);
-    }
-    // pairs whose fragments a workgroup keeps in LDS: HIGSFA_SUM_LDS KiB as for k_stage_sum's node groups, at least one pair, at most 144 KiB
-    int pair_group(const HostStage& s) const {
-        const int kib = 2 * std::max(1, s.node_blocks);
-        return std::max(1, std::min(plan_->opt.sum_lds_kib, 144) / kib);
-    }
-    static int pair_waves(int n_tiles) {
-        int nw = 8;
-        while (nw * kPairTiles > std::max(n_tiles, 1) && nw > 1) nw >>= 1;
-        return nw;
-    }
-    // The link si -> si + 1 is stored summed in this call: the plan has pairs for it, both stages run through launch_stage, the producer has
-    // the shape k_stage_sum_pair is built for (a hoisted stage itself, 4 x 4 tiles, compile-time expansion) and enough work in pair groups
-    // (sweep_shape's criterion on pair groups x tile groups; FusedOptions::pair_min_wgs)
-    bool link_summed(int si, int n_tiles, int sub_set, bool in_summed) const {
-        if (si + 1 >= (int)plan_->stages.size()) return false;
-        const HostStage& s = plan_->stages[si];
-        const HostStage& p = plan_->stages[si + 1];
-        if (p.pair_kids.empty() || !s.sum_in || s.n_nodes != 2 * p.n_nodes) return false;
-        if (!in_summed && (s.pair_kids.empty() || s.kb1 != 2 * s.mt1)) return false;      // the kernel's two input forms: one child per node, or two
-        const bool fs = s.has_exp && s.nf == 2 && s.funcs[0].kind == E_IDENTITY && s.funcs[1].kind == E_ABS_POW && !plan_->opt.no_fspec;
-        if (!fs || s.mt1 != 4 || s.mt2 != 4 || p.mt1 != 4 || s.mto != 4 || s.pack_out || s.rem4) return false;
-        if (!on_sweep(si, n_tiles, sub_set) || !on_sweep(si + 1, n_tiles, sub_set)) return false;
-        const int ppg = pair_group(s), nw = pair_waves(n_tiles);
-        const int64_t n_groups = (p.n_nodes + ppg - 1) / ppg, tile_groups = (n_tiles + nw * kPairTiles - 1) / (nw * kPairTiles);
-        return n_groups * tile_groups >= plan_->opt.pair_min_wgs;
-    }
-    // launch_stage for the producer of a summed link: pair groups in the place of node groups, one tile set stored per node of `parent`
-    void launch_stage_pair(const HostStage& s, const HostStage& parent, const StageDev& pd, StageParams& P, int n_tiles, int si, hipStream_t st) {
-        const int ppg = std::min(pair_group(s), parent.n_nodes), nw = pair_waves(n_tiles), T = kPairTiles;
-        const int n_groups = (parent.n_nodes + ppg - 1) / ppg;
-        const int tile_groups = (n_tiles + nw * T - 1) / (nw * T);
-        const size_t lds_bytes = (size_t)2 * ppg * ((size_t)s.node_blocks * 1024 + (size_t)s.bias_floats * 4 + (size_t)P.kb1 * 8) + (size_t)ppg * 256;
-        StageFn fn = pick_stage_sum_pair(T);
-        if (!fn) fail(HG_ERR_STATE, "internal: no pair kernel of %d tiles per wave", T);
+    // launch_stage for the producer of a summed link: one tile set stored per node of `parent`
+    void launch_stage_pair(const CallStep& step, const HostStage& s, const HostStage& parent, const StageDev& pd, StageParams& P, hipStream_t st) {
+        const CallShape& sh = step.sh;
+        StageFn fn = pick_stage_sum_pair(sh.T);
+        if (!fn) fail(HG_ERR_STATE, "internal: no pair kernel of %d tiles per wave", sh.T);
         P.pair_kids = (const int2*)pd.pair_kids.p;
         P.pair_bias = (const float*)pd.bias.p;      // the parent stage's own floats (not bias_pre)
         P.pair_bias_floats = parent.bias_floats;
         P.n_pairs = parent.n_nodes;
         P.nb_out = parent.n_nodes * s.mto;
-        P.nodes_per_group = ppg;
-        P.nodes_per_wg = ppg;
-        P.n_chunks = n_groups;
-        P.tile_groups = tile_groups;
-        P.tile_parts = sweep_tile_parts(n_groups, tile_groups, resident_blocks(fn, nw * 64, lds_bytes));
-        const int64_t blocks = (int64_t)((n_groups + 7) / 8) * 8 * P.tile_parts;
-        if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
-        set_lds_limit(fn, lds_bytes);
-        if (plan_->opt.debug) fprintf(stderr, "[pair stage %d] pairs %d per group %d shape %dx%d lds %zu tile_groups %d parts %d kids in %d\n", si, parent.n_nodes, ppg, nw, T, lds_bytes, tile_groups, P.tile_parts, P.n_kids);
-        hipLaunchKernelGGL(fn, (unsigned)blocks, nw * 64, lds_bytes, st, P);
+        const int64_t blocks = fill_sweep(step, fn, P);
+        hipLaunchKernelGGL(fn, (unsigned)blocks, sh.threads, sh.lds, st, P);
+    }
+
+    void launch_prod(const CallStep& step, const HostStage& s, const StageDev& d, StageParams& P, hipStream_t st) {
+        StageFn fn = pick_prod(s.mt1, s.mt2, step.sh.T);
+        const int64_t blocks = fill_sweep(step, fn, P);
+        P.etab = (const int2*)d.etab.p;
+        P.neb = s.neb;
+        P.nk_last = s.nk_last;
+        P.has_clip = s.has_clip ? 1 : 0;
+        P.clip_lo = s.clip_lo;
+        P.clip_hi = s.clip_hi;
+        hipLaunchKernelGGL(fn, (unsigned)blocks, step.sh.threads, step.sh.lds, st, P);
     }
 
     // fragment order -> the caller's row-major y (where no top-of-hierarchy launch wrote it)
@@ -1343,40 +1199,6 @@ private:
                                (double*)y, ldy, n, (int)y_cols);
         else
             fail(HG_ERR_ARG, "output dtype must be f32 or f64");
-    }
-
-    void launch_prod(const HostStage& s, const StageDev& d, StageParams& P, int n_tiles, int si, hipStream_t st) {
-        // per-wave z image: T * mt1 KiB; the node group takes what is left of ~52 KiB (three workgroups per CU: the product
-        // columns are LDS reads and multiplies between short MFMA runs, which only other waves can cover), more if one node needs it.
-        // (The shape is chosen over single nodes: the node group follows from it.)
-        static const int shapes[][2] = {{8, 2}, {4, 2}, {4, 1}};
-        const Shape sh = sweep_shape(shapes, n_tiles, s.n_nodes);
-        const int nw = sh.nw, T = sh.T;
-        const size_t zs_bytes = (size_t)nw * T * s.mt1 * 1024, et_bytes = (size_t)s.neb * 128;
-        const size_t per_node = (size_t)s.node_blocks * 1024 + (size_t)s.bias_floats * 4 + (size_t)s.kb1 * 8;
-        const size_t fixed = zs_bytes + et_bytes;
-        const int npg = (int)std::max<size_t>(1, std::min<size_t>(s.n_nodes, fixed + per_node <= 52 * 1024 ? (52 * 1024 - fixed) / per_node : 1));
-        const int n_groups = (s.n_nodes + npg - 1) / npg;
-        const int tile_groups = (n_tiles + nw * T - 1) / (nw * T);
-        const size_t lds_bytes = (size_t)npg * per_node + et_bytes + zs_bytes;
-        StageFn fn = pick_prod(s.mt1, s.mt2, T);
-        const int tile_parts = sweep_tile_parts(n_groups, tile_groups, resident_blocks(fn, nw * 64, lds_bytes));
-        P.nodes_per_group = npg;
-        P.nodes_per_wg = npg;
-        P.n_chunks = n_groups;
-        P.tile_groups = tile_groups;
-        P.tile_parts = tile_parts;
-        P.etab = (const int2*)d.etab.p;
-        P.neb = s.neb;
-        P.nk_last = s.nk_last;
-        P.has_clip = s.has_clip ? 1 : 0;
-        P.clip_lo = s.clip_lo;
-        P.clip_hi = s.clip_hi;
-        const int64_t blocks = (int64_t)((n_groups + 7) / 8) * 8 * tile_parts;
-        if (blocks > 0x7fffffffll) fail(HG_ERR_ARG, "batch too large");
-        set_lds_limit(fn, lds_bytes);
-        if (plan_->opt.debug) fprintf(stderr, "[prod stage %d] nodes %d mt1 %d mt2 %d neb %d shape %dx%d npg %d node_groups %d tile_groups %d parts %d\n", si, s.n_nodes, s.mt1, s.mt2, s.neb, nw, T, npg, n_groups, tile_groups, tile_parts);
-        hipLaunchKernelGGL(fn, (unsigned)blocks, nw * 64, lds_bytes, st, P);
     }
 
 #ifdef HIGSFA_DIAG
@@ -1560,12 +1382,7 @@ private:
 }  // namespace
 
 std::unique_ptr<Executor> make_fused_executor(const TNode& root, std::string* why_not) {
-    fused::FusedOptions opt = fused::FusedOptions::from_env();
-    opt.hoist = getenv("HIGSFA_NO_HOIST") == nullptr;      // (an executor's switch, not the planner's: DESIGN.md §9)
-    opt.fold01 = getenv("HIGSFA_NO_FOLD01") == nullptr;    // likewise
-    opt.fold01_pack = opt.fold01 && getenv("HIGSFA_NO_FOLD01_PACK") == nullptr;      // the folded link's one-row k-steps packed
-    opt.pair = opt.hoist && getenv("HIGSFA_NO_PAIR") == nullptr;      // summed links ride on the hoisted ones
-    auto plan = fused::build_fused_plan(root, opt, why_not);
+    auto plan = fused::build_fused_plan(root, fused::executor_options(), why_not);
     if (!plan) return nullptr;
     return std::make_unique<FusedExecutor>(std::move(plan));
 }

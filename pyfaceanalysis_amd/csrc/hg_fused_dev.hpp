@@ -6,17 +6,13 @@
 
 #include <algorithm>
 
-#include "hg_fused_plan.hpp"      // kMaxMT, kMaxFuncs, kMaxTail, DChunk, DRun: shared with the host-only planner
+#include "hg_fused_call.hpp"      // the host-only units: the plan (kMaxMT, kMaxFuncs, kMaxTail, DChunk, DRun) and the call plan (kDoubleBuffer01, kPairTiles, ...)
 
 namespace hg {
 namespace fused {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// k_stage01p: two LDS tiles (one barrier per tile group) or one (two barriers, half the LDS).  With the packed
-// tile layout (128 + 4 words per row) both fit three workgroups per CU and measure the same (152-154 us).
-constexpr bool kDoubleBuffer01 = true;
 
 struct StageParams {
     const f32x4* afrag;   // [node][ A1: kb1 x MT1 | A2: MT1 x nf x MT2 ] blocks of 64 x f32x4
@@ -517,17 +513,16 @@ typedef void (*StageFn2)(StageParams, StageParams);
 StageFn pick_stage0(int mt1, int mt2, int T, int x_dtype);            // hg_fused_front.hip
 StageFn pick_stage0p(int x_dtype);
 StageFn2 pick_stage01p(int x_dtype, bool stamp, bool rem4, bool fspec, bool fold = false, bool scalar = false, bool pack = false);      // fold: FusedPlan::fold01 (REM4 forms only); scalar: rows without 16-byte loads (fold only); pack: FusedPlan::fold01_pack (fold only)
-int stage01p_tiles(bool rem4, bool fspec);
 StageFn2 pick_stage01d(int x_dtype, bool stamp, bool wgq, bool fold = false, bool pack = false);       // every wave on its own, no LDS tile (hg_fused_front.hip)
 StageFn pick_igsfa(int ms, int mo, int T, int kb1);                   // hg_fused_igsfa.hip
 StageFn pick_igfold(int mo, int T, bool fs = false);
 StageFn pick_prod(int mt1, int mt2, int T);                           // hg_fused_prod.hip
 StageFn pick_stage_sum(int mt1, int mt2, int T, bool fs);             // hg_fused_sum.hip: k_stage for a layer whose first affine was hoisted
 StageFn pick_stage_sum_pair(int T);                                        // ... storing its nodes' tiles summed per node of the layer above (4 x 4 tiles, compile-time expansion)
-constexpr int kPairTiles = 1;                                         // batch tiles per wave of k_stage_sum_pair (two do not fit 128 registers)
-void launch_igfold_split(const StageParams& P, int mo, int n_tiles, hipStream_t st);                                                          // hg_fused_igsfa.hip
+// (grids, workgroups and LDS of these two: the call plan's, CallShape)
+void launch_igfold_split(const StageParams& P, int mo, int T, unsigned grid, int threads, size_t lds, hipStream_t st);                       // hg_fused_igsfa.hip
 void launch_im2frag(const void* x, int x_dtype, int64_t ldx, int64_t n_rows, int n_tiles, int nb, const int32_t* gcol, f32x4* out,
-                    int vec4, hipStream_t st);
+                    int vec4, unsigned grid, hipStream_t st);
 
 // 4 consecutive input elements -> 4 floats (16-byte / 4-byte / 32-byte loads)
 template <typename XT> struct Vec4Load;

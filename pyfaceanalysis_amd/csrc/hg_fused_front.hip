@@ -1055,11 +1055,6 @@ StageFn pick_stage0(int mt1, int mt2, int T, int x_dtype) {
 StageFn pick_stage0p(int x_dtype) {
     return x_dtype == HG_U8 ? (StageFn)k_stage0p<4, uint8_t> : x_dtype == HG_F32 ? (StageFn)k_stage0p<4, float> : (StageFn)k_stage0p<4, double>;
 }
-// Tiles per pass of the instantiation pick_stage01p returns (the host sizes LDS and the group count with it): the
-// compile-time-expansion form takes ONE tile per pass at four waves per SIMD (124 VGPRs; 146 us against 153 with two
-// tiles at three waves), the generic form two tiles at three waves (168 VGPRs).
-int stage01p_tiles(bool rem4, bool fspec) { return fspec ? 1 : 2; }
-
 template <typename XT>
 static StageFn2 pick_stage01p_pack(bool fspec, bool scalar) {      // the folded REM4 forms with the one-row k-steps packed
     if (scalar) return fspec ? (StageFn2)k_stage01p<XT, false, true, 1, 1, true, true, true> : (StageFn2)k_stage01p<XT, false, true, 2, 0, true, true, true>;

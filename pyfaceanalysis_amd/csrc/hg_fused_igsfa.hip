@@ -369,15 +369,11 @@ __global__ void __launch_bounds__(512) k_igfold_split(StageParams P, int mo_n) {
         if (tile[t] < P.n_tiles) P.out[((size_t)tile[t] * P.nb_out + (size_t)node * mo_n + w) * 64 + lane] = y[t];
 }
 
-void launch_igfold_split(const StageParams& P, int mo, int n_tiles, hipStream_t st) {
-    const int T = n_tiles >= 2 ? 2 : 1;
-    const int groups = (n_tiles + T - 1) / T;
-    const int nwv = P.kb1 > mo ? P.kb1 : mo;
-    const size_t lds = (size_t)P.nf * P.kb1 * T * 1024;
+void launch_igfold_split(const StageParams& P, int mo, int T, unsigned grid, int threads, size_t lds, hipStream_t st) {
     if (T == 2)
-        hipLaunchKernelGGL(k_igfold_split<2>, (unsigned)(groups * P.n_nodes), nwv * 64, lds, st, P, mo);
+        hipLaunchKernelGGL(k_igfold_split<2>, grid, threads, lds, st, P, mo);
     else
-        hipLaunchKernelGGL(k_igfold_split<1>, (unsigned)(groups * P.n_nodes), nwv * 64, lds, st, P, mo);
+        hipLaunchKernelGGL(k_igfold_split<1>, grid, threads, lds, st, P, mo);
 }
 
 StageFn pick_igfold(int mo, int T, bool fs) {
@@ -408,9 +404,7 @@ StageFn pick_igsfa(int ms, int mo, int T, int kb1) {   // ms <= mo (the slow fea
 }
 
 void launch_im2frag(const void* x, int x_dtype, int64_t ldx, int64_t n_rows, int n_tiles, int nb, const int32_t* gcol, f32x4* out,
-                    int vec4, hipStream_t st) {
-    const int64_t waves = (int64_t)n_tiles * nb;
-    const unsigned grid = (unsigned)((waves + 3) / 4);
+                    int vec4, unsigned grid, hipStream_t st) {
     if (x_dtype == HG_U8)
         hipLaunchKernelGGL(k_im2frag<uint8_t>, grid, 256, 0, st, (const uint8_t*)x, ldx, n_rows, n_tiles, nb, gcol, out, vec4);
     else if (x_dtype == HG_F32)

@@ -242,8 +242,9 @@ def igsfa_after_ordinary(seed=0):
 
 
 def build_driver(exe, extra_flags=()):
-    """tests/hoist_plan_driver.cpp with plain g++ against hg_tree.cpp and hg_fused_plan.cpp only.  Returns the finished subprocess."""
+    """tests/hoist_plan_driver.cpp with plain g++ against hg_tree.cpp and the host-only plan unit (hg_fused_plan.cpp, hg_fused_call.cpp)
+    only.  Returns the finished subprocess."""
     cmd = ["g++", "-std=c++17", "-O1", "-g"] + list(extra_flags) + ["-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + CSRC,
            "-I" + os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "hoist_plan_driver.cpp"), os.path.join(CSRC, "hg_tree.cpp"),
-           os.path.join(CSRC, "hg_fused_plan.cpp"), "-o", str(exe)]
+           os.path.join(CSRC, "hg_fused_plan.cpp"), os.path.join(CSRC, "hg_fused_call.cpp"), "-o", str(exe)]
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)

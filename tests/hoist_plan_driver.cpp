@@ -1,15 +1,24 @@
-// The hoist pass of the fused planner without a device (host only; links hg_tree.cpp and hg_fused_plan.cpp and nothing of HIP).
+// The hoist pass of the fused planner and the executor's call plan without a device (host only; links hg_tree.cpp, hg_fused_plan.cpp and
+// hg_fused_call.cpp and nothing of HIP).
 //   hoist_plan_driver FILE...          for every blob: the stages whose first affine was hoisted, then the plan build_fused_plan makes
 //                                      with FusedOptions::hoist on (tests/plan_digest.hpp), or the reason it refuses
 //   hoist_plan_driver --dump FILE      the normal form after hoist_first_affines, in full float64: per hoisted parent node its children
 //                                      and bias vector, per child node the folded second affine
 //   hoist_plan_driver --links FILE...  for every blob, per node of a hoisted stage: stage, node, columns of z, children in the order
 //                                      their tiles are added
+//   hoist_plan_driver --call TILES[,TILES...] [--occ K] [--no-vec4] FILE...
+//                                      for every blob and tile count the call plan (hg_fused_call.hpp) of the plan the executor makes:
+//                                      per step its route, first stage, stages covered, summed input, sub-tree set and grid, then
+//                                      the step's HIGSFA_DEBUG line with tile_parts at K resident workgroups per CU (default 1)
+//   hoist_plan_driver --rule parts GROUPS TILE_GROUPS OCC | --rule sweep TILES GROUPS
+//                                      sweep_tile_parts; the waves x tiles of the ordinary sweep
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "hg_fused_call.hpp"
 #include "hg_fused_plan.hpp"
 #include "hg_fused_stages.hpp"
 #include "plan_digest.hpp"
@@ -90,9 +99,78 @@ static int links(int argc, char** argv) {
     return 0;
 }
 
+static const char* base_name(const char* path) {
+    const char* base = path;
+    for (const char* c = path; *c; ++c)
+        if (*c == '/') base = c + 1;
+    return base;
+}
+
+// --call: the executor's plan of every blob (hg::fused::executor_options) and, per tile count, what a call of float32 rows of the
+// flow's own width launches
+static int call(int argc, char** argv) {
+    using namespace hg::fused;
+    std::vector<int> tiles;
+    for (const char* c = argv[2]; *c;) {
+        tiles.push_back(atoi(c));
+        while (*c && *c != ',') ++c;
+        if (*c) ++c;
+    }
+    int occ = 1, i = 3;
+    FrontInput fi;
+    for (; i < argc && argv[i][0] == '-'; ++i) {
+        if (!strcmp(argv[i], "--occ") && i + 1 < argc) occ = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--no-vec4")) fi.vec4_ok = false;
+        else return 2;
+    }
+    std::vector<CallStep> steps;
+    char line[512];
+    for (; i < argc; ++i) {
+        const auto b = slurp(argv[i]);
+        printf("== %s\n", base_name(argv[i]));
+        try {
+            const auto tree = hg::parse_blob(b.data(), b.size());
+            std::string why;
+            const auto plan = build_fused_plan(*tree, executor_options(), &why);
+            if (!plan) {
+                printf("refused: %s\n", why.c_str());
+                continue;
+            }
+            fi.ldx = tree->in_dim;
+            printf("plan stages %zu fuse01 %d fold01 %d tail_begin %d\n", plan->stages.size(), (int)plan->fuse01, (int)plan->fold01, plan->tail_begin);
+            for (int t : tiles) {
+                plan_call(*plan, t, fi, steps);
+                printf("call tiles %d steps %zu\n", t, steps.size());
+                for (const CallStep& st : steps) {
+                    const int parts = step_tile_parts(st, occ);
+                    printf("step %s stage %d covered %d summed %d set %d blocks %lld | %s\n", route_name(st.route), st.stage, st.covered, (int)st.in_summed,
+                           st.sub_run >= 0 ? plan->sub_runs[st.sub_run].set : -1, st.route == Route::Top ? 1ll : (long long)step_blocks(st, parts),
+                           format_step(*plan, st, occ, parts, line, sizeof line));
+                }
+            }
+        } catch (const hg::Error& e) {
+            printf("failed: %s\n", e.what());
+        }
+    }
+    return 0;
+}
+
+// --rule: one launch rule at given values
+static int rule(int argc, char** argv) {
+    using namespace hg::fused;
+    if (argc == 6 && !strcmp(argv[2], "parts")) return printf("%d\n", sweep_tile_parts(atoi(argv[3]), atoi(argv[4]), atoi(argv[5]))) < 0;
+    if (argc == 5 && !strcmp(argv[2], "sweep")) {
+        const WavesTiles w = stage_sweep_shape(atoi(argv[3]), atoi(argv[4]));
+        return printf("%dx%d\n", w.nw, w.T) < 0;
+    }
+    return 2;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "--dump")) return dump(argv[2]);
     if (argc >= 3 && !strcmp(argv[1], "--links")) return links(argc, argv);
+    if (argc >= 4 && !strcmp(argv[1], "--call")) return call(argc, argv);
+    if (argc >= 3 && !strcmp(argv[1], "--rule")) return rule(argc, argv);
     hg::fused::FusedOptions opt = hg::fused::FusedOptions::from_env();
     opt.hoist = true;
     for (int i = 1; i < argc; ++i) {

@@ -225,6 +225,60 @@ def mixed_net(seed=0):
     return [sb0, _plain_layer(rng, 64, 4, 4, 8), sb1, l1, sb2, _ig_layer(rng, rng_v, 4, 72, 10, 14, IG_FUNCS), sb3, _plain_layer(rng, 1, 96, 20, 17)]
 
 
+# ------------------------------------------------------------------------------------------------- what a call must launch, by design
+def stage_table(name):
+    """Per product / iGSFA stage of the net's full plan, from the data above (pinned by the host test): dicts with the stage index,
+    kind, node count and what decides the shape."""
+    if name.startswith("prod") and name != "prod_uneven":
+        mt1, mt2 = int(name[4]), int(name[5])
+        return [dict(kind="prod", stage=1, nodes=64, mt1=mt1, mt2=mt2)]
+    if name == "prod_uneven":
+        return [dict(kind="prod", stage=1, nodes=64, mt1=2, mt2=1), dict(kind="prod", stage=2, nodes=6, mt1=1, mt2=1)]
+    if name.startswith("ig_"):
+        return [dict(kind="igsfa", stage=i + 1, nodes=n, ms=ms, mo=mo, kb1=kb, folded=False) for i, (n, ms, mo, kb) in enumerate(IG_UNFOLDED[name[3:]]["want"])]
+    if name.startswith("igfold"):
+        return [dict(kind="igsfa", stage=i + 1, nodes=n, ms=mo, mo=mo, kb1=kb, folded=True) for i, (n, mo, kb) in enumerate(IG_FOLDED[int(name[6:])]["want"])]
+    assert name == "mixed"
+    return [dict(kind="prod", stage=1, nodes=16, mt1=1, mt2=2), dict(kind="igsfa", stage=2, nodes=4, ms=2, mo=2, kb1=8, folded=True)]
+
+
+def expected_launches(name, rows):
+    """What the product and iGSFA debug lines of one full call must say: (kind, stage, nodes, shape) per launch, and whether an iGSFA
+    shape is the fallback.  A folded layer of at most 8 nodes runs k_igfold_split up to 16384 (node, tile) pairs: no such line.  From
+    prod_shape / ig_shape, the restated rules: the host test holds the library's own rule to it, the GPU test its launches."""
+    t = tiles(rows)
+    out = []
+    for s in stage_table(name):
+        if s["kind"] == "prod":
+            out.append(dict(kind="prod", stage=s["stage"], nodes=s["nodes"], shape=prod_shape(t, s["nodes"]), widths=(s["mt1"], s["mt2"])))
+        elif not (s["folded"] and s["nodes"] <= 8 and s["nodes"] * t <= 16384):
+            nw, tt, fallback = ig_shape(t, s["nodes"], s["kb1"], s["folded"])
+            out.append(dict(kind="igsfa", stage=s["stage"], nodes=s["nodes"], shape=(nw, tt), fallback=fallback, widths=(s["ms"], s["mo"]),
+                            kb1=s["kb1"], folded=s["folded"]))
+    return out
+
+
+PROD_LINE = r"\[prod stage (\d+)\] nodes (\d+) mt1 (\d+) mt2 (\d+) neb (\d+) shape (\d+)x(\d+) npg (\d+) node_groups (\d+) tile_groups (\d+) parts (\d+)"
+IG_LINE = r"\[igsfa stage (\d+)\] nodes (\d+) kb1 (\d+) shape (\d+)x(\d+) occ (\d+) lds (\d+) tile_groups (\d+) parts (\d+)"
+# one HIGSFA_DEBUG line per launch of a call; the stages it covers: "[front]" layers 0 and 1, "[front0]" layer 0, "... stage i]" stage i
+# and, where the line says "layers k", the k - 1 above it
+STEP_LINE = r"\[(front0?|(gather|sweep|splitm|igsplit|igsfa|prod|pair|subtree|top) stage (\d+))\]( layers (\d+))?"
+
+
+def covered_stages(text):
+    """The stages the debug lines of ONE call name, launch by launch, in the order they were written."""
+    import re
+    out = []
+    for ln in text.splitlines():
+        m = re.match(STEP_LINE, ln)
+        if not m:
+            continue
+        first = int(m.group(3)) if m.group(3) is not None else 0
+        n = 2 if m.group(1) == "front" else int(m.group(5)) if m.group(5) else 1
+        out += list(range(first, first + n))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------------- the list
 def nets():
     """{name: (constructor, switches the handle is planned under)} of every net of the per-node, batch-independence and shape tests."""

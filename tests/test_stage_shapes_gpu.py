@@ -4,8 +4,9 @@ launch_igsfa (csrc/hg_fused.hip) pick — held to what the ordinary stage kind i
 by layer, and a row's bits independent of the batch it travels in.  Nets and batch sizes: tests/stage_shape_cases.py, whose premises
 tests/test_stage_shapes_plan_host.py pins on the CPU.
 
-Every handle is planned under HIGSFA_DEBUG, so each launch of a product or iGSFA stage writes one line ("[prod stage i] ... shape
-AxB ..." / "[igsfa stage i] ... shape AxB ..."; k_igfold_split, which has one shape, writes none).  The tests read the lines with
+Every handle is planned under HIGSFA_DEBUG, so every launch writes one line: a product or iGSFA sweep "[prod stage i] ... shape
+AxB ..." / "[igsfa stage i] ... shape AxB ...", every other route a line with a prefix of its own (k_igfold_split: "[igsplit stage
+i] ..."; csrc/hg_fused_call.cpp: format_step).  The tests read the product and iGSFA lines with
 capfd and hold them to the shapes the cases were sized for: a case that falls into another shape fails, it does not pass on
 another kernel.  Rows go in through the device entry, one call per batch (device_call): host rows pass through the host pipeline,
 which cuts a call into passes, and the shape would follow the pass.  Which test puts what on the device (DESIGN.md §6.9 has the table by instantiation):
@@ -21,7 +22,8 @@ which cuts a call into passes, and the shape would follow the pass.  Which test 
   the line between k_igfold_split and k_igfold           test_split_fold_line
   product after ordinary, iGSFA after product            mixed
   n_cols, input dtypes                                   test_n_cols_and_dtypes
-  the absent second tile of a T = 2 wave                 test_nan_stays_in_its_row_at_two_tiles_per_wave, every odd tile count"""
+  the absent second tile of a T = 2 wave                 test_nan_stays_in_its_row_at_two_tiles_per_wave, every odd tile count
+  one line per launch, every stage named once            test_every_launch_of_a_call_is_reported"""
 import re
 
 import numpy as np
@@ -41,8 +43,8 @@ N_REF = cases.N_REF
 NETS = cases.nets()
 NAMES = tuple(NETS)
 
-PROD_LINE = re.compile(r"\[prod stage (\d+)\] nodes (\d+) mt1 (\d+) mt2 (\d+) neb (\d+) shape (\d+)x(\d+) npg (\d+) node_groups (\d+) tile_groups (\d+) parts (\d+)")
-IG_LINE = re.compile(r"\[igsfa stage (\d+)\] nodes (\d+) kb1 (\d+) shape (\d+)x(\d+) occ (\d+) lds (\d+) tile_groups (\d+) parts (\d+)")
+PROD_LINE = re.compile(cases.PROD_LINE)
+IG_LINE = re.compile(cases.IG_LINE)
 
 
 def launches(err):
@@ -64,35 +66,8 @@ def launches(err):
     return out
 
 
-def stage_table(name):
-    """Per product / iGSFA stage of the net's full plan, from the cases file (pinned by the host test): dicts with the stage index,
-    kind, node count and what decides the shape."""
-    if name.startswith("prod") and name != "prod_uneven":
-        mt1, mt2 = int(name[4]), int(name[5])
-        return [dict(kind="prod", stage=1, nodes=64, mt1=mt1, mt2=mt2)]
-    if name == "prod_uneven":
-        return [dict(kind="prod", stage=1, nodes=64, mt1=2, mt2=1), dict(kind="prod", stage=2, nodes=6, mt1=1, mt2=1)]
-    if name.startswith("ig_"):
-        return [dict(kind="igsfa", stage=i + 1, nodes=n, ms=ms, mo=mo, kb1=kb, folded=False) for i, (n, ms, mo, kb) in enumerate(cases.IG_UNFOLDED[name[3:]]["want"])]
-    if name.startswith("igfold"):
-        return [dict(kind="igsfa", stage=i + 1, nodes=n, ms=mo, mo=mo, kb1=kb, folded=True) for i, (n, mo, kb) in enumerate(cases.IG_FOLDED[int(name[6:])]["want"])]
-    assert name == "mixed"
-    return [dict(kind="prod", stage=1, nodes=16, mt1=1, mt2=2), dict(kind="igsfa", stage=2, nodes=4, ms=2, mo=2, kb1=8, folded=True)]
-
-
-def expected_launches(name, rows):
-    """What the debug lines of one full call must say: (kind, stage, nodes, shape) per launch that writes one, and whether an iGSFA
-    shape is the fallback.  A folded layer of at most 8 nodes runs k_igfold_split up to 16384 (node, tile) pairs: no line."""
-    t = cases.tiles(rows)
-    out = []
-    for s in stage_table(name):
-        if s["kind"] == "prod":
-            out.append(dict(kind="prod", stage=s["stage"], nodes=s["nodes"], shape=cases.prod_shape(t, s["nodes"]), widths=(s["mt1"], s["mt2"])))
-        elif not (s["folded"] and s["nodes"] <= 8 and s["nodes"] * t <= 16384):
-            nw, tt, fallback = cases.ig_shape(t, s["nodes"], s["kb1"], s["folded"])
-            out.append(dict(kind="igsfa", stage=s["stage"], nodes=s["nodes"], shape=(nw, tt), fallback=fallback, widths=(s["ms"], s["mo"]),
-                            kb1=s["kb1"], folded=s["folded"]))
-    return out
+stage_table = cases.stage_table                              # what a call must launch, by design: shared with tests/test_call_plan_host.py
+expected_launches = cases.expected_launches
 
 
 def check_launches(name, rows, got):
@@ -279,6 +254,40 @@ def test_shapes_reached(case, capfd):
         assert any(r["widths"][1] == mo and r["tile_groups"] > r["parts"] > 1 for r in fold), mo
 
 
+def test_every_launch_of_a_call_is_reported(case, capfd, monkeypatch):
+    """Under HIGSFA_DEBUG every launch of a call writes one line, so the lines of ONE call name every stage exactly once, in order
+    (cases.covered_stages: "[front]" is layers 0 and 1, "... stage i] layers k" stages i .. i + k - 1); a launch that went unreported
+    would leave its stages out.  mixed_net (ordinary from the caller's rows, product, folded iGSFA, ordinary top) at 1, 2 and 27
+    tiles, and tests/pair_cases.three_pair_net with its summed links at the row count tests/test_pair_gpu.py reads them at.  The
+    product / iGSFA / pair assertions of the other tests hold on the same captures."""
+    from tests import pair_cases
+    from tests.test_pair_gpu import PAIRED
+    c = case("mixed")
+    n_stages = c.flow.info().n_stages - 1      # (the last entry is the pass that writes the caller's rows)
+    assert n_stages == len(cases.MIXED_KINDS)
+    for rows in (1, 17, 425):
+        capfd.readouterr()
+        y = device_call(c.flow, c.xd, rows)
+        err = capfd.readouterr().err
+        assert cases.covered_stages(err) == list(range(n_stages)), (rows, err[-2000:])
+        check_launches("mixed", rows, launches(err))
+        assert np.array_equal(y, c.y[:rows])
+    nodes = pair_cases.three_pair_net()
+    for k, v in dict(PAIRED, HIGSFA_DEBUG="1").items():
+        monkeypatch.setenv(k, v)
+    flow = Flow(nodes, output_dtype=np.float32)
+    n_stages = flow.info().n_stages - 1
+    assert n_stages == 5
+    xd = to_device(np.random.default_rng(950).normal(size=(130, nodes[0].input_dim)).astype(np.float32))
+    capfd.readouterr()
+    device_call(flow, xd, 130)
+    err = capfd.readouterr().err
+    flow.close()
+    assert cases.covered_stages(err) == list(range(n_stages)), err[-2000:]
+    assert "[pair stage 2]" in err and "[pair stage 3]" in err and "[pair stage 4]" not in err and "[pair stage 1]" not in err
+    assert launches(err) == []
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_rows_bit_identical_across_batch_sizes(case, name):
     """(c) A row's features do not depend on the batch it came in: rows [:n] at every size equal those rows of ONE call of 1738
@@ -294,7 +303,7 @@ def test_rows_bit_identical_across_batch_sizes(case, name):
 
 
 def test_split_fold_line(native_lib, monkeypatch, capfd):
-    """(d) A folded first layer of 8 nodes at 32768 rows (8 x 2048 tiles = 16384: k_igfold_split, no debug line) and at 32784 rows
+    """(d) A folded first layer of 8 nodes at 32768 rows (8 x 2048 tiles = 16384: k_igfold_split, no "[igsfa stage" line) and at 32784 rows
     (8 x 2049: k_igfold, one line): each against the oracle per node on 30 strided rows.  k_igfold_split adds function-major,
     k_igfold K-block-major, so the first 32768 rows need not keep their bits across the line: what they do is printed, not asserted
     (DESIGN.md §6.9 records it beside the batch-independence claim).  On either side of the line rows keep their bits.
