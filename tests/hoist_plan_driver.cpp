@@ -10,8 +10,9 @@
 //                                      for every blob and tile count the call plan (hg_fused_call.hpp) of the plan the executor makes:
 //                                      per step its route, first stage, stages covered, summed input, sub-tree set and grid, then
 //                                      the step's HIGSFA_DEBUG line with tile_parts at K resident workgroups per CU (default 1)
-//   hoist_plan_driver --rule parts GROUPS TILE_GROUPS OCC | --rule sweep TILES GROUPS
-//                                      sweep_tile_parts; the waves x tiles of the ordinary sweep
+//   hoist_plan_driver --rule parts GROUPS TILE_GROUPS OCC | --rule sweep TILES GROUPS | --rule sweepgrid TILES_MAX GROUPS_MAX
+//                                      sweep_tile_parts; the waves x tiles of the ordinary sweep; the same for tiles 1 .. TILES_MAX (a line
+//                                      each) x node groups 1 .. GROUPS_MAX
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -162,6 +163,14 @@ static int rule(int argc, char** argv) {
     if (argc == 5 && !strcmp(argv[2], "sweep")) {
         const WavesTiles w = stage_sweep_shape(atoi(argv[3]), atoi(argv[4]));
         return printf("%dx%d\n", w.nw, w.T) < 0;
+    }
+    if (argc == 5 && !strcmp(argv[2], "sweepgrid")) {
+        for (int t = 1; t <= atoi(argv[3]); ++t)
+            for (int g = 1, gn = atoi(argv[4]); g <= gn; ++g) {
+                const WavesTiles w = stage_sweep_shape(t, g);
+                printf("%dx%d%c", w.nw, w.T, g == gn ? '\n' : ' ');
+            }
+        return 0;
     }
     return 2;
 }
